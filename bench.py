@@ -9,20 +9,24 @@ gradient all-reduce (N > 1) + Adam/NoamLR.  Graphs are pre-packed and resident i
 of distinct steps is cycled so no step's activations stay in the 256 MiB Infinity Cache between uses.
 
     python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5 --full            (also every comparison leg listed below)
+    python bench.py --gpus 1 --steps 30 --warmup 5 --dump-outputs DIR (also the last timed step's results as DIR/<name>.npy)
     python bench.py --gpus N ...          (N > 1 without a launcher: starts `python -m torch.distributed.run` itself as a child)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line of at most 6 KB (contract in the task statement; tests/test_bench_line_cpu.py holds the size and
-the keys): value = whole-job queries/s of the headline preset in the library's DEFAULT arithmetic - f32 in / out /
-accumulate, every encoder multiply through three exact bf16 terms per operand (no operand bit dropped).  In the line:
+Rank 0 prints ONE JSON line of at most 6 KB (tests/test_bench_line_cpu.py holds the size and the keys): value = whole-job
+queries/s of the headline preset in the library's DEFAULT arithmetic - f32 in / out / accumulate, every encoder multiply
+through three exact bf16 terms per operand (no operand bit dropped); ms_per_step = wall time of the --steps timed steps / --steps.
+A plain run does only that: set up, warm up, time the steps, dump the outputs when asked, print the line (dp below when N > 1).
+With --full it also measures, after the timed region:
   roofline / roofline_gather   dominant MFMA kernel and the gather kernel, live HIP-event timing in situ
   cpu_baseline                 the CPU oracle on this box's host cores (rank 0 / N=1 only, bounded sample)
   f32_mfma_path, f16x2_path    the same steps with every GEMM on the f32 MFMA / on the opt-in two-f16-term form (own dtype string)
   epoch_stream                 the same training step fed from shard files on disk over >= 200 DISTINCT steps
   presets                      the other BASELINE configurations at full step size: queries/s and ms/step each
+and writes everything else - per-kernel tables, isolated rooflines, the eval path's roofline, notes - to bench_detail.json
+(next to this file) and to stderr.  In either mode:
   dp                           (N > 1) the ranks RCCL saw and the all-reduce's duration from HIP events
-Everything else - per-kernel tables, isolated rooflines, the eval path's roofline, notes - goes to bench_detail.json (next to
-this file and, when it exists, gpurun_out/) and to stderr.
 """
 import argparse
 import gc
@@ -171,8 +175,12 @@ class Runner:
             return s / pairs
         raise ValueError(kind)
 
+    keep_out = False                                      # timed(keep_last=True): the last step's scores stay in last_out
+
     def train_step(self, b):
         out = self.model(b["r"], b["p"], gpu=self.local, add_features=b["add"])
+        if self.keep_out:
+            self.last_out = out.detach()
         loss = self.loss(out, b)
         self.opt.zero_grad(set_to_none=True)
         self.RL.backward(loss)                            # loss.backward() (train_listwise.py:288) with the constant-one seed
@@ -204,8 +212,9 @@ class Runner:
         Fn.WgradOrder.settled()                           # harvest
         self.order_tuning_steps = n
 
-    def timed(self, batches, n_steps):
-        """EXACTLY n_steps optimizer steps between two fences; returns (seconds, per-step device ms list, last loss)."""
+    def timed(self, batches, n_steps, keep_last=False):
+        """EXACTLY n_steps optimizer steps between two fences; returns (seconds, per-step device ms list, last loss).
+        keep_last: the last step also leaves its scores in self.last_out (--dump-outputs)."""
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(n_steps + 1)]
         self.settle(batches)
         self.fence()
@@ -219,11 +228,14 @@ class Runner:
             marks[0].record()
             last = None
             for i in range(n_steps):
+                if i == n_steps - 1:
+                    self.keep_out = keep_last
                 last = self.train_step(batches(i))
                 marks[i + 1].record()
             self.fence()
             secs = time.perf_counter() - t0
         finally:
+            self.keep_out = False
             if gc_was:
                 gc.enable()
         per = [marks[i].elapsed_time(marks[i + 1]) for i in range(n_steps)]
@@ -410,6 +422,44 @@ def cpu_baseline(args, cfg, qb0):
                f"with the {nq}-query figures")
     return vec
 
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT = 64 << 20      # bytes that --dump-outputs may write in all
+
+
+def step_outputs(R, loss):
+    """What the timed path handed its caller in its last step: the scores, the loss, and the model's parameters after that
+    step's optimizer update with the gradients the step computed (rank 0's; after the all-reduce when N > 1)."""
+    arrays = {"scores": R.last_out, "loss": loss}
+    for name, p in R.model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT):
+    """arrays -> out_dir/<name>.npy in float32 (float64 stays float64).  When they would take more than `limit` bytes, an array
+    larger than its equal share keeps a fixed sample of that many elements: flat indices drawn with seed 0, in order.
+    Returns the bytes written."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=v.dtype if v.dtype in (np.float32, np.float64) else np.float32)
+              for k, v in arrays.items()}
+    if sum(a.nbytes + 128 for a in arrays.values()) > limit:
+        share = limit // len(arrays) - 128                # (128: the .npy header)
+        for k, a in arrays.items():
+            n = share // a.itemsize
+            if a.size > n:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))
+                arrays[k] = a.reshape(-1)[idx]
+    written = 0
+    for k, a in arrays.items():
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, a)
+        written += os.path.getsize(path)
+    return written
+
+
 # ------------------------------------------------------------------------------------------------ the one JSON line
 LINE_LIMIT = 6144          # bytes; the driver's capture truncated round 4's 21.5 KB line from the FRONT (metric, value, ... lost)
 ROOF_KEYS = ("kernel", "bound", "achieved", "peak", "unit", "frac", "avg_launch_us", "launches",
@@ -475,7 +525,7 @@ def compact_line(full: dict) -> dict:
 
 def emit(full: dict, write_detail: bool = True) -> str:
     """Write the detail file(s), print the details to stderr and return the compact line as a string <= LINE_LIMIT bytes.
-    write_detail = False (--plan-only: a profiling target with nothing but the timed region) leaves an earlier detail file alone."""
+    write_detail = False (a run without --full, or --plan-only: nothing but the timed region) leaves an earlier detail file alone."""
     paths = [os.path.join(REPO, "bench_detail.json")] if write_detail else []
     if write_detail and os.path.isdir(os.path.join(REPO, "gpurun_out")):
         paths.append(os.path.join(REPO, "gpurun_out", "bench_detail.json"))
@@ -570,8 +620,16 @@ def main():
     ap.add_argument("--aux-backward", action="store_true", help="also run the reactant encoder's backward on the aux stream")
     ap.add_argument("--foreach-adam", action="store_true", help="torch's multi-kernel Adam instead of the library's one-launch Adam")
     ap.add_argument("--torch-fused-adam", action="store_true", help="torch's fused Adam instead of the library's one-launch Adam")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the comparison legs (in-situ and isolated rooflines, forward-only and "
+                         "validation rates, f32-MFMA and other-split paths, streamed epoch, other presets, CPU baseline; the "
+                         "--no-* options still skip single legs) and write bench_detail.json.  Without it: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's scores, loss, updated parameters and gradients as DIR/<name>.npy")
     args = ap.parse_args()
-    if args.plan_only:
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.plan_only or not args.full:
         args.no_profile = args.no_fwd_only = args.no_presets = args.no_epoch = args.no_f32_path = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:   # BEFORE any torch.cuda call: the parent never touches the GPU
@@ -625,7 +683,7 @@ def main():
     Fn.AuxStream.enabled = not args.no_aux_stream
     if args.aux_backward:
         Fn.AuxStream.backward = True
-    traffic, traffic_src = load_traffic()
+    traffic, traffic_src = load_traffic() if not args.no_profile else ({}, None)
 
     log(f"building the step pool of `{args.config}` (synthetic graphs -> native packer -> HBM)")
     R = Runner(args.config, cfg, args, rank, world, local, device, args.pool)
@@ -644,7 +702,12 @@ def main():
     # The timed region issues every step through the step plan (one native call per pass) and records NO kernel events:
     # `value` is the plan path only.  The live roofline timings come from an extra pass right behind it (below).
     log(f"timing {args.steps} steps")
-    elapsed, per_ms, last = R.timed(cyc(args.warmup), args.steps)
+    elapsed, per_ms, last = R.timed(cyc(args.warmup), args.steps, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs:                                 # before any later leg moves the model on
+        if rank == 0:
+            nbytes = write_outputs(args.dump_outputs, step_outputs(R, last))
+            log(f"outputs of the last timed step: {nbytes / 1e6:.2f} MB in {args.dump_outputs}")
+        R.last_out = None
     records = []
     if not args.no_profile:
         # in-situ pass ON THE SAME PATH: the same steps through the same step plans, same three streams overlapping, with
@@ -983,7 +1046,7 @@ def main():
         full.update(extra)
         if cpu:
             full["gpu_over_cpu"] = round(qps / cpu["value"], 1)
-        print(emit(full, write_detail=not args.plan_only), flush=True)
+        print(emit(full, write_detail=args.full and not args.plan_only), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

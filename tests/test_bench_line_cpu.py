@@ -5,6 +5,8 @@ import importlib.util
 import json
 import os
 
+import numpy as np
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -70,3 +72,25 @@ def test_self_launch_is_decided_before_any_gpu_call():
     body = src[src.index("def main():"):]
     assert body.index("self_launch(args.gpus") < body.index("torch.cuda.")
     assert "os.exec" not in src and "execv" not in src
+
+
+def test_write_outputs_keeps_floats_and_a_fixed_sample_above_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 / float64; above the byte limit an array larger than its share
+    keeps the same seeded, ordered sample of its elements on every run."""
+    B = _bench()
+    arrays = {"small": np.arange(10, dtype=np.float32), "big": np.arange(5000, dtype=np.float64).reshape(50, 100),
+              "ints": np.arange(4, dtype=np.int64)}
+    n = B.write_outputs(str(tmp_path / "all"), arrays)
+    assert n == sum(os.path.getsize(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all"))
+    assert sorted(os.listdir(tmp_path / "all")) == ["big.npy", "ints.npy", "small.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "big.npy"), arrays["big"])
+    ints = np.load(tmp_path / "all" / "ints.npy")
+    assert ints.dtype == np.float32 and ints.tolist() == [0, 1, 2, 3]
+    samples = []
+    for d in ("s1", "s2"):
+        assert B.write_outputs(str(tmp_path / d), arrays, limit=3072) <= 3072
+        big = np.load(tmp_path / d / "big.npy")
+        assert big.dtype == np.float64 and 0 < big.size < 5000 and (np.diff(big) > 0).all()
+        np.testing.assert_array_equal(np.load(tmp_path / d / "small.npy"), arrays["small"])
+        samples.append(big)
+    np.testing.assert_array_equal(samples[0], samples[1])

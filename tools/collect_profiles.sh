@@ -4,7 +4,7 @@
 # 1. rocprofv3 --kernel-trace --stats of the bench command   -> gpurun_out/<tag>_bench_kernel_stats.csv
 # 2. two separate --pmc passes (FETCH_SIZE, WRITE_SIZE)      -> gpurun_out/<tag>_traffic.json (+ raw per-kernel tables);
 #    the JSON records the hash of csrc/ it was measured on - bench.py ignores it once a kernel source changes
-# 3. default bench (JSON line incl. cpu_baseline, epoch_stream, presets) -> gpurun_out/<tag>_bench_default.json
+# 3. bench --full (JSON line incl. cpu_baseline, epoch_stream, presets) -> <tag>_bench_default.json beside the files above
 # Copy what should be judged from gpurun_out/ into profiles/.
 set -e
 tag=${1:-r02}
@@ -43,5 +43,5 @@ if json.load(open(newest)).get("csrc_hash") != csrc_hash():
     sys.exit(f"[collect] {newest} does not match the current kernel sources")
 PY
 echo "[collect] default bench"
-python3 bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
+python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err
 echo "[collect] done"
