@@ -83,17 +83,18 @@ def _err(out, ref, den):
     return float(e.max()), float(e.mean())
 
 
-def _compare(o32, osp, ref, den, what, north_star=True):
+def _compare(o32, osp, ref, den, what, north_star=True, bound=2e-6):
     m32, a32 = _err(o32, ref, den)
     msp, asp = _err(osp, ref, den)
-    Hh.record(what + " | split max err / sum|ab|", msp, 2e-6)
+    Hh.record(what + " | split max err / sum|ab|", msp, bound)
     Hh.record(what + " | f32-MFMA max err / sum|ab|", m32)
     assert asp <= 1.25 * a32 + 1e-12, f"{what}: mean error split {asp:.3e} vs f32 {a32:.3e}"
     assert msp <= 2.0 * m32 + 1e-12, f"{what}: max error split {msp:.3e} vs f32 {m32:.3e}"
-    assert msp <= 2e-6, f"{what}: max error {msp:.3e} (relative to sum |a b|)"
+    assert msp <= bound, f"{what}: max error {msp:.3e} (relative to sum |a b|)"
     if north_star:      # (wide-range inputs cancel: there the exact-f32 chain itself is ~1e-4 off by this measure)
         tol = ((osp.double() - ref).abs() / (1 + ref.abs())).max().item()
         assert tol <= 1e-5, f"{what}: north-star tolerance {tol:.3e}"
+    return msp, m32
 
 
 @pytest.mark.parametrize("M", [1, 191, 192, 193, 5000])
