@@ -32,6 +32,25 @@ def make_batches(seed, n_queries, cands, per_batch):
     return out
 
 
+def head_for(task_type):
+    """task_num and head of the model each task type trains: the NIG (normal-inverse-gamma) losses read the four softplus'd
+    columns of 'evidential_with_softplus', the '*dis_*' ones a mean / positive-variance pair, listnet_uq and dirichlet_uq
+    the positive scores of 'listnet_with_uncertainty'."""
+    if task_type in ("evidential", "mle_evidential", "mledis_evidential", "listnet_evidential"):
+        return dict(task_num=4, ffn_last_layer="with_softplus", task_type=None)
+    if task_type == "listnetdis_lognorm":
+        return dict(task_num=2, ffn_last_layer="with_softplus", task_type="listnetdis_lognorm")
+    if task_type in ("mledis_gaussian", "listnetdis_gauss"):
+        return dict(task_num=2, ffn_last_layer="with_softplus", task_type=None)
+    if task_type in ("listnet_uq", "dirichlet_uq"):
+        return dict(task_num=1, ffn_last_layer="with_uncertainty", task_type="listnet")
+    if task_type == "evidential_ranking":
+        return dict(task_num=2, ffn_last_layer="no_softplus", task_type="evidential_ranking")
+    if task_type in ("gauss_regression", "mle_gaussian", "listnet_gauss"):
+        return dict(task_num=2, ffn_last_layer="no_softplus", task_type=None)
+    return dict(task_num=1, ffn_last_layer="with_softplus", task_type=None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task-type", default="mle")
@@ -45,10 +64,8 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     log = logging.getLogger("train_synthetic")
-    task_num = 2 if args.task_type in ("evidential_ranking", "gauss_regression", "mle_gaussian", "listnet_gauss") else 1
     model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
-                        task_num=task_num, ffn_last_layer="with_softplus" if task_num == 1 else "no_softplus",
-                        task_type=args.task_type if args.task_type == "evidential_ranking" else None, add_features_dim=1)
+                        add_features_dim=1, **head_for(args.task_type))
     log.info("parameters: %d", param_count(model))
     train_b = make_batches(0, args.queries, args.cands, args.batch_queries)
     val_b = make_batches(10 ** 6, max(args.batch_queries, args.queries // 8), args.cands, args.batch_queries)

@@ -492,6 +492,85 @@ int rr_gauss_nll_bwd_f32(const float* mean, const float* var, int64_t stride, co
                          int64_t n, const float* gloss, float* dmean, float* dvar, int64_t dstride,
                          rr_stream_t stream);
 
+/* The reference trainer's remaining losses (train/loss.py:102-141, 165-314, 355-474; train/train_listwise.py:274-279).
+ * Same list description as above: seg_off[Q+1], max_len <= 8192 (RR_ERR_UNSUPPORTED above), per-query partials [Q]
+ * finished in a fixed order (no float atomics: run-to-run identical bits).  Every per-candidate input has its own
+ * element stride (a column view of the model output is read in place); gradients are written at d[i * dstride].
+ * `loss` = sum over queries of the query's loss / Q (an empty query adds 0 and still counts).  Backward entries write
+ * *gloss times the gradient of that.  Status: RR_ERR_ARG for a null pointer, a stride < 1 or a negative size.
+ *
+ * MLEDisLoss (:102-141), mean = mu, var = variance; sorted by target (descending, ties by index):
+ *   L_q = mean_j log sum_{i>=j} exp(s_i - s_j + (v_i + v_j) / 2)
+ * Listnet_For_Gauss (:233-272): L_q = mean_i softmax(t)_i log sum_j exp(s_j - s_i + (v_i + v_j) / 2)
+ * Listnetlognorm (:275-314):    L_q = mean_i softmax(t)_i log sum_j (s_j / s_i) exp((v_i + v_j) / 2) */
+int rr_mledis_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,
+                      const int32_t* seg_off, int Q, int max_len, float* loss, float* partial /* [Q] */, rr_stream_t stream);
+int rr_mledis_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,
+                      const int32_t* seg_off, int Q, int max_len, const float* gloss, float* dmean, float* dvar,
+                      int64_t dstride, rr_stream_t stream);
+int rr_listnet_gauss_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride,
+                             const float* targets, const int32_t* seg_off, int Q, int max_len, float* loss,
+                             float* partial /* [Q] */, rr_stream_t stream);
+int rr_listnet_gauss_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride,
+                             const float* targets, const int32_t* seg_off, int Q, int max_len, const float* gloss,
+                             float* dmean, float* dvar, int64_t dstride, rr_stream_t stream);
+int rr_listnet_lognorm_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride,
+                               const float* targets, const int32_t* seg_off, int Q, int max_len, float* loss,
+                               float* partial /* [Q] */, rr_stream_t stream);
+int rr_listnet_lognorm_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride,
+                               const float* targets, const int32_t* seg_off, int Q, int max_len, const float* gloss,
+                               float* dmean, float* dvar, int64_t dstride, rr_stream_t stream);
+/* Listnet_For_evidential (:187-230): L_q = -mean_i softmax(t)_i log_softmax(s)_i (2 v_i + alpha_i) */
+int rr_listnet_evidential_fwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride,
+                                  const float* alpha, int64_t alpha_stride, const float* targets, const int32_t* seg_off,
+                                  int Q, int max_len, float* loss, float* partial /* [Q] */, rr_stream_t stream);
+int rr_listnet_evidential_bwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride,
+                                  const float* alpha, int64_t alpha_stride, const float* targets, const int32_t* seg_off,
+                                  int Q, int max_len, const float* gloss, float* dmean, float* dv, float* dalpha,
+                                  int64_t dstride, rr_stream_t stream);
+/* Listnet_with_uq (:355-399), p = s / sum(s):
+ *   L_q = KLDivLoss_batchmean(log p, softmax(t)) + coef * mean_i |log(softmax(t)_i / p_i) (s_i - 1)|
+ * Dirichlet_uq (:440-474), S = sum(a), p = a / S:
+ *   L_q = mean_i (p_i - softmax(t)_i)^2 + p_i (1 - p_i) / (S + 1) + coef * |log(softmax(t)_i / p_i) (a_i - 1)|
+ * `coef` is the annealing coefficient max_coeff * (epoch / (epochs - 1))^3, computed by the caller. */
+int rr_listnet_uq_fwd_f32(const float* score, int64_t stride, const float* targets, const int32_t* seg_off, int Q,
+                          int max_len, float coef, float* loss, float* partial /* [Q] */, rr_stream_t stream);
+int rr_listnet_uq_bwd_f32(const float* score, int64_t stride, const float* targets, const int32_t* seg_off, int Q,
+                          int max_len, float coef, const float* gloss, float* dscore, int64_t dstride, rr_stream_t stream);
+int rr_dirichlet_uq_fwd_f32(const float* alpha, int64_t stride, const float* targets, const int32_t* seg_off, int Q,
+                            int max_len, float coef, float* loss, float* partial /* [Q] */, rr_stream_t stream);
+int rr_dirichlet_uq_bwd_f32(const float* alpha, int64_t stride, const float* targets, const int32_t* seg_off, int Q,
+                            int max_len, float coef, const float* gloss, float* dalpha, int64_t dstride, rr_stream_t stream);
+
+/* evidential_loss_new (:402-437), the normal-inverse-gamma NLL plus its regulariser, Omega = 2 beta (1 + v), d = t - mu:
+ *   l = log(pi / v) / 2 - alpha log Omega + (alpha + 1/2) log(v d^2 + Omega) + lgamma(alpha) - lgamma(alpha + 1/2)
+ *       + lam (|d| (2 v + alpha) - epsilon)
+ * cross == 0: the four parameters and targets are n-vectors, l is taken elementwise, loss = mean over n.
+ * cross == 1: the parameters are n x 1 columns against n targets (torch broadcasting): l of parameter row i against
+ *   target j for all n x n pairs, loss = mean over n^2; any n (the targets stream through LDS in tiles).
+ * partial: max(n, 1) floats.  n == 0 gives NaN (torch.mean of nothing).  d/dalpha uses a device digamma. */
+int rr_nig_fwd_f32(const float* mu, int64_t mu_stride, const float* v, int64_t v_stride, const float* alpha,
+                   int64_t alpha_stride, const float* beta, int64_t beta_stride, const float* targets, int64_t n, int cross,
+                   float lam, float epsilon, float* loss, float* partial, rr_stream_t stream);
+int rr_nig_bwd_f32(const float* mu, int64_t mu_stride, const float* v, int64_t v_stride, const float* alpha,
+                   int64_t alpha_stride, const float* beta, int64_t beta_stride, const float* targets, int64_t n, int cross,
+                   float lam, const float* gloss, float* dmu, float* dv, float* dalpha, float* dbeta, int64_t dstride,
+                   rr_stream_t stream);
+/* The device digamma of the NIG backward, elementwise (x > 0; NaN for x < 0, -inf at 0). */
+int rr_digamma_f32(const float* x, int64_t n, float* y, rr_stream_t stream);
+
+/* Lognorm (:165-184): mean of log(2 pi) / 2 + log(var s^2) / 2 + (log s - t)^2 / (2 var), pi as float32; the
+ * reference's print of the value is not reproduced.  Exp-MSE: mean((exp(t) - exp(pred))^2), the regression_exploss
+ * branch (train/train_listwise.py:274-279).  partial: rr_pointwise_partial_count(n) floats. */
+int rr_lognorm_fwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n,
+                       float* loss, float* partial, rr_stream_t stream);
+int rr_lognorm_bwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n,
+                       const float* gloss, float* dscore, float* dvar, int64_t dstride, rr_stream_t stream);
+int rr_exp_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
+                       rr_stream_t stream);
+int rr_exp_mse_bwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, const float* gloss,
+                       float* dpred, int64_t dstride, rr_stream_t stream);
+
 /* Per-query ranking evaluation on the device - the metric halves of `ranking_metrics` (train/eval.py:475-555),
  * `evaluate_top_scores` (:76-177) and `calculate_ndcg` (:329-457) without the one-forward-per-query loops and the
  * Python lists; same list description as the losses.  ABI revision 6: `ratio`, `ndcg_cut`, 12 statistics per query.

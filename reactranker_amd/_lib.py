@@ -211,6 +211,31 @@ _SIGS = {
     "rr_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, i64, c_stream]),
     "rr_gauss_nll_fwd_f32": (i32, [c_f32p, c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_stream]),
     "rr_gauss_nll_bwd_f32": (i32, [c_f32p, c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_f32p, i64, c_stream]),
+    "rr_mledis_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_stream]),
+    "rr_mledis_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, i64, c_stream]),
+    "rr_listnet_gauss_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_stream]),
+    "rr_listnet_gauss_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, i64,
+                                       c_stream]),
+    "rr_listnet_lognorm_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_stream]),
+    "rr_listnet_lognorm_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, i64,
+                                         c_stream]),
+    "rr_listnet_evidential_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p,
+                                            c_stream]),
+    "rr_listnet_evidential_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p,
+                                            c_f32p, c_f32p, i64, c_stream]),
+    "rr_listnet_uq_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, c_stream]),
+    "rr_listnet_uq_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_dirichlet_uq_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, c_stream]),
+    "rr_dirichlet_uq_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_nig_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, i64, i32, f32, f32, c_f32p, c_f32p,
+                             c_stream]),
+    "rr_nig_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, i64, i32, f32, c_f32p, c_f32p,
+                             c_f32p, c_f32p, c_f32p, i64, c_stream]),
+    "rr_digamma_f32": (i32, [c_f32p, i64, c_f32p, c_stream]),
+    "rr_lognorm_fwd_f32": (i32, [c_f32p, c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_stream]),
+    "rr_lognorm_bwd_f32": (i32, [c_f32p, c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_f32p, i64, c_stream]),
+    "rr_exp_mse_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_stream]),
+    "rr_exp_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, i64, c_stream]),
     "rr_ranking_metrics_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, C.c_double, C.c_double, c_i32p, C.c_void_p,
                                c_stream]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),

@@ -673,6 +673,430 @@ __global__ void __launch_bounds__(RR_WAVE) lce_bwd_kernel(const float* __restric
   for (int i = lane; i < n; i += RR_WAVE) gx[i] = gy[i] * (expf(x[i]) * cs[i]);      // loss.py:59
 }
 
+// ---------------------------------------------------------------- listwise variants (train/loss.py:102-141, 187-314,
+// 355-399, 440-474): MLEDisLoss, Listnet_For_Gauss, Listnetlognorm, Listnet_For_evidential, Listnet_with_uq, Dirichlet_uq.
+// One wavefront per query like the kernels above; the C x C pair sums of the first three are factorised into per-element
+// terms, so a query costs O(C) - except MLEDisLoss's backward and the target ranking, O(C^2 / 64).
+enum LossVariant : int { kMleDis = 0, kListnetGauss = 1, kListnetLognorm = 2, kListnetEvid = 3, kListnetUq = 4, kDirichletUq = 5 };
+
+struct VarIn {            // up to three per-candidate inputs, each read at x[k][row * st[k]]
+  const float* x[3];
+  int64_t st[3];
+};
+
+struct VarOut {           // their gradients, written at d[k][row * st]
+  float* d[3];
+  int64_t st;
+};
+
+constexpr int variant_inputs(int V) { return V == kListnetEvid ? 3 : (V == kListnetUq || V == kDirichletUq) ? 1 : 2; }
+// staged floats per candidate: x0, t, x1, x2 (ListNet-evidential), perm + scan (MLEDis)
+constexpr int variant_lds(int V) { return V == kMleDis ? 5 : V == kListnetEvid ? 4 : (V == kListnetUq || V == kDirichletUq) ? 2 : 3; }
+
+__device__ inline float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }   // torch.abs' gradient
+
+template <int V>
+__global__ void __launch_bounds__(RR_WAVE) listwise_variant_kernel(VarIn in, const float* __restrict__ targets,
+                                                                   const int32_t* __restrict__ seg_off, int L, int Q, float coef,
+                                                                   int bwd, float* __restrict__ partial,
+                                                                   const float* __restrict__ gloss, VarOut out) {
+  // bwd: 0 = forward (partial[q] = the query's loss), 1 = backward (gradients of sum_q partial[q] / Q, times *gloss)
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  constexpr int NIN = variant_inputs(V);
+  const int q = blockIdx.x, lane = threadIdx.x;
+  const int off = seg_off[q], C = seg_off[q + 1] - off;
+  if (C <= 0) {                                                     // an empty query adds nothing (still counted in Q)
+    if (!bwd && lane == 0) partial[q] = 0.f;
+    return;
+  }
+  float* x0 = sm;
+  float* t = sm + L;
+  float* x1 = sm + 2 * L;
+  float* x2 = sm + 3 * L;
+  for (int i = lane; i < C; i += RR_WAVE) {
+    const int64_t r = off + i;
+    x0[i] = in.x[0][r * in.st[0]];
+    if (NIN > 1) x1[i] = in.x[1][r * in.st[1]];
+    if (NIN > 2) x2[i] = in.x[2][r * in.st[2]];
+    t[i] = targets[r];
+  }
+  wave_sync();
+  const float invC = 1.0f / static_cast<float>(C);
+  const float g = bwd ? gloss[0] / (static_cast<float>(C) * static_cast<float>(Q)) : 0.f;
+  auto put = [&](int k, int i, float val) { out.d[k][static_cast<int64_t>(off + i) * out.st] = val; };
+
+  if constexpr (V == kMleDis) {
+    // sorted by target (descending, stable); a_j = s_j + v_j / 2, F_j = log sum_{i>=j} exp(a_i);
+    // L_q = mean_j log sum_{i>=j} exp(s_i - s_j + (v_i + v_j) / 2) = mean_j (F_j - s_j + v_j / 2)
+    ListView lv;
+    lv.s = x0;
+    lv.t = t;
+    lv.perm = reinterpret_cast<int32_t*>(x2);
+    lv.ss = sm + 4 * L;                                             // sorted scores: scratch, overwritten by F below
+    lv.aux = nullptr;
+    rank_sort(lv, C, lane);
+    float* sa = t;                                                  // targets are not read again: sorted a in their place
+    float* F = sm + 4 * L;
+    for (int r = lane; r < C; r += RR_WAVE) {
+      const int p = lv.perm[r];
+      sa[r] = x0[p] + 0.5f * x1[p];
+    }
+    wave_sync();
+    const float m = list_max(sa, C, lane);
+    logcumsumexp_rev(sa, F, C, lane, m);
+    if (!bwd) {
+      float acc = 0.f;
+      for (int r = lane; r < C; r += RR_WAVE) {
+        const int p = lv.perm[r];
+        acc += F[r] + (0.5f * x1[p] - x0[p]);
+      }
+      acc = rr_wave_sum(acc);
+      if (lane == 0) partial[q] = acc * invC;
+    } else {
+      // d L_q / d a_k = (1/C) sum_{j<=k} exp(a_k - F_j): every term is <= 1, so the pair form cannot overflow
+      for (int k = lane; k < C; k += RR_WAVE) {
+        const float ak = sa[k];
+        float G = 0.f;
+        for (int j = 0; j <= k; ++j) G += expf(ak - F[j]);
+        const int p = lv.perm[k];
+        put(0, p, g * (G - 1.0f));
+        put(1, p, g * 0.5f * (G + 1.0f));
+      }
+    }
+  } else {
+    float mt, zt;                                                   // softmax of the query's targets
+    softmax_stats(t, C, lane, &mt, &zt);
+    auto smt = [&](int i) { return expf(t[i] - mt) / zt; };
+    float tsum = 0.f;
+    if (bwd) {
+      for (int i = lane; i < C; i += RR_WAVE) tsum += smt(i);
+      tsum = rr_wave_sum(tsum);
+    }
+    if constexpr (V == kListnetGauss) {
+      // log sum_j exp(s_j - s_i + (v_i + v_j) / 2) = LSE_j(s_j + v_j / 2) - s_i + v_i / 2
+      float ma = -INFINITY;
+      for (int i = lane; i < C; i += RR_WAVE) ma = fmaxf(ma, x0[i] + 0.5f * x1[i]);
+      ma = rr_wave_max(ma);
+      float za = 0.f;
+      for (int i = lane; i < C; i += RR_WAVE) za += expf(x0[i] + 0.5f * x1[i] - ma);
+      za = rr_wave_sum(za);
+      const float lse = ma + logf(za);
+      if (!bwd) {
+        float acc = 0.f;
+        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * (lse + (0.5f * x1[i] - x0[i]));
+        acc = rr_wave_sum(acc);
+        if (lane == 0) partial[q] = acc * invC;
+      } else {
+        for (int k = lane; k < C; k += RR_WAVE) {
+          const float pk = expf(x0[k] + 0.5f * x1[k] - lse), tk = smt(k);
+          put(0, k, g * (tsum * pk - tk));
+          put(1, k, g * 0.5f * (tsum * pk + tk));
+        }
+      }
+    } else if constexpr (V == kListnetLognorm) {
+      // log sum_j (s_j / s_i) exp((v_i + v_j) / 2) = log(W / s_i) + (v_i + mv) / 2, W = sum_j s_j exp((v_j - mv) / 2):
+      // the sign of W / s_i is the sign of the reference's sum, so log() of a negative one is NaN here as there
+      const float mv = list_max(x1, C, lane);
+      float W = 0.f;
+      for (int i = lane; i < C; i += RR_WAVE) W += x0[i] * expf(0.5f * (x1[i] - mv));
+      W = rr_wave_sum(W);
+      if (!bwd) {
+        float acc = 0.f;
+        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * (logf(W / x0[i]) + 0.5f * (x1[i] + mv));
+        acc = rr_wave_sum(acc);
+        if (lane == 0) partial[q] = acc * invC;
+      } else {
+        for (int k = lane; k < C; k += RR_WAVE) {
+          const float ek = expf(0.5f * (x1[k] - mv)), tk = smt(k);
+          put(0, k, g * (tsum * ek / W - tk / x0[k]));
+          put(1, k, g * 0.5f * (tsum * x0[k] * ek / W + tk));
+        }
+      }
+    } else if constexpr (V == kListnetEvid) {
+      // L_q = -mean_i softmax(t)_i * log_softmax(s)_i * (2 v_i + alpha_i)
+      float ms, zs;
+      softmax_stats(x0, C, lane, &ms, &zs);
+      const float lz = logf(zs);
+      if (!bwd) {
+        float acc = 0.f;
+        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * ((x0[i] - ms) - lz) * (2.0f * x1[i] + x2[i]);
+        acc = rr_wave_sum(acc);
+        if (lane == 0) partial[q] = -(acc * invC);
+      } else {
+        float wsum = 0.f;
+        for (int i = lane; i < C; i += RR_WAVE) wsum += smt(i) * (2.0f * x1[i] + x2[i]);
+        wsum = rr_wave_sum(wsum);
+        for (int k = lane; k < C; k += RR_WAVE) {
+          const float tk = smt(k), lsk = (x0[k] - ms) - lz, pk = expf(x0[k] - ms) / zs;
+          put(0, k, -g * (tk * (2.0f * x1[k] + x2[k]) - pk * wsum));
+          put(1, k, -g * 2.0f * tk * lsk);
+          put(2, k, -g * tk * lsk);
+        }
+      }
+    } else {
+      // kListnetUq: p = s / sum(s); L_q = KL(softmax(t) || p) / C + coef * mean_i |log(softmax(t)_i / p_i) (s_i - 1)|
+      // kDirichletUq: p = a / S, S = sum(a); L_q = mean_i (p_i - sm_i)^2 + p_i (1 - p_i) / (S + 1) + coef * |log(sm_i / p_i) (a_i - 1)|
+      float S = 0.f;
+      for (int i = lane; i < C; i += RR_WAVE) S += x0[i];
+      S = rr_wave_sum(S);
+      if (!bwd) {
+        float acc = 0.f, pen = 0.f;
+        for (int i = lane; i < C; i += RR_WAVE) {
+          const float p = x0[i] / S, tk = smt(i);
+          pen += fabsf(logf(tk / p) * (x0[i] - 1.0f));
+          if constexpr (V == kListnetUq) {
+            acc += (tk > 0.f ? tk * logf(tk) : 0.f) - tk * logf(p);        // KLDivLoss: xlogy(t, t) - t * input
+          } else {
+            const float e = p - tk;
+            acc += e * e + p * (1.0f - p) / (S + 1.0f);
+          }
+        }
+        acc = rr_wave_sum(acc);
+        pen = rr_wave_sum(pen);
+        if (lane == 0) partial[q] = acc * invC + coef * (pen * invC);
+      } else if constexpr (V == kListnetUq) {
+        float U = 0.f;                                              // sum_i sgn(r_i) (s_i - 1)
+        for (int i = lane; i < C; i += RR_WAVE) {
+          const float p = x0[i] / S;
+          U += sgnf(logf(smt(i) / p) * (x0[i] - 1.0f)) * (x0[i] - 1.0f);
+        }
+        U = rr_wave_sum(U);
+        for (int k = lane; k < C; k += RR_WAVE) {
+          const float sk = x0[k], p = sk / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (sk - 1.0f));
+          put(0, k, g * ((tsum / S - tk / sk) + coef * (sg * c - sg * (sk - 1.0f) / sk + U / S)));
+        }
+      } else {
+        float up = 0.f, w = 0.f;                                    // sum_i u_i p_i and d L / d S at fixed p
+        const float S1 = S + 1.0f;
+        for (int i = lane; i < C; i += RR_WAVE) {
+          const float ai = x0[i], p = ai / S, tk = smt(i), sg = sgnf(logf(tk / p) * (ai - 1.0f));
+          const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ai - 1.0f) / p;
+          up += u * p;
+          w -= p * (1.0f - p) / (S1 * S1);
+        }
+        up = rr_wave_sum(up);
+        w = rr_wave_sum(w);
+        for (int k = lane; k < C; k += RR_WAVE) {
+          const float ak = x0[k], p = ak / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (ak - 1.0f));
+          const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ak - 1.0f) / p;
+          put(0, k, g * ((u - up) / S + w + coef * sg * c));
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- evidential_loss_new (train/loss.py:402-437)
+// NIG negative log-likelihood + lam * (|t - mu| (2 v + alpha) - eps) of parameter row i against target j.  Elementwise form:
+// j = i.  Cross form (parameters [M, 1] against targets [M], what torch broadcasting makes of the trainer's call): all M x M
+// pairs.  The device has lgammaf but no digamma: digamma_f below.
+__device__ inline float digamma_f(float xf) {
+  // recurrence psi(x) = psi(x + 1) - 1 / x up to x >= 6, then the asymptotic series; NaN for x <= 0 (alpha > 1 here)
+  double x = xf, r = 0.0;
+  if (!(x > 0.0)) return x == 0.0 ? -INFINITY : NAN;
+  while (x < 6.0) {
+    r -= 1.0 / x;
+    x += 1.0;
+  }
+  const double f = 1.0 / (x * x);
+  const double tail = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
+  return static_cast<float>(r + log(x) - 0.5 / x - tail);
+}
+
+struct NigRow {
+  float mu, v, a, b, omega, ap, lw, k;   // omega = 2 b (1 + v), ap = a + 1/2, lw = lam (2 v + a), k = target-free terms
+  float cv, ca, cb;                      // target-free parts of d/dv, d/dalpha, d/dbeta
+};
+
+__device__ inline NigRow nig_row(float mu, float v, float a, float b, float lam, float eps, bool grads) {
+  NigRow r;
+  r.mu = mu; r.v = v; r.a = a; r.b = b;
+  r.omega = 2.0f * b * (1.0f + v);
+  r.ap = a + 0.5f;
+  r.lw = lam * (2.0f * v + a);
+  const float lo = logf(r.omega);
+  r.k = 0.5f * logf(3.14159274101257324f / v) - a * lo + lgammaf(a) - lgammaf(r.ap) - lam * eps;   // float32(np.pi)
+  r.cv = r.ca = r.cb = 0.f;
+  if (grads) {
+    r.cv = -0.5f / v - a / (1.0f + v);
+    r.ca = -lo + (digamma_f(a) - digamma_f(r.ap));
+    r.cb = -a / b;
+  }
+  return r;
+}
+
+__device__ inline float nig_loss(const NigRow& r, float t) {
+  const float d = t - r.mu;
+  return r.k + (r.ap * logf(r.v * d * d + r.omega) + r.lw * fabsf(d));
+}
+
+struct NigGrad {
+  float mu, v, a, b;
+};
+
+__device__ inline void nig_grad_add(const NigRow& r, float t, float lam, NigGrad& g) {
+  const float d = t - r.mu, ad = fabsf(d);
+  const float qv = r.v * d * d + r.omega;
+  g.mu += -2.0f * r.ap * r.v * d / qv - r.lw * sgnf(d);
+  g.v += r.cv + (r.ap * (d * d + 2.0f * r.b) / qv + 2.0f * lam * ad);
+  g.a += r.ca + (logf(qv) + lam * ad);
+  g.b += r.cb + 2.0f * r.ap * (1.0f + r.v) / qv;
+}
+
+struct NigIn {
+  const float* x[4];   // mu, v, alpha, beta
+  int64_t st[4];
+};
+
+struct NigOut {
+  float* d[4];
+  int64_t st;
+};
+
+__device__ inline NigRow nig_load(const NigIn& in, int64_t i, float lam, float eps, bool grads) {
+  return nig_row(in.x[0][i * in.st[0]], in.x[1][i * in.st[1]], in.x[2][i * in.st[2]], in.x[3][i * in.st[3]], lam, eps, grads);
+}
+
+// elementwise form: grid-stride, one partial per workgroup (pointwise_fwd_kernel's layout)
+__global__ void __launch_bounds__(256) nig_elem_kernel(NigIn in, const float* __restrict__ targets, int64_t n, float lam,
+                                                       float eps, int bwd, float* __restrict__ partial,
+                                                       const float* __restrict__ gloss, NigOut out) {
+  __shared__ float red[256];
+  float acc = 0.f;
+  const float g = bwd ? gloss[0] / static_cast<float>(n) : 0.f;
+  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
+    const NigRow r = nig_load(in, i, lam, eps, bwd != 0);
+    if (!bwd) {
+      acc += nig_loss(r, targets[i]);
+    } else {
+      NigGrad d{0.f, 0.f, 0.f, 0.f};
+      nig_grad_add(r, targets[i], lam, d);
+      out.d[0][i * out.st] = g * d.mu;
+      out.d[1][i * out.st] = g * d.v;
+      out.d[2][i * out.st] = g * d.a;
+      out.d[3][i * out.st] = g * d.b;
+    }
+  }
+  if (bwd) return;
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// cross form: a workgroup owns kNigRows parameter rows (lane = row) and its four waves split the targets, which stream
+// through LDS in tiles of kNigTile; each wave takes a fixed quarter of every tile and the four per-row sums are added in
+// wave order, so partial[i] (the row's sum over all M targets) has the same bits on every run
+constexpr int kNigRows = RR_WAVE;
+constexpr int kNigTile = 1024;
+
+__global__ void __launch_bounds__(256) nig_cross_kernel(NigIn in, const float* __restrict__ targets, int64_t M, float lam,
+                                                        float eps, int bwd, float* __restrict__ partial,
+                                                        const float* __restrict__ gloss, NigOut out) {
+  __shared__ float tile[kNigTile];
+  __shared__ float red[4][4][kNigRows];
+  const int lane = threadIdx.x % RR_WAVE, wave = threadIdx.x / RR_WAVE;
+  const int64_t row = static_cast<int64_t>(blockIdx.x) * kNigRows + lane;
+  const bool live = row < M;
+  NigRow r{};
+  if (live) r = nig_load(in, row, lam, eps, bwd != 0);
+  float acc = 0.f;
+  NigGrad d{0.f, 0.f, 0.f, 0.f};
+  constexpr int part = kNigTile / 4;
+  for (int64_t t0 = 0; t0 < M; t0 += kNigTile) {
+    const int n = static_cast<int>(M - t0 < kNigTile ? M - t0 : kNigTile);
+    __syncthreads();                                                // the previous tile is consumed
+    for (int j = threadIdx.x; j < n; j += 256) tile[j] = targets[t0 + j];
+    __syncthreads();
+    if (live) {
+      const int lo = wave * part, hi = min(lo + part, n);
+      if (!bwd) {
+        for (int j = lo; j < hi; ++j) acc += nig_loss(r, tile[j]);
+      } else {
+        for (int j = lo; j < hi; ++j) nig_grad_add(r, tile[j], lam, d);
+      }
+    }
+  }
+  red[0][wave][lane] = bwd ? d.mu : acc;
+  red[1][wave][lane] = d.v;
+  red[2][wave][lane] = d.a;
+  red[3][wave][lane] = d.b;
+  __syncthreads();
+  if (wave != 0 || !live) return;
+  float s[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = (red[k][0][lane] + red[k][1][lane]) + (red[k][2][lane] + red[k][3][lane]);
+  if (!bwd) {
+    partial[row] = s[0];
+    return;
+  }
+  const float g = gloss[0] / (static_cast<float>(M) * static_cast<float>(M));
+#pragma unroll
+  for (int k = 0; k < 4; ++k) out.d[k][row * out.st] = g * s[k];
+}
+
+__global__ void __launch_bounds__(256) digamma_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ y) {
+  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) y[i] = digamma_f(x[i]);
+}
+
+// ---------------------------------------------------------------- pointwise: Lognorm (train/loss.py:165-184) and the
+// regression_exploss expression mean((exp(t) - exp(o))^2) (train/train_listwise.py:274-279)
+enum PointwiseExt : int { kLognorm = 0, kExpMse = 1 };
+
+template <int MODE>
+__global__ void __launch_bounds__(256) pointwise_ext_fwd_kernel(const float* __restrict__ x, const float* __restrict__ var,
+                                                                int64_t stride, const float* __restrict__ targets, int64_t n,
+                                                                float* __restrict__ partial) {
+  __shared__ float red[256];
+  const float half_log_2pi = 0.5f * logf(2.0f * 3.14159274101257324f);   // float32(np.pi), loss.py:176,180
+  float acc = 0.f;
+  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
+    const float s = x[i * stride];
+    if constexpr (MODE == kLognorm) {
+      const float v = var[i * stride];
+      const float e = logf(s) - targets[i];
+      acc += half_log_2pi + 0.5f * logf(v * (s * s)) + (e * e) / (2.0f * v);
+    } else {
+      const float e = expf(targets[i]) - expf(s);
+      acc += e * e;
+    }
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256) pointwise_ext_bwd_kernel(const float* __restrict__ x, const float* __restrict__ var,
+                                                                int64_t stride, const float* __restrict__ targets, int64_t n,
+                                                                const float* __restrict__ gloss, float* __restrict__ dx,
+                                                                float* __restrict__ dvar, int64_t dstride) {
+  const float g = gloss[0] / static_cast<float>(n);
+  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
+    const float s = x[i * stride];
+    if constexpr (MODE == kLognorm) {
+      const float v = var[i * stride];
+      const float e = logf(s) - targets[i];
+      dx[i * dstride] = g * (1.0f / s + e / (v * s));
+      dvar[i * dstride] = g * (0.5f / v - (e * e) / (2.0f * v * v));
+    } else {
+      const float es = expf(s);
+      dx[i * dstride] = g * (-2.0f * es * (expf(targets[i]) - es));
+    }
+  }
+}
+
 template <typename Kern>
 int set_lds(Kern k, size_t bytes) {
   if (bytes > 65536) {
@@ -685,6 +1109,74 @@ int set_lds(Kern k, size_t bytes) {
 
 inline bool list_args_ok(const void* a, const void* t, const int32_t* seg, int Q, int max_len) {
   return a && t && seg && Q >= 0 && max_len >= 0;
+}
+
+int pointwise_blocks(int64_t n) {
+  int64_t b = (n + 255) / 256;
+  if (b < 1) b = 1;
+  if (b > 1024) b = 1024;
+  return static_cast<int>(b);
+}
+
+// forward (gloss == nullptr: partials + the mean over queries into `loss`) or backward of one listwise variant
+template <int V>
+int variant_launch(const VarIn& in, const float* targets, const int32_t* seg_off, int Q, int max_len, float coef, float* loss,
+                   float* partial, const float* gloss, const VarOut& out, rr_stream_t stream) {
+  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
+  const int bwd = gloss != nullptr;
+  if (bwd && Q == 0) return RR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int L = max_len > 0 ? max_len : 1;
+  const size_t lds = static_cast<size_t>(variant_lds(V)) * L * sizeof(float);
+  if (Q > 0) {
+    if (set_lds(listwise_variant_kernel<V>, lds) != RR_OK) return RR_ERR_LAUNCH;
+    listwise_variant_kernel<V><<<Q, RR_WAVE, lds, s>>>(in, targets, seg_off, L, Q, coef, bwd, partial, gloss, out);
+  }
+  if (!bwd) reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, Q > 0 ? 1.0f / static_cast<float>(Q) : 0.f, loss);
+  return rr_launch_status();
+}
+
+inline bool strides_ok(const VarIn& in, int nin) {
+  for (int k = 0; k < nin; ++k)
+    if (!in.x[k] || in.st[k] < 1) return false;
+  return true;
+}
+
+inline bool outs_ok(const VarOut& o, int nout) {
+  for (int k = 0; k < nout; ++k)
+    if (!o.d[k]) return false;
+  return o.st >= 1;
+}
+
+int nig_launch(const NigIn& in, const float* targets, int64_t n, int cross, float lam, float eps, float* loss, float* partial,
+               const float* gloss, const NigOut& out, rr_stream_t stream) {
+  for (int k = 0; k < 4; ++k)
+    if (!in.x[k] || in.st[k] < 1) return RR_ERR_ARG;
+  if (!targets || n < 0 || (cross != 0 && cross != 1)) return RR_ERR_ARG;
+  const int bwd = gloss != nullptr;
+  if (bwd) {
+    for (int k = 0; k < 4; ++k)
+      if (!out.d[k]) return RR_ERR_ARG;
+    if (out.st < 1) return RR_ERR_ARG;
+    if (n == 0) return RR_OK;
+  } else if (!loss || !partial) {
+    return RR_ERR_ARG;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int nb = 0;
+  float scale = NAN;                                                 // torch.mean of nothing
+  if (cross) {
+    nb = static_cast<int>((n + kNigRows - 1) / kNigRows);
+    if (n > 0) scale = 1.0f / (static_cast<float>(n) * static_cast<float>(n));
+    if (nb > 0) nig_cross_kernel<<<nb, 256, 0, s>>>(in, targets, n, lam, eps, bwd, partial, gloss, out);
+    if (!bwd) reduce_scale_kernel<<<1, 256, 0, s>>>(partial, n, 1, scale, loss);
+  } else {
+    nb = pointwise_blocks(n);
+    if (n > 0) scale = 1.0f / static_cast<float>(n);
+    nig_elem_kernel<<<nb, 256, 0, s>>>(in, targets, n, lam, eps, bwd, partial, gloss, out);
+    if (!bwd) reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, scale, loss);
+  }
+  return rr_launch_status();
 }
 
 }  // namespace
@@ -877,13 +1369,6 @@ int rr_ranknet_bwd_f32(const float* score, int64_t score_stride, const float* ta
   return rr_launch_status();
 }
 
-static int pointwise_blocks(int64_t n) {
-  int64_t b = (n + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > 1024) b = 1024;
-  return static_cast<int>(b);
-}
-
 int64_t rr_pointwise_partial_count(int64_t n) { return pointwise_blocks(n); }
 
 int rr_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
@@ -956,6 +1441,128 @@ int rr_logcumsumexp_bwd_f32(const float* x, const float* y, const float* gy, int
   const size_t lds = 2u * n * sizeof(float);
   if (set_lds(lce_bwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
   lce_bwd_kernel<<<1, RR_WAVE, lds, static_cast<hipStream_t>(stream)>>>(x, y, gy, n, gx);
+  return rr_launch_status();
+}
+
+
+// ---------------------------------------------------------------- listwise variants
+#define RR_VAR2(NAME, V)                                                                                                        \
+  int rr_##NAME##_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
+                          const int32_t* seg_off, int Q, int max_len, float* loss, float* partial, rr_stream_t stream) {      \
+    const VarIn in{{mean, var, nullptr}, {mean_stride, var_stride, 1}};                                                          \
+    RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 2) && loss && partial);                      \
+    return variant_launch<V>(in, targets, seg_off, Q, max_len, 0.f, loss, partial, nullptr, VarOut{}, stream);                  \
+  }                                                                                                                              \
+  int rr_##NAME##_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
+                          const int32_t* seg_off, int Q, int max_len, const float* gloss, float* dmean, float* dvar,           \
+                          int64_t dstride, rr_stream_t stream) {                                                               \
+    const VarIn in{{mean, var, nullptr}, {mean_stride, var_stride, 1}};                                                          \
+    const VarOut out{{dmean, dvar, nullptr}, dstride};                                                                           \
+    RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 2) && gloss && outs_ok(out, 2));             \
+    return variant_launch<V>(in, targets, seg_off, Q, max_len, 0.f, nullptr, nullptr, gloss, out, stream);                      \
+  }
+
+RR_VAR2(mledis, kMleDis)
+RR_VAR2(listnet_gauss, kListnetGauss)
+RR_VAR2(listnet_lognorm, kListnetLognorm)
+#undef RR_VAR2
+
+int rr_listnet_evidential_fwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
+                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
+                                  float* loss, float* partial, rr_stream_t stream) {
+  const VarIn in{{mean, v, alpha}, {mean_stride, v_stride, alpha_stride}};
+  RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 3) && loss && partial);
+  return variant_launch<kListnetEvid>(in, targets, seg_off, Q, max_len, 0.f, loss, partial, nullptr, VarOut{}, stream);
+}
+
+int rr_listnet_evidential_bwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
+                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
+                                  const float* gloss, float* dmean, float* dv, float* dalpha, int64_t dstride,
+                                  rr_stream_t stream) {
+  const VarIn in{{mean, v, alpha}, {mean_stride, v_stride, alpha_stride}};
+  const VarOut out{{dmean, dv, dalpha}, dstride};
+  RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 3) && gloss && outs_ok(out, 3));
+  return variant_launch<kListnetEvid>(in, targets, seg_off, Q, max_len, 0.f, nullptr, nullptr, gloss, out, stream);
+}
+
+#define RR_VAR1(NAME, V)                                                                                                        \
+  int rr_##NAME##_fwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
+                          float coef, float* loss, float* partial, rr_stream_t stream) {                                       \
+    const VarIn in{{x, nullptr, nullptr}, {stride, 1, 1}};                                                                       \
+    RR_CHECK_ARG(list_args_ok(x, targets, seg_off, Q, max_len) && strides_ok(in, 1) && loss && partial);                         \
+    return variant_launch<V>(in, targets, seg_off, Q, max_len, coef, loss, partial, nullptr, VarOut{}, stream);                 \
+  }                                                                                                                              \
+  int rr_##NAME##_bwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
+                          float coef, const float* gloss, float* dx, int64_t dstride, rr_stream_t stream) {                    \
+    const VarIn in{{x, nullptr, nullptr}, {stride, 1, 1}};                                                                       \
+    const VarOut out{{dx, nullptr, nullptr}, dstride};                                                                           \
+    RR_CHECK_ARG(list_args_ok(x, targets, seg_off, Q, max_len) && strides_ok(in, 1) && gloss && outs_ok(out, 1));                \
+    return variant_launch<V>(in, targets, seg_off, Q, max_len, coef, nullptr, nullptr, gloss, out, stream);                     \
+  }
+
+RR_VAR1(listnet_uq, kListnetUq)
+RR_VAR1(dirichlet_uq, kDirichletUq)
+#undef RR_VAR1
+
+// ---------------------------------------------------------------- evidential_loss_new
+int rr_nig_fwd_f32(const float* mu, int64_t mu_stride, const float* v, int64_t v_stride, const float* alpha, int64_t alpha_stride,
+                   const float* beta, int64_t beta_stride, const float* targets, int64_t n, int cross, float lam, float epsilon,
+                   float* loss, float* partial, rr_stream_t stream) {
+  const NigIn in{{mu, v, alpha, beta}, {mu_stride, v_stride, alpha_stride, beta_stride}};
+  return nig_launch(in, targets, n, cross, lam, epsilon, loss, partial, nullptr, NigOut{}, stream);
+}
+
+int rr_nig_bwd_f32(const float* mu, int64_t mu_stride, const float* v, int64_t v_stride, const float* alpha, int64_t alpha_stride,
+                   const float* beta, int64_t beta_stride, const float* targets, int64_t n, int cross, float lam,
+                   const float* gloss, float* dmu, float* dv, float* dalpha, float* dbeta, int64_t dstride, rr_stream_t stream) {
+  if (!gloss) return RR_ERR_ARG;
+  const NigIn in{{mu, v, alpha, beta}, {mu_stride, v_stride, alpha_stride, beta_stride}};
+  return nig_launch(in, targets, n, cross, lam, 0.f, nullptr, nullptr, gloss, NigOut{{dmu, dv, dalpha, dbeta}, dstride}, stream);
+}
+
+int rr_digamma_f32(const float* x, int64_t n, float* y, rr_stream_t stream) {
+  RR_CHECK_ARG(x && y && n >= 0);
+  if (n == 0) return RR_OK;
+  digamma_kernel<<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(x, n, y);
+  return rr_launch_status();
+}
+
+// ---------------------------------------------------------------- Lognorm, exp-MSE
+int rr_lognorm_fwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, float* loss,
+                       float* partial, rr_stream_t stream) {
+  RR_CHECK_ARG(score && var && targets && loss && partial && n >= 0 && stride >= 1);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nb = pointwise_blocks(n);
+  pointwise_ext_fwd_kernel<kLognorm><<<nb, 256, 0, s>>>(score, var, stride, targets, n, partial);
+  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
+  return rr_launch_status();
+}
+
+int rr_lognorm_bwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, const float* gloss,
+                       float* dscore, float* dvar, int64_t dstride, rr_stream_t stream) {
+  RR_CHECK_ARG(score && var && targets && gloss && dscore && dvar && n >= 0 && stride >= 1 && dstride >= 1);
+  if (n == 0) return RR_OK;
+  pointwise_ext_bwd_kernel<kLognorm><<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      score, var, stride, targets, n, gloss, dscore, dvar, dstride);
+  return rr_launch_status();
+}
+
+int rr_exp_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
+                       rr_stream_t stream) {
+  RR_CHECK_ARG(pred && targets && loss && partial && n >= 0 && stride >= 1);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nb = pointwise_blocks(n);
+  pointwise_ext_fwd_kernel<kExpMse><<<nb, 256, 0, s>>>(pred, nullptr, stride, targets, n, partial);
+  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
+  return rr_launch_status();
+}
+
+int rr_exp_mse_bwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, const float* gloss, float* dpred,
+                       int64_t dstride, rr_stream_t stream) {
+  RR_CHECK_ARG(pred && targets && gloss && dpred && n >= 0 && stride >= 1 && dstride >= 1);
+  if (n == 0) return RR_OK;
+  pointwise_ext_bwd_kernel<kExpMse><<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      pred, nullptr, stride, targets, n, gloss, dpred, nullptr, dstride);
   return rr_launch_status();
 }
 

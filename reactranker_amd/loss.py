@@ -1,10 +1,12 @@
-"""Ranking / pointwise losses — mirror of reference `reactranker/train/loss.py` for the losses on
-the hot path (MLEloss :64-99, ListnetLoss :317-352, evidential_ranking :477-556, GaussDisLoss
-:144-162, LogCumsumExp :9-61) plus RankNet's inline loss (train/train_pairwise.py:99-137).
+"""Ranking / pointwise losses — mirror of reference `reactranker/train/loss.py`: the losses on the hot
+path (MLEloss :64-99, ListnetLoss :317-352, evidential_ranking :477-556, GaussDisLoss :144-162,
+LogCumsumExp :9-61), RankNet's inline loss (train/train_pairwise.py:99-137), and the rest of the
+trainer's import line (MLEDisLoss, Lognorm, Listnet_For_evidential, Listnet_For_Gauss, Listnetlognorm,
+Listnet_with_uq, evidential_loss_new, Dirichlet_uq) plus the regression_exploss expression.
 
-Same call signatures `loss(score, scope, targets, gpu)` and return shapes ([1] for ListMLE and
-evidential_ranking, 0-d for ListNet).  Each loss is one fused HIP kernel per direction (one
-wavefront per query) instead of a Python loop of ~10 ATen ops per query.
+Same call signatures (`loss(score, scope, targets, gpu)` and kin) and return shapes ([1] for the
+per-query means, 0-d for ListNet and the pointwise means).  Each loss is one fused HIP kernel per
+direction (one wavefront per query) instead of a Python loop of ~10 ATen ops per query.
 """
 from __future__ import annotations
 
@@ -370,3 +372,252 @@ def ranknet_lambda(y_pred, scope, targets, sigma: float = 1.0, gpu: int = None):
     check(lib().rr_ranknet_bwd_f32(ptr(s), s.stride(0), ptr(t), ptr(seg), len(scope), max_len, float(sigma), 1,
                                    ptr(one), ptr(out), 1, stream()), "rr_ranknet_bwd_f32")
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the remaining task types' losses
+def annealing_coef(max_coeff, epoch, epochs):
+    """The annealing coefficient of Listnet_with_uq / Dirichlet_uq (reference train/loss.py:393, 468), computed on the host as
+    there: epochs == 1 raises ZeroDivisionError in both."""
+    return max_coeff * (epoch / (epochs - 1)) ** 3
+
+
+def _columns(tensors, n, what):
+    """Columns 0 .. n-1 of torch.cat(tensors, 1) as 1-D views, without the copy (the reference concatenates, loss.py:120,
+    211, 253, 295); a 1-D tensor counts as one column."""
+    cols = []
+    for x in tensors:
+        if x.dim() == 1:
+            cols.append(x)
+        elif x.dim() == 2:
+            cols.extend(x[:, k] for k in range(x.shape[1]))
+        else:
+            raise RuntimeError(f"{what}: inputs must be [M] or [M, k], got {tuple(x.shape)}")
+    if len(cols) < n:
+        raise RuntimeError(f"{what}: needs {n} input columns, got {len(cols)}")
+    return cols[:n]
+
+
+_LISTWISE_COEF = ("listnet_uq", "dirichlet_uq")       # entries that take the annealing coefficient
+
+
+class _ListwiseVariantFn(torch.autograd.Function):
+    """rr_{kind}_fwd_f32 / rr_{kind}_bwd_f32 over 1-D (possibly strided) per-candidate inputs; loss shape [1]."""
+
+    @staticmethod
+    def forward(ctx, kind, coef, targets, seg, Q, max_len, *xs):
+        vs = [_vec(x.detach()) for x in xs]
+        dev = vs[0].device
+        for v in vs[1:]:
+            if v.shape[0] != vs[0].shape[0]:
+                raise RuntimeError(f"{kind}: inputs have {vs[0].shape[0]} and {v.shape[0]} rows")
+        loss, part = _f1(dev), torch.empty(max(Q, 1), dtype=torch.float32, device=dev)
+        args = [a for v in vs for a in (ptr(v), v.stride(0))] + [ptr(targets), ptr(seg), Q, max_len]
+        if kind in _LISTWISE_COEF:
+            args.append(float(coef))
+        name = f"rr_{kind}_fwd_f32"
+        check(getattr(lib(), name)(*args, ptr(loss), ptr(part), stream()), name)
+        ctx.save_for_backward(targets, seg, *vs)
+        ctx.meta = (kind, coef, Q, max_len, [tuple(x.shape) for x in xs])
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        targets, seg, *vs = ctx.saved_tensors
+        kind, coef, Q, max_len, shapes = ctx.meta
+        g = g.reshape(-1).contiguous().float()
+        ds = [torch.empty(v.shape[0], dtype=torch.float32, device=v.device) for v in vs]
+        args = [a for v in vs for a in (ptr(v), v.stride(0))] + [ptr(targets), ptr(seg), Q, max_len]
+        if kind in _LISTWISE_COEF:
+            args.append(float(coef))
+        name = f"rr_{kind}_bwd_f32"
+        check(getattr(lib(), name)(*args, ptr(g), *[ptr(d) for d in ds], 1, stream()), name)
+        return (None,) * 6 + tuple(d.reshape(sh) for d, sh in zip(ds, shapes))
+
+
+def _listwise(kind, xs, scope, targets, gpu, coef=0.0):
+    scope, seg, total, max_len, t = _prep(xs[0], scope, targets, gpu)
+    for x in xs[1:]:
+        _lib.require_cuda(x, kind)
+        if x.shape[0] != total:
+            raise RuntimeError(f"sum(scope) = {total} but an input has {x.shape[0]} rows")
+    return _ListwiseVariantFn.apply(kind, coef, t, seg, len(scope), max_len, *xs)
+
+
+class MLEDisLoss(nn.Module):
+    """ListMLE with a per-candidate variance (reference train/loss.py:102-141): mean and variance are [M, k] (or [M]);
+    columns 0 and 1 of their concatenation are the score and the variance, as there.  Returns shape [1]."""
+
+    def forward(self, mean, variance, scope, targets, gpu: int = None):
+        return _listwise("mledis", _columns((mean, variance), 2, "MLEDisLoss"), scope, targets, gpu)
+
+
+class Listnet_For_Gauss(nn.Module):
+    """Reference train/loss.py:233-272 (columns as in MLEDisLoss).  Returns shape [1]."""
+
+    def forward(self, mean, variance, scope, targets, gpu: int = None):
+        return _listwise("listnet_gauss", _columns((mean, variance), 2, "Listnet_For_Gauss"), scope, targets, gpu)
+
+
+class Listnetlognorm(nn.Module):
+    """Reference train/loss.py:275-314 (columns as in MLEDisLoss; scores must be non-zero).  Returns shape [1]."""
+
+    def forward(self, mean, variance, scope, targets, gpu: int = None):
+        return _listwise("listnet_lognorm", _columns((mean, variance), 2, "Listnetlognorm"), scope, targets, gpu)
+
+
+class Listnet_For_evidential(nn.Module):
+    """Reference train/loss.py:187-230: columns 0, 1, 2 of cat(mean, v, alpha).  Returns shape [1]."""
+
+    def forward(self, mean, v, alpha, scope, targets, gpu: int = None):
+        return _listwise("listnet_evidential", _columns((mean, v, alpha), 3, "Listnet_For_evidential"), scope, targets, gpu)
+
+
+def _one_column(x, what):
+    if x.dim() != 1:
+        raise RuntimeError(f"{what}: scores must be [M] (the task_num = 1 head's output), got {tuple(x.shape)}")
+    return x
+
+
+class Listnet_with_uq(nn.Module):
+    """Reference train/loss.py:355-399 on positive scores [M].  Returns shape [1]."""
+
+    def forward(self, score, scope, targets, max_coeff, epoch, epochs, gpu: int = None):
+        coef = annealing_coef(max_coeff, epoch, epochs)
+        return _listwise("listnet_uq", [_one_column(score, "Listnet_with_uq")], scope, targets, gpu, coef)
+
+
+class Dirichlet_uq(nn.Module):
+    """Reference train/loss.py:440-474 on positive concentrations [M].  Returns shape [1]."""
+
+    def forward(self, concentration, scope, targets, max_coeff, epoch, epochs, gpu: int = None):
+        coef = annealing_coef(max_coeff, epoch, epochs)
+        return _listwise("dirichlet_uq", [_one_column(concentration, "Dirichlet_uq")], scope, targets, gpu, coef)
+
+
+class _NigFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cross, lam, eps, targets, *params):
+        xs = [_vec(x.detach()) for x in params]
+        n = targets.shape[0]
+        dev = xs[0].device
+        loss, part = _f1(dev), torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        args = [a for x in xs for a in (ptr(x), x.stride(0))] + [ptr(targets), n, int(cross), float(lam)]
+        check(lib().rr_nig_fwd_f32(*args, float(eps), ptr(loss), ptr(part), stream()), "rr_nig_fwd_f32")
+        ctx.save_for_backward(targets, *xs)
+        ctx.meta = (cross, lam, [tuple(x.shape) for x in params])
+        return loss.reshape(())                         # torch.mean -> 0-d (reference loss.py:437)
+
+    @staticmethod
+    def backward(ctx, g):
+        targets, *xs = ctx.saved_tensors
+        cross, lam, shapes = ctx.meta
+        n = targets.shape[0]
+        g = g.reshape(-1).contiguous().float()
+        ds = [torch.empty(n, dtype=torch.float32, device=g.device) for _ in range(4)]
+        args = [a for x in xs for a in (ptr(x), x.stride(0))] + [ptr(targets), n, int(cross), float(lam)]
+        check(lib().rr_nig_bwd_f32(*args, ptr(g), *[ptr(d) for d in ds], 1, stream()), "rr_nig_bwd_f32")
+        return (None,) * 4 + tuple(d.reshape(sh) for d, sh in zip(ds, shapes))
+
+
+def evidential_loss_new(mu, v, alpha, beta, targets, gpu, lam=1, epsilon=1e-4):
+    """Deep-evidential-regression NLL + regulariser (reference train/loss.py:402-437), mean over the BROADCAST shape, 0-d.
+
+    Two forms, as torch broadcasting makes them: parameters [M] with targets [M] (elementwise), or parameters [M, 1] with
+    targets [M] - what the trainer passes (column slices of the [M, 4] output) - which evaluates every parameter row
+    against every target, M x M terms.  Any other shape is refused."""
+    if gpu is not None:
+        torch.cuda.set_device(gpu)
+    _lib.require_cuda(mu, "mu")
+    params = (mu, v, alpha, beta)
+    shape = tuple(mu.shape)
+    t = torch.as_tensor(targets, dtype=torch.float32)
+    if t.device != mu.device:
+        t = t.to(mu.device)
+    if t.dim() > 1 or any(tuple(x.shape) != shape for x in params):
+        raise ValueError(f"evidential_loss_new: parameters {[tuple(x.shape) for x in params]} with targets {tuple(t.shape)}: "
+                         "supported are parameters [M] or [M, 1], all alike, with targets [M]")
+    t = t.reshape(-1).contiguous()
+    M = t.shape[0]
+    if len(shape) == 1 and shape[0] == M:
+        cross = 0
+    elif len(shape) == 2 and shape[1] == 1 and shape[0] == M:
+        cross = 1
+    else:
+        raise ValueError(f"evidential_loss_new: parameters {shape} with targets [{M}]: "
+                         "supported are parameters [M] (elementwise) or [M, 1] (all M x M pairs) with targets [M]")
+    for x in params:
+        _lib.require_cuda(x, "evidential_loss_new parameter")
+    return _NigFn.apply(cross, float(lam), float(epsilon), t, *params)
+
+
+def digamma(x: torch.Tensor) -> torch.Tensor:
+    """The device digamma behind evidential_loss_new's d/dalpha (elementwise, float32, no autograd)."""
+    _lib.require_cuda(x, "x")
+    x = x.detach().float().contiguous()
+    y = torch.empty_like(x)
+    check(lib().rr_digamma_f32(ptr(x), x.numel(), ptr(y), stream()), "rr_digamma_f32")
+    return y
+
+
+class _PointwiseExtFn(torch.autograd.Function):
+    """Lognorm (kind 'lognorm': x = scores, var = std_scores) and exp-MSE (kind 'exp_mse', var None); 0-d mean."""
+
+    @staticmethod
+    def forward(ctx, kind, x, var, targets):
+        m = _vec(x.detach())
+        v = None if var is None else _vec(var.detach())
+        if v is not None and v.stride(0) != m.stride(0):
+            v = v.contiguous()
+            m = m.contiguous()
+        n = m.shape[0]
+        if targets.shape[0] != n or (v is not None and v.shape[0] != n):
+            raise RuntimeError(f"{kind}: inputs and targets lengths differ")
+        loss = _f1(m.device)
+        part = torch.empty(int(lib().rr_pointwise_partial_count(n)), dtype=torch.float32, device=m.device)
+        if v is None:
+            check(lib().rr_exp_mse_fwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(loss), ptr(part), stream()),
+                  "rr_exp_mse_fwd_f32")
+        else:
+            check(lib().rr_lognorm_fwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(loss), ptr(part), stream()),
+                  "rr_lognorm_fwd_f32")
+        ctx.save_for_backward(m, targets, *([] if v is None else [v]))
+        ctx.shapes = (tuple(x.shape), None if var is None else tuple(var.shape))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = ctx.saved_tensors
+        m, targets = saved[0], saved[1]
+        v = saved[2] if len(saved) > 2 else None
+        n = m.shape[0]
+        g = g.reshape(-1).contiguous().float()
+        dm = torch.empty(n, dtype=torch.float32, device=m.device)
+        if v is None:
+            check(lib().rr_exp_mse_bwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), 1, stream()),
+                  "rr_exp_mse_bwd_f32")
+            return None, dm.reshape(ctx.shapes[0]), None, None
+        dv = torch.empty(n, dtype=torch.float32, device=m.device)
+        check(lib().rr_lognorm_bwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), ptr(dv), 1, stream()),
+              "rr_lognorm_bwd_f32")
+        return None, dm.reshape(ctx.shapes[0]), dv.reshape(ctx.shapes[1]), None
+
+
+class Lognorm(nn.Module):
+    """Reference train/loss.py:165-184 (0-d mean).  The reference prints the value on every call; this one does not."""
+
+    def forward(self, scores, std_scores, targets, gpu: int = None):
+        if gpu is not None:
+            torch.cuda.set_device(gpu)
+        _lib.require_cuda(scores, "scores")
+        t = torch.as_tensor(targets, dtype=torch.float32).to(scores.device).reshape(-1).contiguous()
+        return _PointwiseExtFn.apply("lognorm", scores, std_scores, t)
+
+
+class ExpMSELoss(nn.Module):
+    """mean((exp(targets) - exp(output))^2): the 'regression_exploss' branch (reference train/train_listwise.py:274-279),
+    an inline expression there.  0-d."""
+
+    def forward(self, output, targets):
+        _lib.require_cuda(output, "output")
+        t = torch.as_tensor(targets, dtype=torch.float32).to(output.device).reshape(-1).contiguous()
+        return _PointwiseExtFn.apply("exp_mse", output, None, t)

@@ -1,6 +1,6 @@
 """Listwise training loop on pre-packed batches: the loop body, loss dispatch, validation and checkpoint selection
-of the reference trainer (reactranker/train/train_listwise.py:21-372) for the task types whose losses exist in
-reactranker_amd.loss.  The reference's DataFrame / SMILES plumbing (DataProcessor, Parsing_features: out of scope,
+of the reference trainer (reactranker/train/train_listwise.py:21-372) for every task type whose branch works there
+(SUPPORTED_TASKS; not 'mle_dirichlet', which raises NameError in the reference).  The reference's DataFrame / SMILES plumbing (DataProcessor, Parsing_features: out of scope,
 SURVEY.md section 2 row 17) is replaced by an iterable of batches; everything downstream of
 `model(r_inputs, p_inputs, gpu=gpu, add_features=...)` keeps the reference's call shapes.
 
@@ -20,7 +20,9 @@ from .utils import save_checkpoint
 
 NDCG_METRICS = ["NDCG@1", "NDCG@2", "NDCG@25%", "NDCG@all"]
 SUPPORTED_TASKS = ("mle", "listnet", "evidential_ranking", "gauss_regression", "mle_gaussian", "listnet_gauss",
-                   "mle_regression", "listnet_regression", "regression")
+                   "mle_regression", "listnet_regression", "regression",
+                   "mledis_gaussian", "listnetdis_gauss", "listnetdis_lognorm", "listnet_uq", "evidential", "mle_evidential",
+                   "mledis_evidential", "listnet_evidential", "dirichlet_uq", "regression_exploss")
 
 
 def standardize_targets(train_targets, val_targets, target_name: str = "ea", normalize_target=True, save_metric=None):
@@ -107,6 +109,35 @@ def batch_loss(task_type: str, output, scope, targets, gpu, epoch: int = 0, epoc
         return listnet(output, scope, targets, gpu) + mse(output, targets)
     if task_type == "regression":                       # the reference's default branch: nn.MSELoss
         return mse(output, targets)
+    if task_type == "mledis_gaussian":                  # the odd columns are log(variance) (:196-202)
+        return (RL.MLEDisLoss()(output[:, 0::2], torch.exp(output[:, 1::2]), scope, targets, gpu)
+                + gauss(output[:, 0], output[:, 1], targets, gpu))
+    if task_type == "listnetdis_gauss":
+        return (RL.Listnet_For_Gauss()(output[:, 0::2], output[:, 1::2], scope, targets, gpu)
+                + gauss(output[:, 0], output[:, 1], targets, gpu))
+    if task_type == "listnetdis_lognorm":               # its ListNet term is commented out in the reference (:215-219)
+        return RL.Lognorm()(output[:, 0], output[:, 1], targets, gpu)
+    if task_type == "listnet_uq":
+        return RL.Listnet_with_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)
+    if task_type == "dirichlet_uq":
+        return RL.Dirichlet_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)
+    if task_type == "regression_exploss":               # an inline expression there (:274-279)
+        return RL.ExpMSELoss()(output, targets)
+    if task_type in ("evidential", "mle_evidential", "mledis_evidential", "listnet_evidential"):
+        # NIG columns mu, v, alpha, beta of the [M, 4k] output (:229-260); [M, 1] slices against [M] targets: the M x M form
+        mu, lam, alpha, beta = output[:, 0::4], output[:, 1::4], output[:, 2::4], output[:, 3::4]
+        evid = RL.evidential_loss_new(mu, lam, alpha, beta, targets, gpu, lam=0.2 if task_type == "mle_evidential" else 0.1)
+        if task_type == "evidential":
+            return evid
+        if task_type == "mle_evidential":
+            return mle(output[:, 0], scope, targets, gpu) + evid
+        variance = beta / (lam * (alpha - 1))
+        if task_type == "mledis_evidential":
+            return RL.MLEDisLoss()(mu, variance, scope, targets, gpu) + evid
+        return RL.Listnet_For_Gauss()(mu, variance, scope, targets, gpu) + evid      # listnet_evidential
+    if task_type == "mle_dirichlet":
+        raise ValueError("task_type 'mle_dirichlet' raises NameError in the reference (its losses are never instantiated, "
+                         "train_listwise.py:267-269); it is not supported")
     raise ValueError(f"task_type {task_type!r} is not covered by reactranker_amd (supported: {SUPPORTED_TASKS})")
 
 
