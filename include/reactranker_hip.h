@@ -595,6 +595,44 @@ int rr_ranking_metrics_f32(const float* score, int64_t score_stride, const float
                            int Q, int max_len, double ratio, double ndcg_cut, int32_t* order, double* stats,
                            rr_stream_t stream);
 
+/* Per-candidate and per-query statistics of T >= 2 score samples of ragged lists: MC-dropout passes or ensemble members
+ * (the reference's deleted run_mc_model / run_ensemble_model, SURVEY.md:35-41; this is a definition of its own, not a port).
+ * Same list description as rr_ranking_metrics_f32: seg_off[Q+1], max_len <= 8192.  Sample t of candidate i (0 <= i < M =
+ * seg_off[Q]) is samples[t * sample_stride + i]; sample_stride >= M.  Per candidate (length M, f32):
+ *   mean       f64 sum in sample order / T, rounded once
+ *   std_dev    two-pass, unbiased (ddof = 1, torch.std): sqrt(sum_t (x_t - mean_f64)^2 / (T - 1)) in f64, rounded once
+ *   p_top1     share of the samples in which the candidate is its list's first maximum
+ *   mean_rank  mean 1-based rank; ranks are the stable descending order, ties by list position (the rule of
+ *              rr_ranking_metrics_f32's `order`), so rank 1 is the first maximum
+ * qstats[q*RR_UQ_NQSTATS + 0..3], float64:
+ *   0  entropy -sum p ln p of p_top1 over the list (natural log, p = 0 terms left out)
+ *   1  p_top1 of the TARGET's first maximum
+ *   2  p_top1 of the first maximum of `mean` (agreement of the mean ranking with the samples)
+ *   3  mean of std_dev over the list
+ * An empty list writes zeros.  One wavefront per list; LDS (4 + 8) * max_len bytes (96 KiB at 8192).  No atomics: the bits
+ * are run-to-run identical.  Status: RR_ERR_ARG for T < 2, a null pointer, a negative size or sample_stride < max_len;
+ * RR_ERR_UNSUPPORTED for max_len > 8192 or T * max_len >= 2^32 (32-bit rank sums). */
+#define RR_UQ_NQSTATS 4
+int rr_mc_sample_stats_f32(const float* samples, int64_t sample_stride, int T, const float* targets, const int32_t* seg_off,
+                           int Q, int max_len, float* mean, float* std_dev, float* p_top1, float* mean_rank, double* qstats,
+                           rr_stream_t stream);
+
+/* Does the uncertainty track the error?  err[n], unc[n] (f32, n >= 1) with their stable ascending orders order_err /
+ * order_unc (int64 row indices, ties in row order: torch.sort(stable=True) on the device - sorting stays torch plumbing).
+ * fractions[n_frac] (f64, device), each in [0, 1).  out[1 + 3 * n_frac] (f64, device):
+ *   out[0]            Spearman rho: the Pearson correlation of the tie-averaged ranks of err and unc (scipy.stats.spearmanr);
+ *                     NaN when either rank vector is constant
+ *   out[1 + 3f ...]   for fraction f, k = floor(f * n): the k most uncertain rows - the first k of the stable DESCENDING
+ *                     order of unc (ties by row index) - are removed; kept = n - k, mae = sum |e| / kept,
+ *                     rmse = sqrt(sum e^2 / kept) over the rows that remain
+ * (the reference's deleted spearman_coef / erro_confidence).  Two launches: per-block partials of RR_UQ_CAL_BLOCK rows into
+ * `workspace` (at least ceil(n / RR_UQ_CAL_BLOCK) * (3 + 2 * n_frac) doubles; RR_ERR_WORKSPACE otherwise), then one
+ * workgroup sums them in block order - run-to-run identical bits, no atomics. */
+#define RR_UQ_CAL_BLOCK 256
+int rr_uq_calibration_f64(const float* err, const float* unc, const int64_t* order_err, const int64_t* order_unc, int64_t n,
+                          const double* fractions, int n_frac, void* workspace, size_t workspace_bytes, double* out,
+                          rr_stream_t stream);
+
 /* LogCumsumExp along dim 0 of a 1-D tensor (train/loss.py:9-61); n <= 8192.
  * backward keeps the reference's un-shifted exp(x) (:59). */
 int rr_logcumsumexp_fwd_f32(const float* x, int n, float* y, rr_stream_t stream);

@@ -238,6 +238,10 @@ _SIGS = {
     "rr_exp_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, i64, c_stream]),
     "rr_ranking_metrics_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, C.c_double, C.c_double, c_i32p, C.c_void_p,
                                c_stream]),
+    "rr_mc_sample_stats_f32": (i32, [c_f32p, i64, i32, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
+                                     c_stream]),
+    "rr_uq_calibration_f64": (i32, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.c_void_p, C.c_size_t,
+                                    C.c_void_p, c_stream]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
