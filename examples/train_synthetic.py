@@ -3,6 +3,11 @@
 build_model -> build_optimizer -> build_lr_scheduler -> train -> checkpoint, main.py:90-140).  Needs an MI355X.
 
     python examples/train_synthetic.py --task-type mle --epochs 5 --queries 256 --cands 32
+
+The pairwise trainer's selectors (run_train_pairwise.run_train) are reached with --task-type ranknet (--train-strategy
+sum_session | accelerate_grad), betanet, betanet_evidential, or pair_baseline (the three-graph pair model):
+
+    python examples/train_synthetic.py --task-type betanet --epochs 3 --queries 64 --cands 8
 """
 import argparse
 import logging
@@ -15,6 +20,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
+from reactranker_amd import ranknet_baseline                          # noqa: E402
+from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
 from reactranker_amd.utils import load_checkpoint                     # noqa: E402
@@ -28,8 +35,15 @@ def make_batches(seed, n_queries, cands, per_batch):
         tg = np.array([s.edges.shape[0] for s in qb.p_specs], np.float32) * 0.3 + qb.add_features[:, 0]
         tg = (tg - tg.mean()) / (tg.std() + 1e-6) + 1e-3 * np.arange(len(tg), dtype=np.float32)
         out.append(dict(r=featurization.BatchMolGraph(qb.r_specs, K=4), p=featurization.BatchMolGraph(qb.p_specs, K=4),
-                        scope=qb.scope, targets=torch.tensor(tg.astype(np.float32)), add=qb.add_features))
+                        scope=qb.scope, targets=torch.tensor(tg.astype(np.float32)), add=qb.add_features,
+                        mols_r=qb.r_specs, mols_p=qb.p_specs))
     return out
+
+
+PAIRWISE = {   # --task-type -> (train_strategy or None = --train-strategy, run_train's task_type)
+    "ranknet": (None, "baseline"), "betanet": ("sum_session", "BetaNet"),
+    "betanet_evidential": ("sum_session", "BetaNet_envidential"), "pair_baseline": ("baseline", "baseline"),
+}
 
 
 def head_for(task_type):
@@ -54,6 +68,8 @@ def head_for(task_type):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task-type", default="mle")
+    ap.add_argument("--train-strategy", default="sum_session", help="with --task-type ranknet: sum_session | accelerate_grad")
+    ap.add_argument("--pair-batch", type=int, default=256, help="with --task-type pair_baseline: pairs per optimizer step")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--queries", type=int, default=256)
     ap.add_argument("--cands", type=int, default=32)
@@ -64,14 +80,35 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     log = logging.getLogger("train_synthetic")
-    model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
-                        add_features_dim=1, **head_for(args.task_type))
+    if args.task_type == "pair_baseline":                 # positive outputs for pred_p = y / sum(y)
+        model = ranknet_baseline.build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True,
+                                             dropout=0.1, task_num=2, ffn_last_layer="evidential")
+    elif args.task_type == "betanet_evidential":          # positive scores: the evidence
+        model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
+                            add_features_dim=1, task_num=1, ffn_last_layer="evidential")
+    elif args.task_type in PAIRWISE:
+        model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
+                            add_features_dim=1, task_num=1, ffn_last_layer="no_softplus")
+    else:
+        model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
+                            add_features_dim=1, **head_for(args.task_type))
     log.info("parameters: %d", param_count(model))
     train_b = make_batches(0, args.queries, args.cands, args.batch_queries)
     val_b = make_batches(10 ** 6, max(args.batch_queries, args.queries // 8), args.cands, args.batch_queries)
     opt = build_optimizer(model.cuda(args.gpu))
     sch = build_lr_scheduler(opt, warmup_epochs=2, total_epochs=args.epochs, train_data_size=args.queries,
                              batch_size=args.batch_queries, init_lr=1e-4, max_lr=1e-3, final_lr=1e-4)
+    if args.task_type in PAIRWISE:
+        strategy, task = PAIRWISE[args.task_type]
+        hist = run_train(model, sch, train_b, val_b, args.checkpoint, opt, args.epochs, seed=0, gpu=args.gpu,
+                         train_strategy=strategy or args.train_strategy, task_type=task, logger=log, target_name=None,
+                         batch_size=args.pair_batch, val_batch_size=args.pair_batch)
+        key = "acc" if args.task_type == "pair_baseline" else "top1"
+        best = max(hist, key=lambda h: h[key])
+        log.info("best epoch %d: %s %.4f", best["epoch"], key, best[key])
+        load_checkpoint(args.checkpoint, model)
+        log.info("checkpoint %s restored", args.checkpoint)
+        return
     rng = np.random.default_rng(0)
     hist = train(model, sch, lambda ep: [train_b[i] for i in rng.permutation(len(train_b))], val_b, args.checkpoint, opt,
                  args.epochs, seed=0, gpu=args.gpu, task_type=args.task_type, logger=log, save_metric="NDCG@all")

@@ -829,6 +829,51 @@ enum { RR_SAVED_R_MSG = 0,    /* reactant encoder: message after iteration `inde
 int rr_reaction_saved_f32(const rr_model* model, const rr_step* step, int flags, int which, int index,
                           const float** ptr, int64_t* rows, int64_t* ld);
 
+/* ------------------------------------------------------------------ the pairwise trainer's remaining strategies --- */
+/* BetaNet and BetaNet_envidential (train/train_pairwise.py:176-338): a C x C loss per query on the first score column, list
+ * description as for RankNet above (seg_off[Q+1], max_len <= 8192, RR_ERR_UNSUPPORTED above).  Matrices are oriented as the
+ * reference builds them: entry (i, j) takes "alpha" from candidate j and "beta" from candidate i.
+ *   BetaNet: tau = sigmoid(t), pi = sigmoid(s); x1 = tau_j / (tau_i + tau_j), x2 = tau_i / (tau_i + tau_j); (aT, bT) = alpha0 (x1, x2);
+ *   (aP, bP) = alpha0 (pi_j, pi_i) / (pi_i + pi_j); lt, lp = ln Beta(aT, bT) / Beta(aP, bP) density at x1; entry = exp(lt) (lt - lp).
+ *   Evidential: tau = sigmoid(t), p = s (positive); T1, T2, P1, P2 likewise, S = p_i + p_j;
+ *   entry = (T1-P1)^2 + (T2-P2)^2 + (P1 (1-P1) + P2 (1-P2)) / (S + 1) + coef * 2 |ln(T1 / P1) (p_j - 1)|.
+ * loss_sum = sum over queries and all C x C entries (diagonal included), pairs = sum of C^2 - C.  partial: Q doubles.
+ * bwd: dscore = *gloss * d loss_sum / d score, every row written by the lane that owns it (no atomics; run-to-run identical).
+ * Entries are evaluated in double.  LDS 12 * max_len bytes.  Status: RR_ERR_ARG for a null pointer, a stride < 1, a negative
+ * size or alpha0 <= 0 - checked before any launch. */
+int rr_betanet_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
+                       int max_len, float alpha0, float* loss_sum, int64_t* pairs, double* partial, rr_stream_t stream);
+int rr_betanet_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
+                       int max_len, float alpha0, const float* gloss, float* dscore, int64_t dscore_stride,
+                       rr_stream_t stream);
+int rr_beta_evidential_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
+                               int Q, int max_len, float coef, float* loss_sum, int64_t* pairs, double* partial,
+                               rr_stream_t stream);
+int rr_beta_evidential_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
+                               int Q, int max_len, float coef, const float* gloss, float* dscore, int64_t dscore_stride,
+                               rr_stream_t stream);
+/* pairwise_acc and eval_cross_entropy_loss (train/eval.py:180-224, 15-73) in one pass.  qstats [Q, 4] doubles = { npos = #{t_i > t_j},
+ * sum_ij |[s_i > s_j] - [t_i > t_j]|, sum over t_i != t_j of 0.5 (1 - S_ij) x - logsigmoid(-x) with x = sigma (s_i - s_j), 0 };
+ * out [4] doubles = { sum over queries with npos > 0 of 1 - mismatches / (2 npos), number of those queries, sum of the
+ * cross-entropy terms, sum of 2 npos }: pairwise_acc = out[0] / out[1], eval_cross_entropy_loss = out[2] / out[3]. */
+int rr_pairwise_eval_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
+                         int max_len, float sigma, double* qstats, double* out, rr_stream_t stream);
+/* The baseline pair loop on [B, 2] outputs y and [B, 2] targets (train_pairwise.py:27-59; row strides ldy, ldt >= 2):
+ * loss = mean_b sum_k (softmax(t_b)_k - y_bk / (y_b0 + y_b1))^2; partial: rr_pair_partial_count(B) doubles.
+ * rr_pair_acc_f32: 1 - mean_b |[y_b0 > y_b1] - [tp_b0 > tp_b1]| (eval.py:262-266), B >= 1. */
+int64_t rr_pair_partial_count(int64_t B);
+int rr_pair_softmax_mse_fwd_f32(const float* y, int64_t ldy, const float* targets, int64_t ldt, int64_t B, float* loss,
+                                double* partial, rr_stream_t stream);
+int rr_pair_softmax_mse_bwd_f32(const float* y, int64_t ldy, const float* targets, int64_t ldt, int64_t B,
+                                const float* gloss, float* dy, int64_t ldd, rr_stream_t stream);
+int rr_pair_acc_f32(const float* y, int64_t ldy, const float* targets, int64_t ldt, int64_t B, float* acc,
+                    rr_stream_t stream);
+/* out[row] = (h1[i1[row]] - hr[ir[row]]) + (h2[i2[row]] - hr[ir[row]]) over [n_rows, H]: the input of the pair model's
+ * difference encoder (models/ranknet_baseline.py:57-61).  The three sources share the row pitch ld; a NULL index array is
+ * the identity.  H % 4 == 0, pitches % 4 == 0 and 16-byte aligned pointers (RR_ERR_ALIGN otherwise). */
+int rr_pair_combine_f32(const float* hr, const float* h1, const float* h2, int64_t ld, const int32_t* ir, const int32_t* i1,
+                        const int32_t* i2, int64_t n_rows, int H, float* out, int64_t ld_out, rr_stream_t stream);
+
 /* ------------------------------------------------------------------ data-parallel gradient exchange (RCCL) --- */
 /* Queries are independent: one process per GPU, whole queries per rank, identical replicas, and ONE sum all-reduce of the
  * gradient buffers per optimizer step (the reference itself is single-process).  `comm` is an RCCL

@@ -206,6 +206,16 @@ _SIGS = {
                                             i64, c_stream]),
     "rr_ranknet_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, C.c_void_p, c_f32p, c_stream]),
     "rr_ranknet_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_betanet_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
+    "rr_betanet_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_beta_evidential_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
+    "rr_beta_evidential_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_pairwise_eval_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, C.c_void_p, C.c_void_p, c_stream]),
+    "rr_pair_partial_count": (i64, [i64]),
+    "rr_pair_softmax_mse_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, i64, c_f32p, C.c_void_p, c_stream]),
+    "rr_pair_softmax_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, i64, c_f32p, c_f32p, i64, c_stream]),
+    "rr_pair_acc_f32": (i32, [c_f32p, i64, c_f32p, i64, i64, c_f32p, c_stream]),
+    "rr_pair_combine_f32": (i32, [c_f32p, c_f32p, c_f32p, i64, c_i32p, c_i32p, c_i32p, i64, i32, c_f32p, i64, c_stream]),
     "rr_pointwise_partial_count": (i64, [i64]),
     "rr_mse_fwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, c_stream]),
     "rr_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, i64, c_stream]),

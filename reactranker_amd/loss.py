@@ -2,7 +2,9 @@
 path (MLEloss :64-99, ListnetLoss :317-352, evidential_ranking :477-556, GaussDisLoss :144-162,
 LogCumsumExp :9-61), RankNet's inline loss (train/train_pairwise.py:99-137), and the rest of the
 trainer's import line (MLEDisLoss, Lognorm, Listnet_For_evidential, Listnet_For_Gauss, Listnetlognorm,
-Listnet_with_uq, evidential_loss_new, Dirichlet_uq) plus the regression_exploss expression.
+Listnet_with_uq, evidential_loss_new, Dirichlet_uq) plus the regression_exploss expression, and the pairwise trainer's
+inline losses: the Beta-density KL of beta_dis_train_loop (train_pairwise.py:189-226), the evidential pair loss of
+beta_evi_train_loop (:276-307) and the pair loss of baseline_pairwise_training_loop (:33-59).
 
 Same call signatures (`loss(score, scope, targets, gpu)` and kin) and return shapes ([1] for the
 per-query means, 0-d for ListNet and the pointwise means).  Each loss is one fused HIP kernel per
@@ -621,3 +623,112 @@ class ExpMSELoss(nn.Module):
         _lib.require_cuda(output, "output")
         t = torch.as_tensor(targets, dtype=torch.float32).to(output.device).reshape(-1).contiguous()
         return _PointwiseExtFn.apply("exp_mse", output, None, t)
+
+
+# ---------------------------------------------------------------------------------------------- the pairwise trainer's remaining losses
+class _SqPairFn(torch.autograd.Function):
+    """loss_sum over all C x C entries of every query (csrc/pairwise.hip); backward = its true gradient.
+    kind 'betanet' (param = alpha0) or 'beta_evidential' (param = the annealing coefficient)."""
+
+    @staticmethod
+    def forward(ctx, score, targets, seg, Q, max_len, kind, param):
+        s = _vec(score.detach())
+        loss = _f1(s.device)
+        pairs = torch.empty(1, dtype=torch.int64, device=s.device)
+        part = torch.empty(max(Q, 1), dtype=torch.float64, device=s.device)
+        fwd = getattr(lib(), f"rr_{kind}_fwd_f32")
+        check(fwd(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, float(param), ptr(loss), ptr(pairs), ptr(part),
+                  stream()), f"rr_{kind}_fwd_f32")
+        ctx.save_for_backward(s, targets, seg)
+        ctx.meta = (Q, max_len, kind, float(param))
+        ctx.mark_non_differentiable(pairs)
+        return loss.reshape(()), pairs
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        s, targets, seg = ctx.saved_tensors
+        Q, max_len, kind, param = ctx.meta
+        g = g.reshape(-1).contiguous().float()
+        ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+        bwd = getattr(lib(), f"rr_{kind}_bwd_f32")
+        check(bwd(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, param, ptr(g), ptr(ds), 1, stream()),
+              f"rr_{kind}_bwd_f32")
+        return ds, None, None, None, None, None, None
+
+
+def betanet_loss(y_pred, scope, targets, alpha0: float = 100.0, gpu: int = None):
+    """The Beta-density KL loss of `beta_dis_train_loop` over a window of queries (reference train/train_pairwise.py:189-226):
+    tau = sigmoid(targets), pi = sigmoid(score); per query the sum over ALL C x C entries of exp(lt) * (lt - lp), where lt / lp
+    are the log densities of Beta(alpha0 * tau_j / (tau_i + tau_j), alpha0 * tau_i / (tau_i + tau_j)) and of the same with pi,
+    both at tau_j / (tau_i + tau_j).
+
+    Returns (loss_sum, pairs) like ranknet_loss: loss_sum is differentiable (the trainer divides by the window's pairs and calls
+    backward); pairs = sum of C * C - C (:198), an int64 device scalar.  `y_pred` may be [M] or [M, k] (first column)."""
+    if y_pred.dim() > 1:
+        y_pred = y_pred[:, 0]
+    if not alpha0 > 0:
+        raise ValueError("betanet_loss: alpha0 must be positive")
+    scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
+    return _SqPairFn.apply(y_pred, t, seg, len(scope), max_len, "betanet", alpha0)
+
+
+def beta_evidential_loss(y_pred, scope, targets, coef: float, gpu: int = None):
+    """The evidential pair loss of `beta_evi_train_loop` (reference train/train_pairwise.py:276-307): the raw scores are the
+    evidence (they must be positive - a softplus head; the reference gives NaN otherwise, and so does this), T = tau_j /
+    (tau_i + tau_j), P = p_j / (p_i + p_j); per query the sum over all C x C entries of (T1-P1)^2 + (T2-P2)^2 + (P1 (1-P1) +
+    P2 (1-P2)) / (p_i + p_j + 1) + coef * 2 |ln(T1 / P1) (p_j - 1)|.  coef: the annealing coefficient (`annealing_coef`).
+    Returns (loss_sum, pairs) like betanet_loss."""
+    if y_pred.dim() > 1:
+        y_pred = y_pred[:, 0]
+    scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
+    return _SqPairFn.apply(y_pred, t, seg, len(scope), max_len, "beta_evidential", coef)
+
+
+def sq_pairs(scope) -> int:
+    """sum of C * C - C over the queries of a window: the normaliser of the two losses above (train_pairwise.py:198, 274)."""
+    return int(sum(int(c) * int(c) - int(c) for c in scope))
+
+
+class _PairMseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, targets):
+        B = y.shape[0]
+        loss = _f1(y.device)
+        part = torch.empty(int(lib().rr_pair_partial_count(B)), dtype=torch.float64, device=y.device)
+        check(lib().rr_pair_softmax_mse_fwd_f32(ptr(y), y.stride(0), ptr(targets), targets.stride(0), B, ptr(loss), ptr(part),
+                                                stream()), "rr_pair_softmax_mse_fwd_f32")
+        ctx.save_for_backward(y, targets)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        y, targets = ctx.saved_tensors
+        B = y.shape[0]
+        g = g.reshape(-1).contiguous().float()
+        dy = torch.empty(B, 2, dtype=torch.float32, device=y.device)
+        check(lib().rr_pair_softmax_mse_bwd_f32(ptr(y), y.stride(0), ptr(targets), targets.stride(0), B, ptr(g), ptr(dy), 2,
+                                                stream()), "rr_pair_softmax_mse_bwd_f32")
+        return dy, None
+
+
+def _pair_rows(x, what, device=None):
+    t = torch.as_tensor(x, dtype=torch.float32)
+    if device is not None and t.device != device:
+        t = t.to(device)
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise RuntimeError(f"{what}: expected shape [B, 2], got {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) < 2:
+        t = t.contiguous()
+    return t
+
+
+def pair_softmax_mse(y_pred, targets):
+    """The loss `baseline_pairwise_training_loop` trains on (reference train/train_pairwise.py:33-59): targets [B, 2] ->
+    target_p = softmax over the pair, pred_p = y_pred / sum(y_pred), loss = mean_b sum_k (target_p - pred_p)^2.  (The loop's
+    variance, KL and annealing terms are computed there and then left out of the loss, :59.)  0-d, differentiable."""
+    _lib.require_cuda(y_pred, "y_pred")
+    y = _pair_rows(y_pred, "y_pred")
+    t = _pair_rows(targets, "targets", y.device)
+    if t.shape[0] != y.shape[0]:
+        raise RuntimeError("pair_softmax_mse: y_pred and targets hold different numbers of pairs")
+    return _PairMseFn.apply(y, t)

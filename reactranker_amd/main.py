@@ -36,6 +36,8 @@ class Config:
     batch_size: int = 64                        # queries per optimizer step (only enters the LR schedule here)
     task_type: str = "listnet"                  # loss: mle / listnet / evidential_ranking / regression / ... ; 'ranknet'
     train_strategy: str = "sum_session"         # RankNet only (main_ranknet.py:38): 'sum_session' | 'accelerate_grad'
+    pairwise_task_type: str = "baseline"        # task_type 'ranknet' only: run_train's task_type - 'baseline' | 'BetaNet' |
+                                                # 'BetaNet_envidential' (run_train_pairwise.py:66-90)
     target_name: Optional[str] = "lgk"          # None: targets are already standardised
     normalize_target: Union[bool, float, str] = True
     init_lr: float = 1e-4
@@ -129,7 +131,7 @@ def run(cfg: Config, folds: Callable[[int], Tuple[Sequence, Sequence, Sequence]]
                                        init_lr=cfg.init_lr, max_lr=cfg.max_lr, final_lr=cfg.final_lr)
         if cfg.task_type == "ranknet":
             run_train(model, scheduler, train_b, val_b, ck, optimizer, cfg.total_epochs, seed, cfg.gpu,
-                      train_strategy=cfg.train_strategy, task_type="baseline", logger=logger,
+                      train_strategy=cfg.train_strategy, task_type=cfg.pairwise_task_type, logger=logger,
                       target_name=cfg.target_name, save_metric=cfg.save_metric, group=group)
         else:
             train(model, scheduler, train_b, val_b, ck, optimizer, cfg.total_epochs, seed, cfg.gpu,

@@ -1,6 +1,7 @@
-"""RankNet epoch driver on pre-packed windows of whole queries: `run_train` of the reference
-(reactranker/train/run_train_pairwise.py:18-140) for the strategies main_ranknet.py uses ('sum_session' and
-'accelerate_grad', task_type 'baseline').  Standardises the targets like the reference (:36-45: z-score with the training
+"""Pairwise epoch driver on pre-packed windows of whole queries: `run_train` of the reference
+(reactranker/train/run_train_pairwise.py:18-140) with its five selectors (:66-90): train_strategy 'sum_session' /
+'accelerate_grad' (RankNet, what main_ranknet.py uses) and 'baseline' (the pair model of reactranker_amd.ranknet_baseline)
+under task_type 'baseline', and task_type 'BetaNet' / 'BetaNet_envidential'.  Standardises the targets like the reference (:36-45: z-score with the training
 set's statistics, sign flipped unless the target is 'lgk'), runs `factorized_training_loop` per epoch, evaluates on the
 validation windows with `evaluate_top_scores` (:91-96) and checkpoints on the selected metric (:97-117).  The DataFrame / SMILES side stays the reference's."""
 from __future__ import annotations
@@ -10,9 +11,11 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .eval import evaluate_top_scores
+from .eval import evaluate_top_scores, pairwise_baseline_acc
+from .pairs import pair_windows
 from .train_listwise import standardize_batches
-from .train_pairwise import factorized_training_loop
+from .train_pairwise import (baseline_pairwise_training_loop, beta_dis_train_loop, beta_evi_train_loop,
+                             factorized_training_loop)
 from .utils import save_checkpoint
 
 
@@ -28,8 +31,19 @@ def run_train(model: torch.nn.Module, scheduler, train_batches: Sequence, val_ba
               path_checkpoints: Union[str, List[str], None], optimizer, epochs: int, seed: int, gpu: int,
               train_strategy: str = "sum_session", task_type: str = "baseline", logger=None,
               target_name: Optional[str] = "ea", save_metric: Optional[str] = None, sigma: float = 1.0, epoch_hook=None,
-              group=None):
-    """Returns the per-epoch history [{epoch, train_loss, top1, pred_top25_in_targ_top25, top1_in_pred_top25 (the TARGET's
+              group=None, batch_size: int = 1000, val_batch_size: int = 500):
+    """Selectors as in the reference (:66-90): task_type 'BetaNet' -> beta_dis_train_loop (alpha0 = 100), 'BetaNet_envidential' ->
+    beta_evi_train_loop (max_coeff = 0.01; needs epochs >= 2 and a positive head), otherwise task_type 'baseline' with
+    train_strategy 'sum_session' / 'accelerate_grad' -> factorized_training_loop or 'baseline' -> the pair model's
+    baseline_pairwise_training_loop.  Anything else is a ValueError.
+
+    train_strategy 'baseline': `model` is a reactranker_amd.ranknet_baseline model and every window also carries `mols_r` /
+    `mols_p`, the reactant / product graph of each candidate; after the targets are standardised the pairs of all training
+    windows are cut into batches of `batch_size` (the short last one is skipped, train_pairwise.py:24) and those of the
+    validation windows into batches of `val_batch_size` (:103: 500).  Validation is pairwise_baseline_acc and the checkpoint is
+    written when it does not fall (:125-127); the history then holds {epoch, train_loss, acc, checkpoint}.
+
+    Otherwise returns the per-epoch history [{epoch, train_loss, top1, pred_top25_in_targ_top25, top1_in_pred_top25 (the TARGET's
     top-1 inside the predicted top-25 %), checkpoint, checkpoint_all (which of the three 'all' metrics improved)}].
     epoch_hook(epoch, model, record): optional observer called after every epoch's validation (not in the reference).
     group: data-parallel training under torch.distributed exactly as in reactranker_amd.train_listwise.train - every rank
@@ -37,18 +51,82 @@ def run_train(model: torch.nn.Module, scheduler, train_batches: Sequence, val_ba
     validation queries; the loss is normalised by the WINDOW's ordered pairs, gradients are summed over the ranks,
     validation statistics likewise, rank 0 writes the checkpoints (main_ranknet.py:143-160 is the single-process driver)."""
     from .dp import Exchange
-    if train_strategy not in ("sum_session", "accelerate_grad") or task_type != "baseline":
-        raise ValueError("reactranker_amd covers the RankNet strategies main_ranknet.py selects: train_strategy "
-                         "'sum_session' / 'accelerate_grad' with task_type 'baseline'")
+    selector = select_loop(train_strategy, task_type)
+    if selector == "BetaNet_envidential" and epochs < 2:
+        raise ValueError("task_type 'BetaNet_envidential' needs epochs >= 2: its annealing coefficient divides by epochs - 1 "
+                         "(reference train_pairwise.py:308 raises ZeroDivisionError)")
     if gpu is not None:
         torch.cuda.set_device(gpu)
     model = model.cuda(gpu)
     ex = Exchange(model, group)
     try:
-        return _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, train_strategy,
+        if selector == "pair_baseline":
+            return _run_train_pairs(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu,
+                                    logger, target_name, epoch_hook, ex, batch_size, val_batch_size)
+        return _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, selector,
                           logger, target_name, save_metric, sigma, epoch_hook, ex)
     finally:
         ex.close()
+
+
+def select_loop(train_strategy: str, task_type: str) -> str:
+    """The reference's if / elif chain (:66-90) as one name: 'pair_baseline', 'sum_session', 'accelerate_grad', 'BetaNet' or
+    'BetaNet_envidential'; ValueError for anything the reference's chain would fall through."""
+    if task_type == "baseline" and train_strategy == "baseline":
+        return "pair_baseline"
+    if task_type == "baseline" and train_strategy in ("sum_session", "accelerate_grad"):
+        return train_strategy
+    if task_type in ("BetaNet", "BetaNet_envidential"):
+        return task_type
+    raise ValueError("reactranker_amd covers the reference's pairwise selectors: train_strategy 'baseline' / 'sum_session' / "
+                     "'accelerate_grad' with task_type 'baseline', or task_type 'BetaNet' / 'BetaNet_envidential' "
+                     f"(got train_strategy {train_strategy!r}, task_type {task_type!r})")
+
+
+def _all_pairs(windows, batch_size):
+    mols_r, mols_p, scope, targets = [], [], [], []
+    for b in windows:
+        if "mols_r" not in b or "mols_p" not in b:
+            raise ValueError("train_strategy 'baseline' needs `mols_r` and `mols_p` (one graph per candidate) in every window")
+        mols_r += list(b["mols_r"])
+        mols_p += list(b["mols_p"])
+        scope += [int(c) for c in b["scope"]]
+        targets.append(np.asarray(torch.as_tensor(b["targets"]).cpu(), np.float32).reshape(-1))
+    t = np.concatenate(targets) if targets else np.zeros(0, np.float32)
+    return list(pair_windows(mols_r, mols_p, scope, t, batch_size))
+
+
+def _run_train_pairs(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, logger, target_name,
+                     epoch_hook, ex, batch_size, val_batch_size):
+    mean, std = 0.0, 1.0
+    if target_name is not None:
+        tn = "lgk" if target_name == "lgk" else "ea"
+        train_batches, val_batches, mean, std = standardize_batches(list(train_batches), list(val_batches), tn, True, None, ex)
+    train_pairs = _all_pairs(train_batches, batch_size)
+    val_pairs = _all_pairs(val_batches, val_batch_size)
+    ex.broadcast_model(model)
+    ex.check_same_steps(sum(1 for b in train_pairs if b["full"]), next(model.parameters()).device)
+    say = logger.info if (logger is not None and ex.is_writer) else (lambda *_: None)
+    score_old, history = 0.0, []
+    for epoch in range(epochs):
+        say("learning rate is: {}".format(optimizer.param_groups[0]["lr"]))
+        model.zero_grad()
+        model.train()
+        epoch_loss = baseline_pairwise_training_loop(epoch, epochs, model, optimizer, scheduler, train_pairs,
+                                                     batch_size=batch_size, max_coeff=0.001, gpu=gpu, exchange=ex)
+        acc = pairwise_baseline_acc(model, gpu, val_pairs)
+        saved = False
+        if acc >= score_old:                                  # :125-127
+            score_old = acc
+            if path_checkpoints is not None:
+                saved = True
+                if ex.is_writer:
+                    save_checkpoint(path_checkpoints, model, mean, std)
+        history.append(dict(epoch=epoch + 1, train_loss=float(epoch_loss), acc=float(acc), checkpoint=saved))
+        if epoch_hook is not None:
+            epoch_hook(epoch, model, history[-1])
+        say("Epoch [{}/{}],train_loss,{:.4f}, acc,{:.4f}".format(epoch + 1, epochs, epoch_loss, acc))
+    return history
 
 
 def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, train_strategy, logger,
@@ -67,8 +145,14 @@ def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, o
         say("learning rate is: {}".format(optimizer.param_groups[0]["lr"]))
         model.zero_grad()
         model.train()
-        epoch_loss = factorized_training_loop(epoch, model, optimizer, scheduler, train_batches, sigma=sigma,
-                                              training_algo=train_strategy, gpu=gpu, exchange=ex)
+        if train_strategy == "BetaNet":                       # :78-82
+            epoch_loss = beta_dis_train_loop(epoch, model, optimizer, scheduler, train_batches, alpha0=100, gpu=gpu, exchange=ex)
+        elif train_strategy == "BetaNet_envidential":         # :83-88
+            epoch_loss = beta_evi_train_loop(epoch, model, optimizer, scheduler, train_batches, max_coeff=0.01, epochs=epochs,
+                                             gpu=gpu, exchange=ex)
+        else:
+            epoch_loss = factorized_training_loop(epoch, model, optimizer, scheduler, train_batches, sigma=sigma,
+                                                  training_algo=train_strategy, gpu=gpu, exchange=ex)
         model.eval()
         with torch.no_grad():
             # evaluate_top_scores, not ranking_metrics (:91-96): its third value is the TARGET's top-1 inside the

@@ -1,4 +1,8 @@
-"""RankNet training loop on pre-packed windows of whole queries: `factorized_training_loop` of the reference
+"""The pairwise trainer's loops on pre-packed windows (reference reactranker/train/train_pairwise.py): RankNet's
+`factorized_training_loop` (:81-173), the two Beta loops `beta_dis_train_loop` (:176-262) and `beta_evi_train_loop` (:263-338),
+and the pair model's `baseline_pairwise_training_loop` (:6-78).
+
+RankNet training loop on pre-packed windows of whole queries: `factorized_training_loop` of the reference
 (reactranker/train/train_pairwise.py:81-173).  The reference runs one forward per query and accumulates loss /
 lambdas until `batch_size` candidates have been seen (:141-160); here a batch already IS such a window (its queries
 are scored in one forward, reactranker_amd.loss.ranknet_loss / ranknet_lambda handle every query of the window), so
@@ -12,7 +16,8 @@ from typing import Iterable
 
 import torch
 
-from .loss import backward as loss_backward, ranknet_lambda, ranknet_loss
+from .loss import (annealing_coef, backward as loss_backward, beta_evidential_loss, betanet_loss, pair_softmax_mse,
+                   ranknet_lambda, ranknet_loss, sq_pairs)
 
 
 def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, sigma: float = 1.0,
@@ -66,4 +71,110 @@ def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: I
     if not minibatch_loss:
         return float("nan")
     per_step = ex.sum(torch.cat(minibatch_loss).double())
+    return float(per_step.mean())
+
+
+def window_sq_pairs(batch, exchange, device) -> tuple:
+    """(this shard's, the whole window's) sum of C * C - C: the normaliser of the two Beta loops (:198, :230).  Counted from
+    `scope` on the host.  Under an active Exchange the window total is the `sq_pairs` entry of the batch's `global` counts
+    when it is there, otherwise one all-reduce - cached on the batch either way."""
+    if "_sq_pairs" not in batch:
+        local = sq_pairs(batch["scope"])
+        glob = local
+        if exchange is not None and exchange.on:
+            g = (batch.get("global") or {}).get("sq_pairs")
+            if g is None:
+                g = int(exchange.sum(torch.tensor([float(local)], dtype=torch.float64, device=device)).item())
+            glob = int(g)
+        batch["_sq_pairs"] = (local, glob)
+    return batch["_sq_pairs"]
+
+
+def _sq_pair_loop(loss_of, model, optimizer, scheduler, batches, gpu, exchange) -> float:
+    from .dp import Exchange
+    own_exchange = exchange is None
+    ex = exchange if exchange is not None else Exchange(model)
+    dev = next(model.parameters()).device
+    minibatch_loss = []
+    for b in batches:
+        local, pairs = window_sq_pairs(b, ex, dev)
+        if pairs == 0:                                   # nothing to normalise by (the reference would divide by zero)
+            continue
+        model.zero_grad()
+        if len(b["scope"]) > 0:
+            y_pred = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
+            loss_sum, _ = loss_of(y_pred, b["scope"], b["targets"])
+            loss = loss_sum / pairs
+            loss_backward(loss)
+            minibatch_loss.append(loss.detach().sum().reshape(1))
+        else:                                            # an empty shard: zero gradient, zero loss
+            minibatch_loss.append(torch.zeros(1, device=dev))
+        ex.reduce_grads(1.0)                             # already normalised by the WINDOW's count: a plain sum
+        optimizer.step()
+        scheduler.step()
+    model.zero_grad()
+    if own_exchange:
+        ex.close()
+    if not minibatch_loss:
+        return float("nan")
+    per_step = ex.sum(torch.cat(minibatch_loss).double())
+    return float(per_step.mean())
+
+
+def beta_dis_train_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, alpha0: float = 100, gpu: int = 0,
+                        exchange=None) -> float:
+    """One epoch of `task_type='BetaNet'` (:176-262); returns the mean of the per-step losses (:262).
+
+    The reference hard-codes "two queries per optimizer step" and its end-of-epoch flush raises AttributeError whenever a
+    partial group remains (:254 calls .item() on a Python int).  Here, as in factorized_training_loop, a pre-packed window IS
+    one optimizer step, normalised by the window's sum of C * C - C (:198, :230); a window whose count is 0 (only
+    one-candidate queries) is skipped.  exchange: a reactranker_amd.dp.Exchange; a batch is then this rank's shard of the
+    window and the normaliser is the whole window's count (window_sq_pairs)."""
+    return _sq_pair_loop(lambda y, scope, t: betanet_loss(y, scope, t, alpha0, gpu), model, optimizer, scheduler, batches, gpu,
+                         exchange)
+
+
+def beta_evi_train_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, max_coeff: float = 0.001,
+                        epochs: int = 100, gpu: int = 0, exchange=None) -> float:
+    """One epoch of `task_type='BetaNet_envidential'` (:263-338): the model's raw scores are the evidence, so it needs a
+    positive head (ffn_last_layer 'evidential' / 'with_softplus'); the penalty is annealed with max_coeff * (epoch /
+    (epochs - 1)) ** 3 (:308).  epochs == 1 is a ZeroDivisionError in the reference: a ValueError that says so here.
+    Windows, normaliser and `exchange` as in beta_dis_train_loop."""
+    if epochs == 1:
+        raise ValueError("beta_evi_train_loop: epochs == 1 makes the annealing coefficient max_coeff * (epoch / (epochs - 1)) "
+                         "** 3 a division by zero (reference train_pairwise.py:308); train for at least 2 epochs")
+    coef = annealing_coef(max_coeff, epoch, epochs)
+    return _sq_pair_loop(lambda y, scope, t: beta_evidential_loss(y, scope, t, coef, gpu), model, optimizer, scheduler, batches,
+                         gpu, exchange)
+
+
+def baseline_pairwise_training_loop(epoch: int, epochs: int, model, optimizer, scheduler, pair_batches: Iterable,
+                                    batch_size: int = 1000, max_coeff: float = 0.01, gpu: int = 0, exchange=None) -> float:
+    """One epoch of `train_strategy='baseline'` (:6-78) over pair batches (reactranker_amd.pairs.pair_windows): one optimizer
+    step per batch of exactly `batch_size` pairs - shorter ones are skipped (:24) - on loss = mean_b sum_k (softmax(t_b)_k -
+    y_bk / sum_k y_bk)^2 (:33-59; the loop's variance, KL and annealing terms never reach the loss, so `epochs` and
+    `max_coeff` are accepted and unused).  Returns the mean of the per-step losses (NaN when no batch was whole, as np.mean of
+    an empty list).  exchange: every rank holds its own pair batches of one global step and the same number of them; the
+    gradient is the mean over the ranks."""
+    from .dp import Exchange
+    own_exchange = exchange is None
+    ex = exchange if exchange is not None else Exchange(model)
+    minibatch_loss = []
+    for b in pair_batches:
+        if len(b["targets"]) < batch_size:
+            continue
+        model.zero_grad()
+        y_pred = model(b["r"], b["p1"], b["p2"], gpu=gpu)
+        loss = pair_softmax_mse(y_pred, b["targets"])
+        loss_backward(loss)
+        minibatch_loss.append(loss.detach().reshape(1))
+        ex.reduce_grads(1.0 / ex.world)
+        optimizer.step()
+        scheduler.step()
+    model.zero_grad()
+    if own_exchange:
+        ex.close()
+    if not minibatch_loss:
+        return float("nan")
+    per_step = ex.sum(torch.cat(minibatch_loss).double()) / ex.world
     return float(per_step.mean())
