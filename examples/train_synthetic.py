@@ -8,6 +8,11 @@ The pairwise trainer's selectors (run_train_pairwise.run_train) are reached with
 sum_session | accelerate_grad), betanet, betanet_evidential, or pair_baseline (the three-graph pair model):
 
     python examples/train_synthetic.py --task-type betanet --epochs 3 --queries 64 --cands 8
+
+Under `python -m torch.distributed.run --nproc-per-node N examples/train_synthetic.py ...` the listwise task types train data
+parallel: every rank builds the same batches and keeps its block of whole queries of each (dp.shard_query_batch).  Backend:
+$RR_DIST_BACKEND (default nccl = RCCL); RR_SINGLE_DEVICE=1 puts every rank on --gpu.  The four NIG task types need every target
+of a step and are refused there (one process trains them).
 """
 import argparse
 import logging
@@ -27,16 +32,24 @@ from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, par
 from reactranker_amd.utils import load_checkpoint                     # noqa: E402
 
 
-def make_batches(seed, n_queries, cands, per_batch):
+def make_batches(seed, n_queries, cands, per_batch, rank=0, world=1):
     out = []
     for b0 in range(0, n_queries, per_batch):
         qb = synth.make_queries(seed + b0, min(per_batch, n_queries - b0), cands)
         # a learnable target: a fixed function of the product graph and the extra feature, distinct inside a query
         tg = np.array([s.edges.shape[0] for s in qb.p_specs], np.float32) * 0.3 + qb.add_features[:, 0]
         tg = (tg - tg.mean()) / (tg.std() + 1e-6) + 1e-3 * np.arange(len(tg), dtype=np.float32)
-        out.append(dict(r=featurization.BatchMolGraph(qb.r_specs, K=4), p=featurization.BatchMolGraph(qb.p_specs, K=4),
-                        scope=qb.scope, targets=torch.tensor(tg.astype(np.float32)), add=qb.add_features,
-                        mols_r=qb.r_specs, mols_p=qb.p_specs))
+        qb.targets = tg.astype(np.float32)
+        extra = {}
+        if world > 1:                                     # this rank's whole queries of the step + the step's counts
+            from reactranker_amd import dp
+            qb, glob = dp.shard_query_batch(qb, rank, world)
+            extra["global"] = glob
+        some = len(qb.scope) > 0
+        out.append(dict(r=featurization.BatchMolGraph(qb.r_specs, K=4) if some else None,
+                        p=featurization.BatchMolGraph(qb.p_specs, K=4) if some else None,
+                        scope=qb.scope, targets=torch.tensor(qb.targets), add=qb.add_features,
+                        mols_r=qb.r_specs, mols_p=qb.p_specs, **extra))
     return out
 
 
@@ -80,6 +93,15 @@ def main():
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     log = logging.getLogger("train_synthetic")
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if world > 1:                                          # started by torch.distributed.run: data-parallel listwise training
+        if args.task_type in PAIRWISE:
+            raise SystemExit("examples/train_synthetic.py shards the listwise task types only; run the pairwise ones in one process")
+        import torch.distributed as dist
+        if not os.environ.get("RR_SINGLE_DEVICE"):
+            args.gpu = int(os.environ.get("LOCAL_RANK", "0"))
+        torch.cuda.set_device(args.gpu)
+        dist.init_process_group(os.environ.get("RR_DIST_BACKEND", "nccl"), rank=rank, world_size=world)
     if args.task_type == "pair_baseline":                 # positive outputs for pred_p = y / sum(y)
         model = ranknet_baseline.build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True,
                                              dropout=0.1, task_num=2, ffn_last_layer="evidential")
@@ -93,8 +115,8 @@ def main():
         model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
                             add_features_dim=1, **head_for(args.task_type))
     log.info("parameters: %d", param_count(model))
-    train_b = make_batches(0, args.queries, args.cands, args.batch_queries)
-    val_b = make_batches(10 ** 6, max(args.batch_queries, args.queries // 8), args.cands, args.batch_queries)
+    train_b = make_batches(0, args.queries, args.cands, args.batch_queries, rank, world)
+    val_b = make_batches(10 ** 6, max(args.batch_queries, args.queries // 8), args.cands, args.batch_queries, rank, world)
     opt = build_optimizer(model.cuda(args.gpu))
     sch = build_lr_scheduler(opt, warmup_epochs=2, total_epochs=args.epochs, train_data_size=args.queries,
                              batch_size=args.batch_queries, init_lr=1e-4, max_lr=1e-3, final_lr=1e-4)
@@ -113,9 +135,16 @@ def main():
     hist = train(model, sch, lambda ep: [train_b[i] for i in rng.permutation(len(train_b))], val_b, args.checkpoint, opt,
                  args.epochs, seed=0, gpu=args.gpu, task_type=args.task_type, logger=log, save_metric="NDCG@all")
     best = max(hist, key=lambda h: h["ndcg"][3])
-    log.info("best epoch %d: NDCG@all %.4f top1 %.4f", best["epoch"], best["ndcg"][3], best["top1"])
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()                                    # rank 0 wrote the checkpoint
+    if rank == 0:
+        log.info("best epoch %d: NDCG@all %.4f top1 %.4f", best["epoch"], best["ndcg"][3], best["top1"])
     load_checkpoint(args.checkpoint, model)
-    log.info("checkpoint %s restored", args.checkpoint)
+    if rank == 0:
+        log.info("checkpoint %s restored", args.checkpoint)
+    if world > 1:
+        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

@@ -449,6 +449,49 @@ int rr_evidential_ranking_step_f32(const float* mu, const float* var, int64_t st
                                    const int32_t* seg_off, int Q, int max_len, float* loss, float* partial,
                                    unsigned int* counter, float* dmu, float* dvar, int64_t dstride, rr_stream_t stream);
 
+/* A composite task type's loss and its gradient in ONE launch (additive: two new symbols, the ABI revision stays 8; a
+ * library without them fails a binding's symbol lookup, and rr_abi_task_loss_size() checks the struct layout).  The trainer's composite task types
+ * (train/train_listwise.py:196-285) add a per-list term and a per-candidate term over column slices of the head's output
+ * `out` [M, n_cols] (row stride ld_out, M = seg_off[Q]).  rr_task_loss_step_f32 writes loss = list term + point term and
+ * d loss / d out [M, n_cols] (row stride ld_dout; EVERY column of every row, exact zeros where the task reads none) for an
+ * upstream gradient of one.  One wavefront per query evaluates the list term on the staged list and the point term of the
+ * query's own candidates.
+ *   list term    reads                                   averaged over
+ *   MLE          column 0                                n_queries (mean over a list, then over lists)
+ *   LISTNET      column 0                                n_cands   (one mean over all candidates)
+ *   MLEDIS       column 0, variance = exp(column 1)      n_queries (the transform of the mledis_gaussian branch, :196-202;
+ *                                                                   d / d column 1 carries the factor exp(column 1))
+ *   LISTNET_GAUSS column 0, variance = column 1          n_queries
+ *   LISTNET_UQ / DIRICHLET_UQ  column 0, `coef`          n_queries (coef: the annealing coefficient)
+ *   point term   MSE: column 0;  GAUSS: mean = column 0, variance = the raw column 1      n_cands
+ * n_queries / n_cands are the counts to divide by: Q and M for one process, the whole step's counts for a shard of a
+ * data-parallel step (the shards' losses and gradients then add up to the unsharded ones).  A count of 0 scales by 0.
+ * `partial` is a [2, Q] workspace (list row, point row); the workgroup that finishes last sums both rows in a fixed order,
+ * so the loss has the same bits on every run.  `terms` (or NULL) receives the two terms; loss == terms[0] + terms[1]
+ * exactly.  `counter`: ONE device word per concurrent launch that the caller keeps.  PRECONDITION: it is zero (or a
+ * multiple of Q: the ticket is tested modulo Q) when the launch starts; the kernel leaves it at zero.  An empty query
+ * adds zero and still counts; max_len > 8192 -> RR_ERR_UNSUPPORTED, nothing is launched; Q == 0 writes a zero loss. */
+enum { RR_LIST_NONE = 0, RR_LIST_MLE = 1, RR_LIST_LISTNET = 2, RR_LIST_MLEDIS = 3, RR_LIST_LISTNET_GAUSS = 4,
+       RR_LIST_LISTNET_UQ = 5, RR_LIST_DIRICHLET_UQ = 6 };
+enum { RR_POINT_NONE = 0, RR_POINT_MSE = 1, RR_POINT_GAUSS = 2 };
+typedef struct rr_task_loss_args {
+  int list_term, point_term;          /* RR_LIST_*, RR_POINT_*: not both NONE */
+  const float* out;  int64_t ld_out;  /* [M, n_cols], row stride ld_out >= n_cols (a column slice of a wider tensor is fine) */
+  int n_cols;
+  const float* targets;               /* [M] */
+  const int32_t* seg_off;             /* [Q + 1] */
+  int Q, max_len;
+  float coef;
+  int64_t n_queries, n_cands;
+  float* loss;                        /* one float */
+  float* terms;                       /* [2] or NULL */
+  float* dout;  int64_t ld_dout;      /* [M, n_cols], row stride ld_dout >= n_cols */
+  float* partial;                     /* [2, Q] */
+  unsigned int* counter;
+} rr_task_loss_args;
+size_t rr_abi_task_loss_size(void);
+int rr_task_loss_step_f32(const rr_task_loss_args* args, rr_stream_t stream);
+
 /* ListNet top-1, one global mean over all candidates (train/loss.py:327-352). */
 int rr_listnet_fwd_f32(const float* score, int64_t score_stride, const float* targets,
                        const int32_t* seg_off, int Q, int max_len, int64_t total /* = seg_off[Q] */,

@@ -110,6 +110,20 @@ class FfnChainArgs(C.Structure):
     ]
 
 
+class TaskLossArgs(C.Structure):
+    """rr_task_loss_args"""
+    _fields_ = [
+        ("list_term", i32), ("point_term", i32), ("out", c_f32p), ("ld_out", i64), ("n_cols", i32), ("targets", c_f32p),
+        ("seg_off", c_i32p), ("Q", i32), ("max_len", i32), ("coef", f32), ("n_queries", i64), ("n_cands", i64),
+        ("loss", c_f32p), ("terms", c_f32p), ("dout", c_f32p), ("ld_dout", i64), ("partial", c_f32p), ("counter", C.c_void_p),
+    ]
+
+
+(RR_LIST_NONE, RR_LIST_MLE, RR_LIST_LISTNET, RR_LIST_MLEDIS, RR_LIST_LISTNET_GAUSS, RR_LIST_LISTNET_UQ,
+ RR_LIST_DIRICHLET_UQ) = range(7)
+RR_POINT_NONE, RR_POINT_MSE, RR_POINT_GAUSS = range(3)
+
+
 class Graph(C.Structure):
     _fields_ = [
         ("nA", i64), ("nB", i64), ("M", i64), ("K", i32), ("Kb", i32),
@@ -197,6 +211,8 @@ _SIGS = {
     "rr_listmle_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, i64, c_stream]),
     "rr_listmle_step_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, C.c_void_p, c_f32p, i64, c_stream]),
     "rr_listnet_step_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, i64, c_f32p, c_f32p, C.c_void_p, c_f32p, i64, c_stream]),
+    "rr_abi_task_loss_size": (C.c_size_t, []),
+    "rr_task_loss_step_f32": (i32, [C.POINTER(TaskLossArgs), c_stream]),
     "rr_evidential_ranking_step_f32": (i32, [c_f32p, c_f32p, i64, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, C.c_void_p, c_f32p,
                                              c_f32p, i64, c_stream]),
     "rr_listnet_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, i64, c_f32p, c_f32p, c_stream]),
@@ -324,6 +340,8 @@ def lib():
             raise RuntimeError("reactranker_amd: ctypes plan struct layout differs from the compiled header")
         if l.rr_abi_ffn_chain_size() != C.sizeof(FfnChainArgs):
             raise RuntimeError("reactranker_amd: ctypes rr_ffn_chain_args layout differs from the compiled header")
+        if l.rr_abi_task_loss_size() != C.sizeof(TaskLossArgs):
+            raise RuntimeError("reactranker_amd: ctypes rr_task_loss_args layout differs from the compiled header")
         _lib = l
     return _lib
 

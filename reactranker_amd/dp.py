@@ -5,7 +5,9 @@ section 2.1) — this is the north star's scaling path, not a port.
 
 Normalisation: ListMLE / evidential_ranking average over queries, ListNet
 and MSE over candidates, RankNet over pairs.  Each rank weights its local gradient by
-local_count / global_count so the reduced gradient equals the single-process one.
+local_count / global_count so the reduced gradient equals the single-process one.  Task types that
+sum terms with different normalisers (TASK_TERMS) divide every term by the whole step's count
+instead (train_listwise.batch_loss(norm=...)) and reduce with weight one.
 """
 from __future__ import annotations
 
@@ -188,6 +190,67 @@ def shard_query_batch(qb, rank: int, world: int):
 
 _KIND = {"mle": "mle", "evidential_ranking": "mle", "listnet": "listnet", "regression": "listnet", "gauss_regression": "listnet",
          "mse": "listnet", "ranknet": "ranknet"}
+
+
+# Per-term normalisers of every listwise task type (train_listwise.SUPPORTED_TASKS): (term, what its mean runs over).
+# "queries": a mean over each list, then over the lists of the step (the kernels' 1 / (C * Q)); "cands": ONE mean over the
+# candidates of the step.  Read off the kernels (csrc/loss.hip, csrc/task_loss.hip) and the reference losses they restate
+# (train/loss.py: MLEloss :94-99, ListnetLoss :347, GaussDisLoss :162, MLEDisLoss :136-141, Listnet_For_Gauss :266-272,
+# Lognorm :184, Listnet_with_uq :394-399, Dirichlet_uq :468-474, evidential_ranking :549-556, evidential_loss_new :437).
+# A task type whose terms do not all share one normaliser cannot be weighted by ONE factor per rank (GradBucket.allreduce):
+# train_listwise.batch_loss(norm=...) divides each term by the WHOLE step's count instead and the ranks' losses and
+# gradients simply add up.
+_MLE, _LISTNET, _GAUSS, _MSE = ("ListMLE", "queries"), ("ListNet top-1", "cands"), ("Gaussian NLL", "cands"), ("MSE", "cands")
+_NIG = ("NIG evidential (cross form)", "cands")
+TASK_TERMS = {
+    "mle": (_MLE,),
+    "listnet": (_LISTNET,),
+    "evidential_ranking": (("evidential_ranking", "queries"),),
+    "gauss_regression": (_GAUSS,),
+    "regression": (_MSE,),
+    "mle_gaussian": (_MLE, _GAUSS),
+    "listnet_gauss": (_LISTNET, _GAUSS),
+    "mle_regression": (_MSE, _MLE),
+    "listnet_regression": (_LISTNET, _MSE),
+    "mledis_gaussian": (("MLEDisLoss", "queries"), _GAUSS),
+    "listnetdis_gauss": (("Listnet_For_Gauss", "queries"), _GAUSS),
+    "listnetdis_lognorm": (("Lognorm", "cands"),),
+    "listnet_uq": (("Listnet_with_uq", "queries"),),
+    "dirichlet_uq": (("Dirichlet_uq", "queries"),),
+    "regression_exploss": (("exp-MSE", "cands"),),
+    "evidential": (_NIG,),
+    "mle_evidential": (_MLE, _NIG),
+    "mledis_evidential": (("MLEDisLoss", "queries"), _NIG),
+    "listnet_evidential": (("Listnet_For_Gauss", "queries"), _NIG),
+}
+# The reference evaluates evidential_loss_new on [M, 1] parameters against [M] targets (train_listwise.py:229-260): every
+# candidate of the step against every target of the step, across queries.  A shard does not hold the other ranks' targets.
+CROSS_STEP_TASKS = ("evidential", "mle_evidential", "mledis_evidential", "listnet_evidential")
+
+
+def task_terms(task_type: str):
+    """((term, normaliser), ...) of a listwise task type, normaliser in {"queries", "cands"}."""
+    try:
+        return TASK_TERMS[task_type]
+    except KeyError:
+        raise ValueError(f"task_type {task_type!r} has no entry in reactranker_amd.dp.TASK_TERMS "
+                         f"(known: {sorted(TASK_TERMS)})") from None
+
+
+def require_shardable(task_type: str) -> None:
+    """ValueError for a task type whose loss cannot be formed from a shard of the step."""
+    task_terms(task_type)
+    if task_type in CROSS_STEP_TASKS:
+        raise ValueError(f"task_type {task_type!r} cannot be trained data-parallel: its NIG term compares every candidate of the "
+                         "step with every target of the step, across queries (the reference's [M, 1]-against-[M] broadcast), "
+                         "and a rank's shard does not hold the other ranks' targets; train it in one process")
+
+
+def term_scales(task_type: str, scope, norm) -> list:
+    """Per term, the factor that turns its local mean into its share of the whole step's mean: local count / global count of
+    the term's own normaliser (`norm`: the step's global counts, Exchange.counts' second value)."""
+    local = dict(queries=len(scope), cands=int(sum(int(c) for c in scope)))
+    return [local[n] / max(1, int(norm[n])) for _, n in task_terms(task_type)]
 
 
 class Exchange:

@@ -72,6 +72,8 @@ class FusedStep:
     that already exists.  What a step no longer launches: the separate reduction of the per-query partials, autograd's
     ones_like(loss) fill, a `.sum()` over one element, the loss's backward kernel.  Any other upstream gradient (a plain
     `loss.backward()`, a scaled loss) takes the backward kernel as before - nothing depends on the fast path being hit.
+    The composite task types of TASK_STEPS do the same over the head's whole output (rr_task_loss_step_f32, csrc/task_loss.hip:
+    _TaskStepFn below); there another upstream gradient multiplies the stored gradient.
     hits counts the backward calls it served (tests)."""
     enabled = True
     hits = 0
@@ -623,6 +625,93 @@ class ExpMSELoss(nn.Module):
         _lib.require_cuda(output, "output")
         t = torch.as_tensor(targets, dtype=torch.float32).to(output.device).reshape(-1).contiguous()
         return _PointwiseExtFn.apply("exp_mse", output, None, t)
+
+
+# ---------------------------------------------------------------------------------------------- composite task types in one launch
+# task type -> (list term, point term, columns it reads, loss is 0-d) for rr_task_loss_step_f32 (csrc/task_loss.hip)
+TASK_STEPS = {
+    "mle_gaussian": (_lib.RR_LIST_MLE, _lib.RR_POINT_GAUSS, 2, False),
+    "listnet_gauss": (_lib.RR_LIST_LISTNET, _lib.RR_POINT_GAUSS, 2, True),
+    "mle_regression": (_lib.RR_LIST_MLE, _lib.RR_POINT_MSE, 1, False),
+    "listnet_regression": (_lib.RR_LIST_LISTNET, _lib.RR_POINT_MSE, 1, True),
+    "mledis_gaussian": (_lib.RR_LIST_MLEDIS, _lib.RR_POINT_GAUSS, 2, False),
+    "listnetdis_gauss": (_lib.RR_LIST_LISTNET_GAUSS, _lib.RR_POINT_GAUSS, 2, False),
+    "listnet_uq": (_lib.RR_LIST_LISTNET_UQ, _lib.RR_POINT_NONE, 1, False),
+    "dirichlet_uq": (_lib.RR_LIST_DIRICHLET_UQ, _lib.RR_POINT_NONE, 1, False),
+}
+
+
+def task_loss_step(list_term, point_term, out2d, targets, seg, Q, max_len, coef, n_queries, n_cands, dout2d, terms=None,
+                   counter=None):
+    """One rr_task_loss_step_f32 launch on out2d [M, n_cols] (unit column stride): returns the [1] loss, fills dout2d."""
+    dev = out2d.device
+    loss, part = _f1(dev), torch.empty(2 * max(Q, 1), dtype=torch.float32, device=dev)
+    a = _lib.TaskLossArgs(list_term=list_term, point_term=point_term, out=out2d.data_ptr(), ld_out=out2d.stride(0),
+                          n_cols=out2d.shape[1], targets=targets.data_ptr(), seg_off=seg.data_ptr(), Q=Q, max_len=max_len,
+                          coef=float(coef), n_queries=int(n_queries), n_cands=int(n_cands), loss=loss.data_ptr(),
+                          terms=None if terms is None else terms.data_ptr(), dout=dout2d.data_ptr(), ld_dout=dout2d.stride(0),
+                          partial=part.data_ptr(), counter=(_counter(dev) if counter is None else counter).data_ptr())
+    check(lib().rr_task_loss_step_f32(C.byref(a), stream()), "rr_task_loss_step_f32")
+    return loss
+
+
+class _TaskStepFn(torch.autograd.Function):
+    """A composite task type's loss over the head's output, loss and d loss / d out in one launch (FusedStep): the forward
+    keeps d loss / d out for an upstream gradient of one; `backward(loss)` with the library's constant one hands it out, any
+    other upstream gradient multiplies it."""
+
+    @staticmethod
+    def forward(ctx, out, targets, seg, Q, max_len, list_term, point_term, coef, n_queries, n_cands, scalar):
+        o = out.detach()
+        o2 = o if o.dim() == 2 else o.unsqueeze(1)
+        dout = torch.empty(tuple(out.shape), dtype=torch.float32, device=o.device)
+        loss = task_loss_step(list_term, point_term, o2, targets, seg, Q, max_len, coef, n_queries, n_cands,
+                              dout if dout.dim() == 2 else dout.unsqueeze(1))
+        ctx.dout = dout
+        return loss.reshape(()) if scalar else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d = ctx.dout
+        if d is None:
+            raise RuntimeError("reactranker_amd.loss: the gradient of this fused loss was already handed out (a second backward "
+                               "through a retained graph); set loss.FusedStep.enabled = False for that")
+        if _is_unit(g):                                  # handed out once, without a reference left behind: autograd keeps it
+            ctx.dout = None                              # as the leaf's .grad instead of cloning it
+            FusedStep.hits += 1
+        else:
+            d = d * g.reshape(()).float()
+        return (d,) + (None,) * 10
+
+
+def task_step_loss(task_type, output, scope, targets, gpu, coef=0.0, norm=None):
+    """batch_loss of one of TASK_STEPS through rr_task_loss_step_f32, or None where the entry does not apply (FusedStep off,
+    no gradient wanted, an output layout it does not know): the caller then forms the loss term by term.  norm: the counts
+    to divide by (mapping with `queries` and `cands`), None = this batch's own."""
+    spec = TASK_STEPS.get(task_type)
+    if spec is None or not FusedStep.enabled or not (torch.is_tensor(output) and output.requires_grad and torch.is_grad_enabled()):
+        return None
+    list_term, point_term, cols, scalar = spec
+    if output.dtype != torch.float32 or not output.is_cuda:
+        return None
+    if cols == 1:
+        if task_type in ("listnet_uq", "dirichlet_uq"):
+            ok = output.dim() == 1
+        else:
+            ok = output.dim() == 1 or (output.dim() == 2 and output.shape[1] == 1)
+    elif task_type in ("mledis_gaussian", "listnetdis_gauss"):   # their list term reads columns 0, 1 of cat(out[:, 0::2], out[:, 1::2])
+        ok = output.dim() == 2 and output.shape[1] == 2
+    else:
+        ok = output.dim() == 2 and output.shape[1] >= 2
+    if ok and output.dim() == 2:
+        ok = (output.stride(1) == 1 or output.shape[1] == 1) and output.stride(0) >= output.shape[1]
+    elif ok:
+        ok = output.stride(0) >= 1
+    if not ok:
+        return None
+    scope, seg, total, max_len, t = _prep(output, scope, targets, gpu)
+    nq, nc = (len(scope), total) if norm is None else (int(norm["queries"]), int(norm["cands"]))
+    return _TaskStepFn.apply(output, t, seg, len(scope), max_len, list_term, point_term, coef, nq, nc, scalar)
 
 
 # ---------------------------------------------------------------------------------------------- the pairwise trainer's remaining losses

@@ -88,57 +88,86 @@ def standardize_batches(train_batches, val_batches, target_name="ea", normalize_
     return split(train_batches, tr), split(val_batches, va), mean, std
 
 
-def batch_loss(task_type: str, output, scope, targets, gpu, epoch: int = 0, epochs: int = 1, max_coeff: float = 1e-4):
-    """The loss the reference trainer forms for one batch (train_listwise.py:196-285)."""
+def _loss_terms(task_type: str, output, scope, targets, gpu, epoch, epochs, max_coeff):
+    """The terms of the loss the reference trainer forms for one batch (train_listwise.py:196-285), in the order of
+    dp.TASK_TERMS[task_type]."""
     mle, listnet, evid, gauss, mse = RL.MLEloss(), RL.ListnetLoss(), RL.evidential_ranking(), RL.GaussDisLoss(), RL.MSELoss()
     if task_type == "mle":
-        return mle(output, scope, targets, gpu)
+        return [mle(output, scope, targets, gpu)]
     if task_type == "listnet":
-        return listnet(output, scope, targets, gpu)
+        return [listnet(output, scope, targets, gpu)]
     if task_type == "evidential_ranking":
-        return evid(output, scope, targets, max_coeff, epoch, epochs, gpu)
+        return [evid(output, scope, targets, max_coeff, epoch, epochs, gpu)]
     if task_type == "gauss_regression":
-        return gauss(output[:, 0], output[:, 1], targets, gpu)
+        return [gauss(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "mle_gaussian":
-        return mle(output[:, 0], scope, targets, gpu) + gauss(output[:, 0], output[:, 1], targets, gpu)
+        return [mle(output[:, 0], scope, targets, gpu), gauss(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "listnet_gauss":
-        return listnet(output[:, 0], scope, targets, gpu) + gauss(output[:, 0], output[:, 1], targets, gpu)
+        return [listnet(output[:, 0], scope, targets, gpu), gauss(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "mle_regression":
-        return mse(output, targets) + mle(output, scope, targets, gpu)
+        return [mse(output, targets), mle(output, scope, targets, gpu)]
     if task_type == "listnet_regression":
-        return listnet(output, scope, targets, gpu) + mse(output, targets)
+        return [listnet(output, scope, targets, gpu), mse(output, targets)]
     if task_type == "regression":                       # the reference's default branch: nn.MSELoss
-        return mse(output, targets)
+        return [mse(output, targets)]
     if task_type == "mledis_gaussian":                  # the odd columns are log(variance) (:196-202)
-        return (RL.MLEDisLoss()(output[:, 0::2], torch.exp(output[:, 1::2]), scope, targets, gpu)
-                + gauss(output[:, 0], output[:, 1], targets, gpu))
+        return [RL.MLEDisLoss()(output[:, 0::2], torch.exp(output[:, 1::2]), scope, targets, gpu),
+                gauss(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "listnetdis_gauss":
-        return (RL.Listnet_For_Gauss()(output[:, 0::2], output[:, 1::2], scope, targets, gpu)
-                + gauss(output[:, 0], output[:, 1], targets, gpu))
+        return [RL.Listnet_For_Gauss()(output[:, 0::2], output[:, 1::2], scope, targets, gpu),
+                gauss(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "listnetdis_lognorm":               # its ListNet term is commented out in the reference (:215-219)
-        return RL.Lognorm()(output[:, 0], output[:, 1], targets, gpu)
+        return [RL.Lognorm()(output[:, 0], output[:, 1], targets, gpu)]
     if task_type == "listnet_uq":
-        return RL.Listnet_with_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)
+        return [RL.Listnet_with_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)]
     if task_type == "dirichlet_uq":
-        return RL.Dirichlet_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)
+        return [RL.Dirichlet_uq()(output, scope, targets, max_coeff, epoch, epochs, gpu)]
     if task_type == "regression_exploss":               # an inline expression there (:274-279)
-        return RL.ExpMSELoss()(output, targets)
+        return [RL.ExpMSELoss()(output, targets)]
     if task_type in ("evidential", "mle_evidential", "mledis_evidential", "listnet_evidential"):
         # NIG columns mu, v, alpha, beta of the [M, 4k] output (:229-260); [M, 1] slices against [M] targets: the M x M form
         mu, lam, alpha, beta = output[:, 0::4], output[:, 1::4], output[:, 2::4], output[:, 3::4]
         evid = RL.evidential_loss_new(mu, lam, alpha, beta, targets, gpu, lam=0.2 if task_type == "mle_evidential" else 0.1)
         if task_type == "evidential":
-            return evid
+            return [evid]
         if task_type == "mle_evidential":
-            return mle(output[:, 0], scope, targets, gpu) + evid
+            return [mle(output[:, 0], scope, targets, gpu), evid]
         variance = beta / (lam * (alpha - 1))
         if task_type == "mledis_evidential":
-            return RL.MLEDisLoss()(mu, variance, scope, targets, gpu) + evid
-        return RL.Listnet_For_Gauss()(mu, variance, scope, targets, gpu) + evid      # listnet_evidential
+            return [RL.MLEDisLoss()(mu, variance, scope, targets, gpu), evid]
+        return [RL.Listnet_For_Gauss()(mu, variance, scope, targets, gpu), evid]      # listnet_evidential
     if task_type == "mle_dirichlet":
         raise ValueError("task_type 'mle_dirichlet' raises NameError in the reference (its losses are never instantiated, "
                          "train_listwise.py:267-269); it is not supported")
     raise ValueError(f"task_type {task_type!r} is not covered by reactranker_amd (supported: {SUPPORTED_TASKS})")
+
+
+def batch_loss(task_type: str, output, scope, targets, gpu, epoch: int = 0, epochs: int = 1, max_coeff: float = 1e-4, norm=None):
+    """The loss the reference trainer forms for one batch (train_listwise.py:196-285).
+
+    norm: None, or a mapping with the GLOBAL `queries` and `cands` counts of the step this batch is a shard of (what
+    dp.Exchange.counts returns as its second value).  Every term is then divided by the global count of its own normaliser
+    (dp.TASK_TERMS) instead of the batch's: the result is this shard's share of the whole step's loss - the shards' losses
+    add up to the unsharded loss and their gradients to the unsharded gradient.  The four NIG task types compare every
+    candidate with every target of the step and cannot be formed from a shard (ValueError).
+
+    The eight composite task types of loss.TASK_STEPS take one launch for the loss and its gradient (loss.FusedStep,
+    rr_task_loss_step_f32) when the output needs a gradient; FusedStep.enabled = False forms them term by term."""
+    from . import dp
+    if norm is not None:
+        dp.require_shardable(task_type)
+    if task_type in RL.TASK_STEPS:
+        coef = RL.annealing_coef(max_coeff, epoch, epochs) if task_type in ("listnet_uq", "dirichlet_uq") else 0.0
+        fused = RL.task_step_loss(task_type, output, scope, targets, gpu, coef, norm)
+        if fused is not None:
+            return fused
+    terms = _loss_terms(task_type, output, scope, targets, gpu, epoch, epochs, max_coeff)
+    if norm is not None:
+        terms = [t if f == 1.0 else t * f for t, f in zip(terms, dp.term_scales(task_type, scope, norm))]
+    loss = terms[0]
+    for t in terms[1:]:
+        loss = loss + t
+    return loss
 
 
 def train(model: torch.nn.Module, scheduler, train_batches: Union[Sequence, Callable[[int], Iterable]],
@@ -158,15 +187,18 @@ def train(model: torch.nn.Module, scheduler, train_batches: Union[Sequence, Call
     see reactranker_amd.dp.shard_query_batch - and of the validation queries.  Per step the rank's gradient is weighted
     by its share of the loss's normaliser and summed over the ranks in one all-reduce of the flat bucket the explicit
     backward writes into; validation statistics are summed over the ranks; rank 0 writes the checkpoints; every rank
-    returns the same history.  One process (no torch.distributed) runs the same code with the exchange switched off."""
+    returns the same history.  Task types that sum terms with different normalisers (dp.TASK_TERMS) instead divide every
+    term by the whole step's count (batch_loss(norm=...)) and sum the ranks' gradients unweighted; the four NIG task types need
+    every target of the step and are refused (ValueError) before the first step.  One process (no torch.distributed) runs the same code with the exchange switched off."""
     from .dp import Exchange
     torch.manual_seed(seed)
     torch.cuda.manual_seed_all(seed)
     model = model.cuda(gpu)
     ex = Exchange(model, group)
-    if ex.on and task_type not in ("mle", "listnet", "evidential_ranking", "regression", "gauss_regression"):
-        raise ValueError(f"data-parallel training covers losses with ONE normaliser; {task_type!r} sums two")
     try:
+        if ex.on:                                       # refused before the first step, on every rank
+            from .dp import require_shardable
+            require_shardable(task_type)
         return _train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, task_type, logger,
                       save_metric, max_coeff, mean, std, target_name, normalize_target, epoch_hook, ex)
     finally:
@@ -192,21 +224,30 @@ def _train(model, scheduler, train_batches, val_batches, path_checkpoints, optim
     history = []
     say = logger.info if (logger is not None and ex.is_writer) else (lambda *_: None)
     dev = next(model.parameters()).device
+    from .dp import _KIND
+    one_weight = task_type in _KIND                      # ONE normaliser: the rank's gradient is weighted as a whole
     for epoch in range(epochs):
         say("learning rate is: {}".format(optimizer.param_groups[0]["lr"]))
         model.train()
         loss = torch.zeros(1, device=dev)
         for b in (train_batches(epoch) if callable(train_batches) else train_batches):
             optimizer.zero_grad()
+            norm = None
+            if ex.on and not one_weight:                # terms with different normalisers: divide each by the step's count
+                local, glob = ex.counts(b, dev)
+                norm = glob
             if len(b["scope"]) > 0:
                 output = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
-                loss = batch_loss(task_type, output, b["scope"], b["targets"], gpu, epoch, epochs, max_coeff)
+                loss = batch_loss(task_type, output, b["scope"], b["targets"], gpu, epoch, epochs, max_coeff, norm=norm)
                 RL.backward(loss)                       # loss.backward() (:288) seeded with the library's constant one (loss.FusedStep)
             else:                                       # an empty shard: this rank adds nothing to the step
                 loss = torch.zeros(1, device=dev)
             if ex.on:
-                local, glob = ex.counts(b, dev)
-                w = ex.weight(task_type, local, glob)
+                if one_weight:
+                    local, glob = ex.counts(b, dev)
+                    w = ex.weight(task_type, local, glob)
+                else:                                   # the rank's loss is already its share of the step's: plain sums
+                    w = 1.0
                 ex.reduce_grads(w)
                 loss = loss.detach().reshape(-1)[:1] * w    # summed over the ranks below: the whole step's loss
             optimizer.step()
