@@ -438,7 +438,8 @@ int rr_listmle_bwd_f32(const float* score, int64_t score_stride, const float* ta
  * so a training step needs no second loss kernel, no separate reduction launch and no device-side gradient seed.  `loss`,
  * `partial` and `dscore` hold the bits rr_*_fwd_f32 / rr_*_bwd_f32 (with *gloss == 1.0f) write: same operations in the same
  * order, the per-query partials summed in the same fixed order by the workgroup that finishes last.  `counter` is ONE
- * zero-initialised device word per concurrent launch that the caller keeps; the kernel leaves it at zero. */
+ * device word per concurrent launch that the caller keeps.  PRECONDITION: it is zero (or a multiple of Q: the ticket is
+ * tested modulo Q) when the launch starts; the kernel leaves it at zero. */
 int rr_listmle_step_f32(const float* score, int64_t score_stride, const float* targets,
                         const int32_t* seg_off, int Q, int max_len, float* loss, float* partial /* [Q] */,
                         unsigned int* counter, float* dscore, int64_t dscore_stride, rr_stream_t stream);

@@ -2,11 +2,15 @@
 // pointwise MSE / Gaussian NLL and the standalone LogCumsumExp op.
 //
 // One 64-lane wavefront owns one list (a query's candidates).  The list is staged in LDS
-// (5 * max_len floats), ranked by target with an O(C^2/64) counting pass, and reduced /
+// (up to 5 * max_len floats), ranked by target with an O(C^2/64) counting pass, and reduced /
 // scanned with wave shuffles; lists longer than 64 give each lane a contiguous chunk.
 // Only wave-level synchronisation is used (no workgroup barrier), so waves of different
 // list lengths never wait on each other.  Per-query partials are finished by a fixed-order
 // second kernel: no float atomics, results are run-to-run identical.
+//
+// The kernels of the list losses are shells: stage the list, build its term (loss_list.h, where each loss formula is
+// written once - the composite step of task_loss.hip builds the same terms), write the partial with this entry point's
+// normaliser and / or hand the term an emit that stores the gradient, finish.
 //
 // The reference evaluates these losses as a Python loop of ~10 tiny ATen ops per query
 // (train/loss.py:86-97, 338-347, 504-554; train/train_pairwise.py:99-137).
@@ -15,124 +19,47 @@
 namespace {
 
 // ---------------------------------------------------------------- fused loss + gradient launches ("step" entry points)
-// One launch writes the loss AND d loss / d score for an upstream gradient of one (what `loss.backward()` feeds a loss that
-// is the root of the graph): the reference's trainer step (train_listwise.py:287-288) then needs no second loss kernel, no
-// separate reduction launch and no host-created gradient.  After its partial is written every workgroup draws a ticket; the
-// one that draws the last sums all partials in reduce_scale_kernel's order - 256 strided accumulators, then its halving
-// tree; here on one wave, lane l playing threads l, l + 64, l + 128, l + 192 - so the loss has the bits of the two-kernel
-// path, and re-arms the counter (one zero-initialised device word the caller keeps) for the next launch.
-__device__ inline void finish_last(const float* partial, int n, float scale, float* out, unsigned int* counter, int lane) {
-  __threadfence();                                                   // release: this workgroup's partial
-  unsigned int ticket = 0u;
-  if (lane == 0) ticket = atomicAdd(counter, 1u);
-  ticket = __shfl(ticket, 0, RR_WAVE);
-  if (ticket != static_cast<unsigned int>(n) - 1u) return;
-  __threadfence();                                                   // acquire: every other workgroup's partial
-  float a[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    float acc = 0.f;
-    for (int i = lane + 64 * u; i < n; i += 256) acc += partial[i];
-    a[u] = acc;
-  }
-  float r = (a[0] + a[2]) + (a[1] + a[3]);                           // tree steps o = 128 and o = 64
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) r += __shfl_down(r, o, RR_WAVE);  // red[t] += red[t + o] for t < o
-  if (lane == 0) {
-    out[0] = r * scale;
-    *counter = 0u;
-  }
+// mode 2 of the three kernels below writes the loss AND d loss / d score for an upstream gradient of one (what
+// `loss.backward()` feeds a loss that is the root of the graph; gloss == nullptr stands for it): the reference's trainer
+// step (train_listwise.py:287-288) then needs no second loss kernel, no separate reduction launch and no host-created
+// gradient.  Same operations in the same order as modes 0 (forward: partial) and 1 (backward: the gradient), and the
+// partials are summed by the last-arriving workgroup (finish_last, loss_list.h), so the bits are those of the two-kernel path.
+__device__ inline void finish_step(const float* partial, int n, float scale, float* loss, unsigned int* counter, int lane) {
+  float sum[1];
+  if (finish_last(partial, n, counter, lane, sum)) loss[0] = sum[0] * scale;
 }
 
 // ---------------------------------------------------------------- ListMLE
-__global__ void __launch_bounds__(RR_WAVE) listmle_fwd_kernel(const float* __restrict__ score, int64_t sstride,
-                                                              const float* __restrict__ targets,
-                                                              const int32_t* __restrict__ seg_off, int L,
-                                                              float* __restrict__ partial) {
+__global__ void __launch_bounds__(RR_WAVE) listmle_kernel(const float* __restrict__ score, int64_t sstride,
+                                                          const float* __restrict__ targets,
+                                                          const int32_t* __restrict__ seg_off, int L, int Q, int bwd,
+                                                          float* __restrict__ partial, const float* __restrict__ gloss,
+                                                          float* __restrict__ dscore, int64_t dstride, float scale = 0.f,
+                                                          float* __restrict__ loss = nullptr,
+                                                          unsigned int* __restrict__ counter = nullptr) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
   if (C <= 0) {
-    if (lane == 0) partial[q] = 0.f;
-    return;
-  }
-  ListView v = carve(sm, L);
-  for (int i = lane; i < C; i += RR_WAVE) {
-    v.s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    v.t[i] = targets[off + i];
-  }
-  wave_sync();
-  rank_sort(v, C, lane);
-  const float m = list_max(v.ss, C, lane);
-  logcumsumexp_rev(v.ss, v.aux, C, lane, m);
-  float acc = 0.f;
-  for (int i = lane; i < C; i += RR_WAVE) acc += v.aux[i] - v.ss[i];
-  acc = rr_wave_sum(acc);
-  if (lane == 0) partial[q] = acc / static_cast<float>(C);          // torch.mean, loss.py:94
-}
-
-__global__ void __launch_bounds__(RR_WAVE) listmle_bwd_kernel(const float* __restrict__ score, int64_t sstride,
-                                                              const float* __restrict__ targets,
-                                                              const int32_t* __restrict__ seg_off, int L, int Q,
-                                                              const float* __restrict__ gloss,
-                                                              float* __restrict__ dscore, int64_t dstride) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) return;
-  ListView v = carve(sm, L);
-  for (int i = lane; i < C; i += RR_WAVE) {
-    v.s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    v.t[i] = targets[off + i];
-  }
-  wave_sync();
-  rank_sort(v, C, lane);
-  const float m = list_max(v.ss, C, lane);
-  logcumsumexp_rev(v.ss, v.aux, C, lane, m);
-  cumsum_exp_neg(v.aux, v.t, C, lane);                              // v.t now holds cumsum(exp(-fd))
-  const float g = gloss[0] / (static_cast<float>(C) * static_cast<float>(Q));
-  for (int j = lane; j < C; j += RR_WAVE) {
-    // LogCumsumExp.backward keeps the un-shifted exp(x) (loss.py:59); "- 1" is d(-sorted_item)
-    const float d = g * (expf(v.ss[j]) * v.t[j]) - g;
-    dscore[static_cast<int64_t>(off + v.perm[j]) * dstride] = d;
-  }
-}
-
-// forward + backward (upstream gradient one) of a list in one pass over its staged copy; same operations in the same order
-// as the two kernels above, so partial[q] and dscore have their bits
-__global__ void __launch_bounds__(RR_WAVE) listmle_step_kernel(const float* __restrict__ score, int64_t sstride,
-                                                               const float* __restrict__ targets,
-                                                               const int32_t* __restrict__ seg_off, int L, int Q,
-                                                               float* __restrict__ partial, float* __restrict__ dscore,
-                                                               int64_t dstride, float scale, float* __restrict__ loss,
-                                                               unsigned int* __restrict__ counter) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) {
-    if (lane == 0) partial[q] = 0.f;
+    if (bwd != 1 && lane == 0) partial[q] = 0.f;
   } else {
-    ListView v = carve(sm, L);
+    const ListView v = carve(sm, L);
     for (int i = lane; i < C; i += RR_WAVE) {
       v.s[i] = score[static_cast<int64_t>(off + i) * sstride];
       v.t[i] = targets[off + i];
     }
     wave_sync();
-    rank_sort(v, C, lane);
-    const float m = list_max(v.ss, C, lane);
-    logcumsumexp_rev(v.ss, v.aux, C, lane, m);
-    float acc = 0.f;
-    for (int i = lane; i < C; i += RR_WAVE) acc += v.aux[i] - v.ss[i];
-    acc = rr_wave_sum(acc);
-    if (lane == 0) partial[q] = acc / static_cast<float>(C);
-    cumsum_exp_neg(v.aux, v.t, C, lane);
-    const float g = 1.0f / (static_cast<float>(C) * static_cast<float>(Q));
-    for (int j = lane; j < C; j += RR_WAVE) {
-      const float d = g * (expf(v.ss[j]) * v.t[j]) - g;
-      dscore[static_cast<int64_t>(off + v.perm[j]) * dstride] = d;
+    const ListMleTerm term(v, C, lane);
+    if (bwd != 1) {
+      const float acc = term.forward();
+      if (lane == 0) partial[q] = acc / static_cast<float>(C);      // torch.mean, loss.py:94
+    }
+    if (bwd != 0) {
+      const float g = (gloss ? gloss[0] : 1.0f) / (static_cast<float>(C) * static_cast<float>(Q));
+      term.gradient(g, [&](int i, float d) { dscore[static_cast<int64_t>(off + i) * dstride] = d; });
     }
   }
-  finish_last(partial, Q, scale, loss, counter, lane);
+  if (bwd == 2) finish_step(partial, Q, scale, loss, counter, lane);
 }
 
 // ---------------------------------------------------------------- ListNet
@@ -143,48 +70,30 @@ __global__ void __launch_bounds__(RR_WAVE) listnet_kernel(const float* __restric
                                                           float inv_total, float* __restrict__ dscore,
                                                           int64_t dstride, float* __restrict__ loss = nullptr,
                                                           unsigned int* __restrict__ counter = nullptr) {
-  // bwd: 0 = forward (partial), 1 = backward (dscore), 2 = both in one pass + the last-arriver reduction (step entry point:
-  // gloss == nullptr means an upstream gradient of one)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
   if (C <= 0) {
     if (bwd != 1 && lane == 0) partial[q] = 0.f;
-    if (bwd == 2) finish_last(partial, gridDim.x, inv_total, loss, counter, lane);
-    return;
-  }
-  float* s = sm;
-  float* t = sm + L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
-  float ms, zs, mt, zt;
-  softmax_stats(s, C, lane, &ms, &zs);
-  softmax_stats(t, C, lane, &mt, &zt);
-  if (bwd != 1) {
-    float acc = 0.f;
+  } else {
+    float* s = sm;
+    float* t = sm + L;
     for (int i = lane; i < C; i += RR_WAVE) {
-      const float pred = logf(expf(s[i] - ms) / zs);                // torch.log(F.softmax(item)), loss.py:339
-      const float targ = expf(t[i] - mt) / zt;                      // loss.py:341
-      acc += -targ * pred;                                          // loss.py:343
+      s[i] = score[static_cast<int64_t>(off + i) * sstride];
+      t[i] = targets[off + i];
     }
-    acc = rr_wave_sum(acc);
-    if (lane == 0) partial[q] = acc;
-  }
-  if (bwd != 0) {
-    float tsum = 0.f;
-    for (int i = lane; i < C; i += RR_WAVE) tsum += expf(t[i] - mt) / zt;
-    tsum = rr_wave_sum(tsum);
-    const float g = (gloss ? gloss[0] : 1.0f) * inv_total;
-    for (int i = lane; i < C; i += RR_WAVE) {
-      const float p = expf(s[i] - ms) / zs;
-      const float targ = expf(t[i] - mt) / zt;
-      dscore[static_cast<int64_t>(off + i) * dstride] = g * (p * tsum - targ);
+    wave_sync();
+    const ListNetTerm term(s, t, C, lane);
+    if (bwd != 1) {
+      const float acc = term.forward();
+      if (lane == 0) partial[q] = acc;                              // ONE mean over all candidates (loss.py:347): inv_total
+    }
+    if (bwd != 0) {
+      const float g = (gloss ? gloss[0] : 1.0f) * inv_total;
+      term.gradient(g, [&](int i, float d) { dscore[static_cast<int64_t>(off + i) * dstride] = d; });
     }
   }
-  if (bwd == 2) finish_last(partial, gridDim.x, inv_total, loss, counter, lane);
+  if (bwd == 2) finish_step(partial, gridDim.x, inv_total, loss, counter, lane);
 }
 
 // ---------------------------------------------------------------- evidential UC-Listwise
@@ -196,63 +105,35 @@ __global__ void __launch_bounds__(RR_WAVE) evidential_kernel(const float* __rest
                                                              float* __restrict__ dvar, int64_t dstride,
                                                              float* __restrict__ loss = nullptr,
                                                              unsigned int* __restrict__ counter = nullptr) {
-  // bwd: 0 = forward, 1 = backward, 2 = both + the last-arriver reduction (see listnet_kernel)
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
   if (C <= 0) {
     if (bwd != 1 && lane == 0) partial[q] = 0.f;
-    if (bwd == 2) finish_last(partial, gridDim.x, 1.0f / static_cast<float>(Q), loss, counter, lane);
-    return;
-  }
-  float* s = sm;
-  float* t = sm + L;
-  float* vv = sm + 2 * L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = mu[static_cast<int64_t>(off + i) * stride];
-    vv[i] = var[static_cast<int64_t>(off + i) * stride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
-  float ms, zs, mt, zt;
-  softmax_stats(s, C, lane, &ms, &zs);
-  softmax_stats(t, C, lane, &mt, &zt);
-  const float two_pi = 2.0f * 3.141592653f;                         // loss.py:543 (truncated pi)
-  if (bwd != 1) {
-    float acc = 0.f;
+  } else {
+    float* s = sm;
+    float* t = sm + L;
+    float* vv = sm + 2 * L;
     for (int i = lane; i < C; i += RR_WAVE) {
-      const float lp = logf(expf(s[i] - ms) / zs);
-      const float lt = logf(expf(t[i] - mt) / zt);
-      const float d = lt - lp;
-      const float unc = 0.5f * (d * d) / vv[i] + 0.5f * logf(two_pi * vv[i]);   // loss.py:541-543
-      const float pen = fabsf(s[i] - t[i]);                                       // loss.py:545
-      acc += -lt + unc + pen;                                                      // loss.py:549
+      s[i] = mu[static_cast<int64_t>(off + i) * stride];
+      vv[i] = var[static_cast<int64_t>(off + i) * stride];
+      t[i] = targets[off + i];
     }
-    acc = rr_wave_sum(acc);
-    if (lane == 0) partial[q] = acc / static_cast<float>(C);
-  }
-  if (bwd != 0) {
-    float csum = 0.f;
-    for (int i = lane; i < C; i += RR_WAVE) {
-      const float lp = logf(expf(s[i] - ms) / zs);
-      const float lt = logf(expf(t[i] - mt) / zt);
-      csum += -(lt - lp) / vv[i];
+    wave_sync();
+    const UcListwiseTerm term(s, vv, t, C, lane);
+    if (bwd != 1) {
+      const float acc = term.forward();
+      if (lane == 0) partial[q] = acc / static_cast<float>(C);
     }
-    csum = rr_wave_sum(csum);
-    const float g = (gloss ? gloss[0] : 1.0f) / (static_cast<float>(C) * static_cast<float>(Q));
-    for (int i = lane; i < C; i += RR_WAVE) {
-      const float p = expf(s[i] - ms) / zs;
-      const float lp = logf(p);
-      const float lt = logf(expf(t[i] - mt) / zt);
-      const float d = lt - lp;
-      const float c = -d / vv[i];
-      const float diff = s[i] - t[i];
-      const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-      dmu[static_cast<int64_t>(off + i) * dstride] = g * (c - p * csum + sgn);
-      dvar[static_cast<int64_t>(off + i) * dstride] = g * (-0.5f * d * d / (vv[i] * vv[i]) + 0.5f / vv[i]);
+    if (bwd != 0) {
+      const float g = (gloss ? gloss[0] : 1.0f) / (static_cast<float>(C) * static_cast<float>(Q));
+      term.gradient(g, [&](int i, float gm, float gv) {
+        dmu[static_cast<int64_t>(off + i) * dstride] = gm;
+        dvar[static_cast<int64_t>(off + i) * dstride] = gv;
+      });
     }
   }
-  if (bwd == 2) finish_last(partial, gridDim.x, 1.0f / static_cast<float>(Q), loss, counter, lane);
+  if (bwd == 2) finish_step(partial, gridDim.x, 1.0f / static_cast<float>(Q), loss, counter, lane);
 }
 
 // ---------------------------------------------------------------- RankNet
@@ -373,21 +254,18 @@ __global__ void __launch_bounds__(256) reduce_pairs_kernel(const float* __restri
   if (threadIdx.x == 0) out[0] = red[0];
 }
 
-// ---------------------------------------------------------------- pointwise losses
+// ---------------------------------------------------------------- pointwise losses (rows: point_row, loss_list.h)
 __global__ void __launch_bounds__(256) pointwise_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ var,
                                                             int64_t stride, const float* __restrict__ targets,
                                                             int64_t n, int gauss, float* __restrict__ partial) {
   __shared__ float red[256];
-  const float half_log_2pi = 0.5f * logf(2.0f * 3.14159274101257324f);   // float32(np.pi), loss.py:152,159
   float acc = 0.f;
   const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    const float d = mean[i * stride] - targets[i];
     if (gauss) {
-      const float v = var[i * stride];
-      acc += half_log_2pi + 0.5f * logf(v) + (d * d) / (2.0f * v);
+      acc += point_row<true>(mean[i * stride], targets[i], var[i * stride], 0.f).value;
     } else {
-      acc += d * d;
+      acc += point_row<false>(mean[i * stride], targets[i], 0.f, 0.f).value;
     }
   }
   red[threadIdx.x] = acc;
@@ -407,24 +285,17 @@ __global__ void __launch_bounds__(256) pointwise_bwd_kernel(const float* __restr
   const float g = gloss[0] / static_cast<float>(n);
   const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    const float d = mean[i * stride] - targets[i];
     if (gauss) {
-      const float v = var[i * stride];
-      dmean[i * dstride] = g * d / v;
-      dvar[i * dstride] = g * (0.5f / v - (d * d) / (2.0f * v * v));
+      const PointRow r = point_row<true>(mean[i * stride], targets[i], var[i * stride], g);
+      dmean[i * dstride] = r.dmean;
+      dvar[i * dstride] = r.dvar;
     } else {
-      dmean[i * dstride] = g * 2.0f * d;
+      dmean[i * dstride] = point_row<false>(mean[i * stride], targets[i], 0.f, g).dmean;
     }
   }
 }
 
 // ---------------------------------------------------------------- ranking metrics (eval.py:475-555)
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* __restrict__ score, int64_t sstride,
                                                                   const float* __restrict__ targets,
                                                                   const int32_t* __restrict__ seg_off, int L,
@@ -577,14 +448,11 @@ __global__ void __launch_bounds__(RR_WAVE) lce_bwd_kernel(const float* __restric
   float* cs = sm + n;
   for (int i = lane; i < n; i += RR_WAVE) fd[i] = y[i];
   wave_sync();
-  cumsum_exp_neg(fd, cs, n, lane);
-  for (int i = lane; i < n; i += RR_WAVE) gx[i] = gy[i] * (expf(x[i]) * cs[i]);      // loss.py:59
+  lce_backward(x, fd, cs, n, lane, [&](int i, float w) { gx[i] = gy[i] * w; });
 }
 
-// ---------------------------------------------------------------- listwise variants (train/loss.py:102-141, 187-314,
-// 355-399, 440-474): MLEDisLoss, Listnet_For_Gauss, Listnetlognorm, Listnet_For_evidential, Listnet_with_uq, Dirichlet_uq.
-// One wavefront per query like the kernels above; the C x C pair sums of the first three are factorised into per-element
-// terms, so a query costs O(C) - except MLEDisLoss's backward and the target ranking, O(C^2 / 64).
+// ---------------------------------------------------------------- listwise variants: MLEDisLoss, Listnet_For_Gauss,
+// Listnetlognorm, Listnet_For_evidential, Listnet_with_uq, Dirichlet_uq (their terms: loss_list.h)
 enum LossVariant : int { kMleDis = 0, kListnetGauss = 1, kListnetLognorm = 2, kListnetEvid = 3, kListnetUq = 4, kDirichletUq = 5 };
 
 struct VarIn {            // up to three per-candidate inputs, each read at x[k][row * st[k]]
@@ -598,7 +466,7 @@ struct VarOut {           // their gradients, written at d[k][row * st]
 };
 
 constexpr int variant_inputs(int V) { return V == kListnetEvid ? 3 : (V == kListnetUq || V == kDirichletUq) ? 1 : 2; }
-// staged floats per candidate: x0, t, x1, x2 (ListNet-evidential), perm + scan (MLEDis)
+// staged floats per candidate: x0, t, x1, x2 (ListNet-evidential) or perm (MLEDis), scan (MLEDis)
 constexpr int variant_lds(int V) { return V == kMleDis ? 5 : V == kListnetEvid ? 4 : (V == kListnetUq || V == kDirichletUq) ? 2 : 3; }
 
 template <int V>
@@ -629,167 +497,25 @@ __global__ void __launch_bounds__(RR_WAVE) listwise_variant_kernel(VarIn in, con
   wave_sync();
   const float invC = 1.0f / static_cast<float>(C);
   const float g = bwd ? gloss[0] / (static_cast<float>(C) * static_cast<float>(Q)) : 0.f;
-  auto put = [&](int k, int i, float val) { out.d[k][static_cast<int64_t>(off + i) * out.st] = val; };
-
-  if constexpr (V == kMleDis) {
-    // sorted by target (descending, stable); a_j = s_j + v_j / 2, F_j = log sum_{i>=j} exp(a_i);
-    // L_q = mean_j log sum_{i>=j} exp(s_i - s_j + (v_i + v_j) / 2) = mean_j (F_j - s_j + v_j / 2)
-    ListView lv;
-    lv.s = x0;
-    lv.t = t;
-    lv.perm = reinterpret_cast<int32_t*>(x2);
-    lv.ss = sm + 4 * L;                                             // sorted scores: scratch, overwritten by F below
-    lv.aux = nullptr;
-    rank_sort(lv, C, lane);
-    float* sa = t;                                                  // targets are not read again: sorted a in their place
-    float* F = sm + 4 * L;
-    for (int r = lane; r < C; r += RR_WAVE) {
-      const int p = lv.perm[r];
-      sa[r] = x0[p] + 0.5f * x1[p];
-    }
-    wave_sync();
-    const float m = list_max(sa, C, lane);
-    logcumsumexp_rev(sa, F, C, lane, m);
+  auto run = [&](const auto& term) {
     if (!bwd) {
-      float acc = 0.f;
-      for (int r = lane; r < C; r += RR_WAVE) {
-        const int p = lv.perm[r];
-        acc += F[r] + (0.5f * x1[p] - x0[p]);
-      }
-      acc = rr_wave_sum(acc);
-      if (lane == 0) partial[q] = acc * invC;
+      const auto acc = term.forward();
+      if (lane != 0) return;
+      if constexpr (V == kListnetUq || V == kDirichletUq) partial[q] = acc.acc * invC + coef * (acc.pen * invC);
+      else if constexpr (V == kListnetEvid) partial[q] = -(acc * invC);
+      else partial[q] = acc * invC;
     } else {
-      // d L_q / d a_k = (1/C) sum_{j<=k} exp(a_k - F_j): every term is <= 1, so the pair form cannot overflow
-      for (int k = lane; k < C; k += RR_WAVE) {
-        const float ak = sa[k];
-        float G = 0.f;
-        for (int j = 0; j <= k; ++j) G += expf(ak - F[j]);
-        const int p = lv.perm[k];
-        put(0, p, g * (G - 1.0f));
-        put(1, p, g * 0.5f * (G + 1.0f));
-      }
+      term.gradient(g, [&](int i, auto... gs) {
+        int k = 0;
+        ((out.d[k++][static_cast<int64_t>(off + i) * out.st] = gs), ...);
+      });
     }
-  } else {
-    float mt, zt;                                                   // softmax of the query's targets
-    softmax_stats(t, C, lane, &mt, &zt);
-    auto smt = [&](int i) { return expf(t[i] - mt) / zt; };
-    float tsum = 0.f;
-    if (bwd) {
-      for (int i = lane; i < C; i += RR_WAVE) tsum += smt(i);
-      tsum = rr_wave_sum(tsum);
-    }
-    if constexpr (V == kListnetGauss) {
-      // log sum_j exp(s_j - s_i + (v_i + v_j) / 2) = LSE_j(s_j + v_j / 2) - s_i + v_i / 2
-      float ma = -INFINITY;
-      for (int i = lane; i < C; i += RR_WAVE) ma = fmaxf(ma, x0[i] + 0.5f * x1[i]);
-      ma = rr_wave_max(ma);
-      float za = 0.f;
-      for (int i = lane; i < C; i += RR_WAVE) za += expf(x0[i] + 0.5f * x1[i] - ma);
-      za = rr_wave_sum(za);
-      const float lse = ma + logf(za);
-      if (!bwd) {
-        float acc = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * (lse + (0.5f * x1[i] - x0[i]));
-        acc = rr_wave_sum(acc);
-        if (lane == 0) partial[q] = acc * invC;
-      } else {
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float pk = expf(x0[k] + 0.5f * x1[k] - lse), tk = smt(k);
-          put(0, k, g * (tsum * pk - tk));
-          put(1, k, g * 0.5f * (tsum * pk + tk));
-        }
-      }
-    } else if constexpr (V == kListnetLognorm) {
-      // log sum_j (s_j / s_i) exp((v_i + v_j) / 2) = log(W / s_i) + (v_i + mv) / 2, W = sum_j s_j exp((v_j - mv) / 2):
-      // the sign of W / s_i is the sign of the reference's sum, so log() of a negative one is NaN here as there
-      const float mv = list_max(x1, C, lane);
-      float W = 0.f;
-      for (int i = lane; i < C; i += RR_WAVE) W += x0[i] * expf(0.5f * (x1[i] - mv));
-      W = rr_wave_sum(W);
-      if (!bwd) {
-        float acc = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * (logf(W / x0[i]) + 0.5f * (x1[i] + mv));
-        acc = rr_wave_sum(acc);
-        if (lane == 0) partial[q] = acc * invC;
-      } else {
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float ek = expf(0.5f * (x1[k] - mv)), tk = smt(k);
-          put(0, k, g * (tsum * ek / W - tk / x0[k]));
-          put(1, k, g * 0.5f * (tsum * x0[k] * ek / W + tk));
-        }
-      }
-    } else if constexpr (V == kListnetEvid) {
-      // L_q = -mean_i softmax(t)_i * log_softmax(s)_i * (2 v_i + alpha_i)
-      float ms, zs;
-      softmax_stats(x0, C, lane, &ms, &zs);
-      const float lz = logf(zs);
-      if (!bwd) {
-        float acc = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * ((x0[i] - ms) - lz) * (2.0f * x1[i] + x2[i]);
-        acc = rr_wave_sum(acc);
-        if (lane == 0) partial[q] = -(acc * invC);
-      } else {
-        float wsum = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) wsum += smt(i) * (2.0f * x1[i] + x2[i]);
-        wsum = rr_wave_sum(wsum);
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float tk = smt(k), lsk = (x0[k] - ms) - lz, pk = expf(x0[k] - ms) / zs;
-          put(0, k, -g * (tk * (2.0f * x1[k] + x2[k]) - pk * wsum));
-          put(1, k, -g * 2.0f * tk * lsk);
-          put(2, k, -g * tk * lsk);
-        }
-      }
-    } else {
-      // kListnetUq: p = s / sum(s); L_q = KL(softmax(t) || p) / C + coef * mean_i |log(softmax(t)_i / p_i) (s_i - 1)|
-      // kDirichletUq: p = a / S, S = sum(a); L_q = mean_i (p_i - sm_i)^2 + p_i (1 - p_i) / (S + 1) + coef * |log(sm_i / p_i) (a_i - 1)|
-      float S = 0.f;
-      for (int i = lane; i < C; i += RR_WAVE) S += x0[i];
-      S = rr_wave_sum(S);
-      if (!bwd) {
-        float acc = 0.f, pen = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) {
-          const float p = x0[i] / S, tk = smt(i);
-          pen += fabsf(logf(tk / p) * (x0[i] - 1.0f));
-          if constexpr (V == kListnetUq) {
-            acc += (tk > 0.f ? tk * logf(tk) : 0.f) - tk * logf(p);        // KLDivLoss: xlogy(t, t) - t * input
-          } else {
-            const float e = p - tk;
-            acc += e * e + p * (1.0f - p) / (S + 1.0f);
-          }
-        }
-        acc = rr_wave_sum(acc);
-        pen = rr_wave_sum(pen);
-        if (lane == 0) partial[q] = acc * invC + coef * (pen * invC);
-      } else if constexpr (V == kListnetUq) {
-        float U = 0.f;                                              // sum_i sgn(r_i) (s_i - 1)
-        for (int i = lane; i < C; i += RR_WAVE) {
-          const float p = x0[i] / S;
-          U += sgnf(logf(smt(i) / p) * (x0[i] - 1.0f)) * (x0[i] - 1.0f);
-        }
-        U = rr_wave_sum(U);
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float sk = x0[k], p = sk / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (sk - 1.0f));
-          put(0, k, g * ((tsum / S - tk / sk) + coef * (sg * c - sg * (sk - 1.0f) / sk + U / S)));
-        }
-      } else {
-        float up = 0.f, w = 0.f;                                    // sum_i u_i p_i and d L / d S at fixed p
-        const float S1 = S + 1.0f;
-        for (int i = lane; i < C; i += RR_WAVE) {
-          const float ai = x0[i], p = ai / S, tk = smt(i), sg = sgnf(logf(tk / p) * (ai - 1.0f));
-          const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ai - 1.0f) / p;
-          up += u * p;
-          w -= p * (1.0f - p) / (S1 * S1);
-        }
-        up = rr_wave_sum(up);
-        w = rr_wave_sum(w);
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float ak = x0[k], p = ak / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (ak - 1.0f));
-          const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ak - 1.0f) / p;
-          put(0, k, g * ((u - up) / S + w + coef * sg * c));
-        }
-      }
-    }
-  }
+  };
+  if constexpr (V == kMleDis) run(MleDisTerm<false>(x0, x1, t, reinterpret_cast<int32_t*>(x2), sm + 4 * L, C, lane));
+  else if constexpr (V == kListnetGauss) run(ListNetGaussTerm(x0, x1, t, C, lane));
+  else if constexpr (V == kListnetLognorm) run(ListNetLognormTerm(x0, x1, t, C, lane));
+  else if constexpr (V == kListnetEvid) run(ListNetEvidTerm(x0, x1, x2, t, C, lane));
+  else run(UqTerm<V == kDirichletUq>(x0, t, coef, C, lane));
 }
 
 // ---------------------------------------------------------------- evidential_loss_new (train/loss.py:402-437)
@@ -1083,8 +809,8 @@ int rr_listmle_fwd_f32(const float* score, int64_t score_stride, const float* ta
   const int L = max_len > 0 ? max_len : 1;
   const size_t lds = 5u * L * sizeof(float);
   if (Q > 0) {
-    if (set_lds(listmle_fwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    listmle_fwd_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, partial);
+    if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
+    listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 0, partial, nullptr, nullptr, 1);
   }
   reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, Q > 0 ? 1.0f / static_cast<float>(Q) : 0.f, loss);
   return rr_launch_status();
@@ -1099,9 +825,8 @@ int rr_listmle_bwd_f32(const float* score, int64_t score_stride, const float* ta
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int L = max_len > 0 ? max_len : 1;
   const size_t lds = 5u * L * sizeof(float);
-  if (set_lds(listmle_bwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listmle_bwd_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, gloss, dscore,
-                                             dscore_stride);
+  if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
+  listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 1, nullptr, gloss, dscore, dscore_stride);
   return rr_launch_status();
 }
 
@@ -1118,9 +843,9 @@ int rr_listmle_step_f32(const float* score, int64_t score_stride, const float* t
   }
   const int L = max_len > 0 ? max_len : 1;
   const size_t lds = 5u * L * sizeof(float);
-  if (set_lds(listmle_step_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listmle_step_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, partial, dscore, dscore_stride,
-                                              1.0f / static_cast<float>(Q), loss, counter);
+  if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
+  listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 2, partial, nullptr, dscore, dscore_stride,
+                                         1.0f / static_cast<float>(Q), loss, counter);
   return rr_launch_status();
 }
 

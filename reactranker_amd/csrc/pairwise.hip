@@ -10,36 +10,9 @@
 // runs give the same bits.  The per-entry arithmetic is double: BetaNet cancels lgamma values near 360 (alpha0 = 100), and
 // float32 there sits 0.5e-5 .. 2.3e-5 from the exact value.  Per-query partials are doubles, summed by one block in a
 // fixed order.
-#include "rr_common.h"
+#include "wave_util.h"
 
 namespace {
-
-constexpr int kMaxLen = 8192;
-
-__device__ inline void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-template <typename Kern>
-int set_lds(Kern k, size_t bytes) {
-  if (bytes > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(bytes)) != hipSuccess)
-      return RR_ERR_LAUNCH;
-  }
-  return RR_OK;
-}
-
-inline bool list_args_ok(const void* a, const void* t, const int32_t* seg, int Q, int max_len) {
-  return a && t && seg && Q >= 0 && max_len >= 0;
-}
 
 __device__ inline double sigmoid_d(double x) { return x >= 0.0 ? 1.0 / (1.0 + exp(-x)) : exp(x) / (1.0 + exp(x)); }
 

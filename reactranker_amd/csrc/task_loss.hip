@@ -2,14 +2,15 @@
 //
 // The trainer's composite task types (train/train_listwise.py:196-285 of the reference) sum a per-list term and a
 // per-candidate term over column slices of the head's [M, n_cols] output.  Every row of that output belongs to exactly one
-// query, so the query's wavefront - which already holds the list in LDS for the list term (loss_list.h) - also evaluates
-// the pointwise term of its own candidates and writes every column of its rows of d loss / d out, for an upstream gradient
-// of one.  The two terms keep separate per-query partials (partial[0:Q] list, partial[Q:2Q] point) and separate
-// normalisers (n_queries, n_cands: the counts of this process' step, or of the whole data-parallel step); the workgroup
-// that draws the last ticket sums both rows in a fixed order, so the loss has the same bits on every run.
+// query, so the query's wavefront - which already holds the list in LDS for the list term - also evaluates the pointwise
+// term of its own candidates and writes every column of its rows of d loss / d out, for an upstream gradient of one.  The
+// two terms keep separate per-query partials (partial[0:Q] list, partial[Q:2Q] point) and separate normalisers (n_queries,
+// n_cands: the counts of this process' step, or of the whole data-parallel step); the workgroup that draws the last ticket
+// sums both rows in a fixed order, so the loss has the same bits on every run.
 //
-// List terms restate the per-list arithmetic of loss.hip (listmle_step_kernel, listnet_kernel, listwise_variant_kernel);
-// the point terms restate pointwise_fwd_kernel / pointwise_bwd_kernel.
+// The kernel is a shell over loss_list.h: it builds the SAME list term the standalone kernels of loss.hip build, and its
+// rows go through the same point_row; what is its own are the normalisers, the exp() on column 1 for MLEDis, and the emit
+// that adds the point term's gradient and writes whole rows.
 #include "loss_list.h"
 
 namespace {
@@ -37,22 +38,6 @@ struct TaskArgs {
   unsigned int* counter;
 };
 
-// fixed-order sum of n floats on one wave: reduce_scale_kernel's order (256 strided accumulators, then its halving tree),
-// lane l playing threads l, l + 64, l + 128, l + 192; the result is valid in lane 0
-__device__ inline float fixed_sum(const float* p, int n, int lane) {
-  float a[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    float acc = 0.f;
-    for (int i = lane + 64 * u; i < n; i += 256) acc += p[i];
-    a[u] = acc;
-  }
-  float r = (a[0] + a[2]) + (a[1] + a[3]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) r += __shfl_down(r, o, RR_WAVE);
-  return r;
-}
-
 template <int LT, int PT>
 __global__ void __launch_bounds__(RR_WAVE) task_step_kernel(TaskArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -63,7 +48,7 @@ __global__ void __launch_bounds__(RR_WAVE) task_step_kernel(TaskArgs a) {
 
   if (C > 0) {
     float* x0 = sm;               // column 0
-    float* t = sm + L;            // targets: kept intact until the rows are written (the point term reads them)
+    float* t = sm + L;            // targets: no term overwrites them (the point term reads them as the rows are written)
     if constexpr (LT != RR_LIST_NONE) {
       for (int i = lane; i < C; i += RR_WAVE) {
         x0[i] = a.out[static_cast<int64_t>(off + i) * a.ld_out];
@@ -71,161 +56,59 @@ __global__ void __launch_bounds__(RR_WAVE) task_step_kernel(TaskArgs a) {
       }
       wave_sync();
     }
-    const float half_log_2pi = 0.5f * logf(2.0f * 3.14159274101257324f);   // float32(np.pi), loss.py:152,159
     // Writes row i of the query: column 0 gets the list term's gradient gl0 plus the point term's, column 1 gl1 plus the
     // point term's, every further column zero; adds the row's point term to point_acc.  Called once per row.
-    auto finish_row = [&](int i, float gl0, float gl1) {
+    auto finish_row = [&](int i, float gl0, float gl1 = 0.f) {
       const int64_t r = off + i;
-      float gp0 = 0.f, gp1 = 0.f;
+      PointRow p{0.f, 0.f, 0.f};
       if constexpr (PT != RR_POINT_NONE) {
         const float mean = LT != RR_LIST_NONE ? x0[i] : a.out[r * a.ld_out];
         const float targ = LT != RR_LIST_NONE ? t[i] : a.targets[r];
-        const float d = mean - targ;
         if constexpr (PT == RR_POINT_GAUSS) {
-          const float v = a.out[r * a.ld_out + 1];                  // the raw column 1 (GaussDisLoss takes its log)
-          point_acc += half_log_2pi + 0.5f * logf(v) + (d * d) / (2.0f * v);
-          gp0 = a.inv_cands * d / v;
-          gp1 = a.inv_cands * (0.5f / v - (d * d) / (2.0f * v * v));
+          p = point_row<true>(mean, targ, a.out[r * a.ld_out + 1], a.inv_cands);   // the raw column 1 (GaussDisLoss takes its log)
         } else {
-          point_acc += d * d;
-          gp0 = a.inv_cands * 2.0f * d;
+          p = point_row<false>(mean, targ, 0.f, a.inv_cands);
         }
+        point_acc += p.value;
       }
       float* row = a.dout + r * a.ld_dout;
-      row[0] = gl0 + gp0;
-      if (a.n_cols > 1) row[1] = gl1 + gp1;
+      row[0] = gl0 + p.dmean;
+      if (a.n_cols > 1) row[1] = gl1 + p.dvar;
       for (int c = 2; c < a.n_cols; ++c) row[c] = 0.f;
     };
     const float invC = 1.0f / static_cast<float>(C);
     const float g = a.inv_queries * invC;                           // d / d (a per-query mean's element), mean over queries
 
     if constexpr (LT == RR_LIST_NONE) {
-      for (int i = lane; i < C; i += RR_WAVE) finish_row(i, 0.f, 0.f);
+      for (int i = lane; i < C; i += RR_WAVE) finish_row(i, 0.f);
     } else if constexpr (LT == RR_LIST_MLE) {
-      ListView v = carve(sm, L);
-      rank_sort(v, C, lane);
-      const float m = list_max(v.ss, C, lane);
-      logcumsumexp_rev(v.ss, v.aux, C, lane, m);
-      float acc = 0.f;
-      for (int i = lane; i < C; i += RR_WAVE) acc += v.aux[i] - v.ss[i];
-      list_part = rr_wave_sum(acc) * invC;                          // torch.mean, loss.py:94
-      cumsum_exp_neg(v.aux, v.aux, C, lane);                        // in place (each lane reads fd[j] before it writes [j])
-      for (int j = lane; j < C; j += RR_WAVE) finish_row(v.perm[j], g * (expf(v.ss[j]) * v.aux[j]) - g, 0.f);
+      const ListMleTerm term(carve(sm, L), C, lane);
+      list_part = term.forward() * invC;                            // torch.mean, loss.py:94
+      term.gradient(g, finish_row);
+    } else if constexpr (LT == RR_LIST_LISTNET) {
+      const ListNetTerm term(x0, t, C, lane);
+      list_part = term.forward();                                   // ONE mean over all candidates (loss.py:347)
+      term.gradient(a.inv_cands, finish_row);
     } else if constexpr (LT == RR_LIST_MLEDIS) {
-      // listwise_variant_kernel<kMleDis> with variance = exp(column 1), the transform the trainer applies (:196-202)
+      // variance = exp(column 1), the transform the trainer applies (:196-202); d / d out[:, 1] carries exp'(out[:, 1]) =
+      // the staged variance
       float* x1 = sm + 2 * L;
-      int32_t* perm = reinterpret_cast<int32_t*>(sm + 3 * L);
-      float* F = sm + 4 * L;
       for (int i = lane; i < C; i += RR_WAVE) x1[i] = expf(a.out[static_cast<int64_t>(off + i) * a.ld_out + 1]);
-      ListView lv;
-      lv.s = x0;
-      lv.t = t;
-      lv.perm = perm;
-      lv.ss = F;                                                    // sorted scores: scratch, overwritten below
-      lv.aux = nullptr;
-      rank_sort(lv, C, lane);
-      for (int r = lane; r < C; r += RR_WAVE) {
-        const int p = perm[r];
-        F[r] = x0[p] + 0.5f * x1[p];                                // sorted a_j = s_j + v_j / 2
-      }
+      const MleDisTerm<true> term(x0, x1, t, reinterpret_cast<int32_t*>(sm + 3 * L), sm + 4 * L, C, lane);
+      list_part = term.forward() * invC;
+      term.gradient(g, [&](int p, float g0, float g1) { finish_row(p, g0, g1 * x1[p]); });
+    } else if constexpr (LT == RR_LIST_LISTNET_GAUSS) {
+      float* x1 = sm + 2 * L;
+      for (int i = lane; i < C; i += RR_WAVE) x1[i] = a.out[static_cast<int64_t>(off + i) * a.ld_out + 1];
       wave_sync();
-      const float m = list_max(F, C, lane);
-      logcumsumexp_rev(F, F, C, lane, m);                           // in place: F_j = log sum_{i>=j} exp(a_i)
-      float acc = 0.f;
-      for (int r = lane; r < C; r += RR_WAVE) {
-        const int p = perm[r];
-        acc += F[r] + (0.5f * x1[p] - x0[p]);
-      }
-      list_part = rr_wave_sum(acc) * invC;
-      for (int k = lane; k < C; k += RR_WAVE) {
-        const int p = perm[k];
-        const float ak = x0[p] + 0.5f * x1[p];
-        float G = 0.f;
-        for (int j = 0; j <= k; ++j) G += expf(ak - F[j]);
-        // d / d out[:, 1] carries exp'(out[:, 1]) = the staged variance
-        finish_row(p, g * (G - 1.0f), (g * 0.5f * (G + 1.0f)) * x1[p]);
-      }
+      const ListNetGaussTerm term(x0, x1, t, C, lane);
+      list_part = term.forward() * invC;
+      term.gradient(g, finish_row);
     } else {
-      float mt, zt;                                                 // softmax of the query's targets
-      softmax_stats(t, C, lane, &mt, &zt);
-      auto smt = [&](int i) { return expf(t[i] - mt) / zt; };
-      float tsum = 0.f;
-      for (int i = lane; i < C; i += RR_WAVE) tsum += smt(i);
-      tsum = rr_wave_sum(tsum);
-      if constexpr (LT == RR_LIST_LISTNET) {
-        float ms, zs;
-        softmax_stats(x0, C, lane, &ms, &zs);
-        float acc = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) acc += -smt(i) * logf(expf(x0[i] - ms) / zs);   // loss.py:339-343
-        list_part = rr_wave_sum(acc);                               // ONE mean over all candidates (loss.py:347)
-        for (int i = lane; i < C; i += RR_WAVE) finish_row(i, a.inv_cands * ((expf(x0[i] - ms) / zs) * tsum - smt(i)), 0.f);
-      } else if constexpr (LT == RR_LIST_LISTNET_GAUSS) {
-        float* x1 = sm + 2 * L;
-        for (int i = lane; i < C; i += RR_WAVE) x1[i] = a.out[static_cast<int64_t>(off + i) * a.ld_out + 1];
-        wave_sync();
-        float ma = -INFINITY;
-        for (int i = lane; i < C; i += RR_WAVE) ma = fmaxf(ma, x0[i] + 0.5f * x1[i]);
-        ma = rr_wave_max(ma);
-        float za = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) za += expf(x0[i] + 0.5f * x1[i] - ma);
-        za = rr_wave_sum(za);
-        const float lse = ma + logf(za);
-        float acc = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) acc += smt(i) * (lse + (0.5f * x1[i] - x0[i]));
-        list_part = rr_wave_sum(acc) * invC;
-        for (int k = lane; k < C; k += RR_WAVE) {
-          const float pk = expf(x0[k] + 0.5f * x1[k] - lse), tk = smt(k);
-          finish_row(k, g * (tsum * pk - tk), g * 0.5f * (tsum * pk + tk));
-        }
-      } else {
-        // RR_LIST_LISTNET_UQ / RR_LIST_DIRICHLET_UQ: see listwise_variant_kernel
-        const float coef = a.coef;
-        float S = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) S += x0[i];
-        S = rr_wave_sum(S);
-        float acc = 0.f, pen = 0.f;
-        for (int i = lane; i < C; i += RR_WAVE) {
-          const float p = x0[i] / S, tk = smt(i);
-          pen += fabsf(logf(tk / p) * (x0[i] - 1.0f));
-          if constexpr (LT == RR_LIST_LISTNET_UQ) {
-            acc += (tk > 0.f ? tk * logf(tk) : 0.f) - tk * logf(p);          // KLDivLoss: xlogy(t, t) - t * input
-          } else {
-            const float e = p - tk;
-            acc += e * e + p * (1.0f - p) / (S + 1.0f);
-          }
-        }
-        acc = rr_wave_sum(acc);
-        pen = rr_wave_sum(pen);
-        list_part = acc * invC + coef * (pen * invC);
-        if constexpr (LT == RR_LIST_LISTNET_UQ) {
-          float U = 0.f;                                            // sum_i sgn(r_i) (s_i - 1)
-          for (int i = lane; i < C; i += RR_WAVE) {
-            const float p = x0[i] / S;
-            U += sgnf(logf(smt(i) / p) * (x0[i] - 1.0f)) * (x0[i] - 1.0f);
-          }
-          U = rr_wave_sum(U);
-          for (int k = lane; k < C; k += RR_WAVE) {
-            const float sk = x0[k], p = sk / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (sk - 1.0f));
-            finish_row(k, g * ((tsum / S - tk / sk) + coef * (sg * c - sg * (sk - 1.0f) / sk + U / S)), 0.f);
-          }
-        } else {
-          float up = 0.f, w = 0.f;                                  // sum_i u_i p_i and d L / d S at fixed p
-          const float S1 = S + 1.0f;
-          for (int i = lane; i < C; i += RR_WAVE) {
-            const float ai = x0[i], p = ai / S, tk = smt(i), sg = sgnf(logf(tk / p) * (ai - 1.0f));
-            const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ai - 1.0f) / p;
-            up += u * p;
-            w -= p * (1.0f - p) / (S1 * S1);
-          }
-          up = rr_wave_sum(up);
-          w = rr_wave_sum(w);
-          for (int k = lane; k < C; k += RR_WAVE) {
-            const float ak = x0[k], p = ak / S, tk = smt(k), c = logf(tk / p), sg = sgnf(c * (ak - 1.0f));
-            const float u = 2.0f * (p - tk) + (1.0f - 2.0f * p) / S1 - coef * sg * (ak - 1.0f) / p;
-            finish_row(k, g * ((u - up) / S + w + coef * sg * c), 0.f);
-          }
-        }
-      }
+      const UqTerm<LT == RR_LIST_DIRICHLET_UQ> term(x0, t, a.coef, C, lane);
+      const UqSums s = term.forward();
+      list_part = s.acc * invC + a.coef * (s.pen * invC);
+      term.gradient(g, finish_row);
     }
     if constexpr (PT != RR_POINT_NONE) point_acc = rr_wave_sum(point_acc);
   }
@@ -234,27 +117,16 @@ __global__ void __launch_bounds__(RR_WAVE) task_step_kernel(TaskArgs a) {
     a.partial[Q + q] = point_acc;
   }
 
-  // the last-arriving workgroup sums both rows of `partial` (finish_last of loss.hip: release fence, ticket, acquire fence,
-  // one wave, fixed tree).  The ticket is tested modulo Q, so a word that an earlier launch left at a multiple of Q still
-  // lets this launch finish; the finisher re-arms it with zero.
-  __threadfence();                                                  // release: this workgroup's partials
-  unsigned int ticket = 0u;
-  if (lane == 0) ticket = atomicAdd(a.counter, 1u);
-  ticket = __shfl(ticket, 0, RR_WAVE);
-  if (ticket % static_cast<unsigned int>(Q) != static_cast<unsigned int>(Q) - 1u) return;
-  __threadfence();                                                  // acquire: every other workgroup's partials
-  const float s_list = fixed_sum(a.partial, Q, lane);
-  const float s_point = fixed_sum(a.partial + Q, Q, lane);
-  if (lane == 0) {
+  float sum[2];
+  if (finish_last(a.partial, Q, a.counter, lane, sum)) {
     const float list_scale = LT == RR_LIST_LISTNET ? a.inv_cands : a.inv_queries;
-    const float t0 = LT != RR_LIST_NONE ? s_list * list_scale : 0.f;
-    const float t1 = PT != RR_POINT_NONE ? s_point * a.inv_cands : 0.f;
+    const float t0 = LT != RR_LIST_NONE ? sum[0] * list_scale : 0.f;
+    const float t1 = PT != RR_POINT_NONE ? sum[1] * a.inv_cands : 0.f;
     a.loss[0] = t0 + t1;
     if (a.terms) {
       a.terms[0] = t0;
       a.terms[1] = t1;
     }
-    *a.counter = 0u;
   }
 }
 

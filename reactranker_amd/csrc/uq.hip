@@ -10,24 +10,12 @@
 // rr_uq_calibration_f64: tie-averaged ranks and the descending-uncertainty positions come from binary searches over the
 // two stable ascending orders (torch.sort on the device), one row per thread; block partials go to the workspace and a
 // one-block second launch sums them in block order.
-#include "rr_common.h"
+#include "wave_util.h"
 
 namespace {
 
-constexpr int kMaxLen = 8192;
 constexpr int kCalBlock = RR_UQ_CAL_BLOCK;
 static_assert(kCalBlock % RR_WAVE == 0, "the calibration block is whole wavefronts");
-
-__device__ inline void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // (value, position) of the first maximum across the wave; position -1 = this lane saw no candidate
 __device__ inline void wave_first_max(float& v, int& i) {
@@ -37,16 +25,6 @@ __device__ inline void wave_first_max(float& v, int& i) {
     const int oi = __shfl_xor(i, off, 64);
     if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
   }
-}
-
-template <typename Kern>
-int set_lds(Kern k, size_t bytes) {
-  if (bytes > 65536) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(bytes)) != hipSuccess)
-      return RR_ERR_LAUNCH;
-  }
-  return RR_OK;
 }
 
 __global__ void __launch_bounds__(RR_WAVE) mc_stats_kernel(const float* __restrict__ samples, int64_t sstride, int T,

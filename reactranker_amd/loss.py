@@ -31,6 +31,19 @@ def _segments(scope: tuple, device_str: str):
     return t, int(off[-1]), (max(scope) if scope else 0)
 
 
+def _targets(targets, device) -> torch.Tensor:
+    """targets as a contiguous float32 vector on `device` (reference loss.py:85)"""
+    t = torch.as_tensor(targets, dtype=torch.float32)
+    if t.device != device:                              # (a same-device .to() still costs a dispatch on the step's host path)
+        t = t.to(device)
+    return t.reshape(-1).contiguous()
+
+
+def _call(name, *args):
+    """the library's entry point `name` on the current stream; a non-zero status raises"""
+    check(getattr(lib(), name)(*args, stream()), name)
+
+
 def _prep(score: torch.Tensor, scope, targets, gpu):
     if gpu is not None:
         torch.cuda.set_device(gpu)                      # reference loss.py:83
@@ -39,10 +52,7 @@ def _prep(score: torch.Tensor, scope, targets, gpu):
     seg, total, max_len = _segments(scope, str(score.device))
     if total != score.shape[0]:
         raise RuntimeError(f"sum(scope) = {total} but score has {score.shape[0]} rows")
-    t = torch.as_tensor(targets, dtype=torch.float32)
-    if t.device != score.device:
-        t = t.to(score.device)                          # reference loss.py:85
-    t = t.reshape(-1).contiguous()
+    t = _targets(targets, score.device)
     if t.numel() != total:
         raise RuntimeError("targets and score lengths differ")
     return scope, seg, total, max_len, t
@@ -114,108 +124,53 @@ def backward(loss: torch.Tensor) -> None:
         loss.backward()
 
 
-class _ListMLEFn(torch.autograd.Function):
+class _FusedListFn(torch.autograd.Function):
+    """rr_{kind}_{fwd,step,bwd}_f32 of the three losses with a one-launch step (FusedStep).  'listmle' and 'listnet' read one
+    strided column; 'evidential_ranking' reads the two columns of an [M, 2] tensor.  'listnet' also passes `total` (its ONE
+    mean over all candidates) and returns 0-d (torch.mean, reference loss.py:347); the other two return [1]."""
+
     @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len):
-        s = _vec(score.detach())
-        loss, part = _f1(s.device), torch.empty(max(Q, 1), dtype=torch.float32, device=s.device)
+    def _in(kind, x):
+        return [ptr(x[:, 0]), ptr(x[:, 1]), x.stride(0)] if kind == "evidential_ranking" else [ptr(x), x.stride(0)]
+
+    @staticmethod
+    def _out(kind, x):
+        """an empty gradient like x and its arguments"""
+        d = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+        return d, ([ptr(d[:, 0]), ptr(d[:, 1]), 2] if kind == "evidential_ranking" else [ptr(d), 1])
+
+    @staticmethod
+    def forward(ctx, kind, x, targets, seg, Q, max_len, total):
+        x = x.detach()
+        if kind != "evidential_ranking":
+            x = _vec(x)
+        elif x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 2 or x.stride(1) != 1:
+            x = x.float().reshape(-1, 2).contiguous()
+        loss, part = _f1(x.device), torch.empty(max(Q, 1), dtype=torch.float32, device=x.device)
+        args = _FusedListFn._in(kind, x) + [ptr(targets), ptr(seg), Q, max_len] + ([total] if kind == "listnet" else [])
         ctx.ds_unit = None
-        if FusedStep.enabled and ctx.needs_input_grad[0]:
-            ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            check(lib().rr_listmle_step_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, ptr(loss), ptr(part),
-                                            ptr(_counter(s.device)), ptr(ds), 1, stream()), "rr_listmle_step_f32")
-            ctx.ds_unit = ds
+        if FusedStep.enabled and ctx.needs_input_grad[1]:
+            d, outs = _FusedListFn._out(kind, x)
+            _call(f"rr_{kind}_step_f32", *args, ptr(loss), ptr(part), ptr(_counter(x.device)), *outs)
+            ctx.ds_unit = d
         else:
-            check(lib().rr_listmle_fwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, ptr(loss), ptr(part),
-                                           stream()), "rr_listmle_fwd_f32")
-        ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (Q, max_len)
-        return loss
+            _call(f"rr_{kind}_fwd_f32", *args, ptr(loss), ptr(part))
+        ctx.save_for_backward(x, targets, seg)
+        ctx.meta = (kind, args)
+        return loss.reshape(()) if kind == "listnet" else loss
 
     @staticmethod
     def backward(ctx, g):
         if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
-            ds, ctx.ds_unit = ctx.ds_unit, None
-            FusedStep.hits += 1
-            return ds, None, None, None, None
-        s, targets, seg = ctx.saved_tensors
-        Q, max_len = ctx.meta
-        g = g.reshape(-1).contiguous().float()
-        ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-        check(lib().rr_listmle_bwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, ptr(g), ptr(ds), 1,
-                                       stream()), "rr_listmle_bwd_f32")
-        return ds, None, None, None, None
-
-
-class _ListNetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len, total):
-        s = _vec(score.detach())
-        loss, part = _f1(s.device), torch.empty(max(Q, 1), dtype=torch.float32, device=s.device)
-        ctx.ds_unit = None
-        if FusedStep.enabled and ctx.needs_input_grad[0]:
-            ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            check(lib().rr_listnet_step_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, total, ptr(loss), ptr(part),
-                                            ptr(_counter(s.device)), ptr(ds), 1, stream()), "rr_listnet_step_f32")
-            ctx.ds_unit = ds
-        else:
-            check(lib().rr_listnet_fwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, total, ptr(loss),
-                                           ptr(part), stream()), "rr_listnet_fwd_f32")
-        ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (Q, max_len, total)
-        return loss.reshape(())                         # torch.mean -> 0-d (reference loss.py:347)
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.ds_unit is not None and _is_unit(g):
-            ds, ctx.ds_unit = ctx.ds_unit, None
-            FusedStep.hits += 1
-            return ds, None, None, None, None, None
-        s, targets, seg = ctx.saved_tensors
-        Q, max_len, total = ctx.meta
-        g = g.reshape(-1).contiguous().float()
-        ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-        check(lib().rr_listnet_bwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, total, ptr(g), ptr(ds),
-                                       1, stream()), "rr_listnet_bwd_f32")
-        return ds, None, None, None, None, None
-
-
-class _EvidentialFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, poss, targets, seg, Q, max_len):
-        p = poss.detach()
-        if p.dtype != torch.float32 or p.dim() != 2 or p.shape[1] != 2 or p.stride(1) != 1:
-            p = p.float().reshape(-1, 2).contiguous()
-        loss, part = _f1(p.device), torch.empty(max(Q, 1), dtype=torch.float32, device=p.device)
-        mu, var = p[:, 0], p[:, 1]
-        ctx.ds_unit = None
-        if FusedStep.enabled and ctx.needs_input_grad[0]:
-            d = torch.empty(p.shape[0], 2, dtype=torch.float32, device=p.device)
-            check(lib().rr_evidential_ranking_step_f32(ptr(mu), ptr(var), p.stride(0), ptr(targets), ptr(seg), Q, max_len,
-                                                       ptr(loss), ptr(part), ptr(_counter(p.device)), ptr(d[:, 0]), ptr(d[:, 1]), 2,
-                                                       stream()), "rr_evidential_ranking_step_f32")
-            ctx.ds_unit = d
-        else:
-            check(lib().rr_evidential_ranking_fwd_f32(ptr(mu), ptr(var), p.stride(0), ptr(targets), ptr(seg), Q, max_len,
-                                                      ptr(loss), ptr(part), stream()), "rr_evidential_ranking_fwd_f32")
-        ctx.save_for_backward(p, targets, seg)
-        ctx.meta = (Q, max_len)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        if ctx.ds_unit is not None and _is_unit(g):
             d, ctx.ds_unit = ctx.ds_unit, None
             FusedStep.hits += 1
-            return d, None, None, None, None
-        p, targets, seg = ctx.saved_tensors
-        Q, max_len = ctx.meta
-        g = g.reshape(-1).contiguous().float()
-        d = torch.empty(p.shape[0], 2, dtype=torch.float32, device=p.device)
-        check(lib().rr_evidential_ranking_bwd_f32(ptr(p[:, 0]), ptr(p[:, 1]), p.stride(0), ptr(targets), ptr(seg), Q,
-                                                  max_len, ptr(g), ptr(d[:, 0]), ptr(d[:, 1]), 2, stream()),
-              "rr_evidential_ranking_bwd_f32")
-        return d, None, None, None, None
+        else:
+            x = ctx.saved_tensors[0]                     # (the saved tensors keep the pointers in `args` alive)
+            kind, args = ctx.meta
+            g = g.reshape(-1).contiguous().float()
+            d, outs = _FusedListFn._out(kind, x)
+            _call(f"rr_{kind}_bwd_f32", *args, ptr(g), *outs)
+        return (None, d) + (None,) * 5
 
 
 class _RankNetFn(torch.autograd.Function):
@@ -246,41 +201,35 @@ class _RankNetFn(torch.autograd.Function):
 
 
 class _PointwiseFn(torch.autograd.Function):
+    """rr_{kind}_fwd_f32 / rr_{kind}_bwd_f32 of the pointwise means: kind 'mse' and 'exp_mse' (var None), 'gauss_nll' and
+    'lognorm' (x and var read with one stride); 0-d mean."""
+
     @staticmethod
-    def forward(ctx, mean, var, targets):
-        m = _vec(mean.detach())
+    def forward(ctx, kind, x, var, targets):
+        m = _vec(x.detach())
         v = None if var is None else _vec(var.detach())
         if v is not None and v.stride(0) != m.stride(0):
             v = v.contiguous()
             m = m.contiguous()
         n = m.shape[0]
+        if targets.shape[0] != n or (v is not None and v.shape[0] != n):
+            raise RuntimeError(f"{kind}: inputs and targets lengths differ")
         loss = _f1(m.device)
         part = torch.empty(int(lib().rr_pointwise_partial_count(n)), dtype=torch.float32, device=m.device)
-        if v is None:
-            check(lib().rr_mse_fwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(loss), ptr(part), stream()),
-                  "rr_mse_fwd_f32")
-        else:
-            check(lib().rr_gauss_nll_fwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(loss), ptr(part),
-                                             stream()), "rr_gauss_nll_fwd_f32")
+        args = ([ptr(m)] if v is None else [ptr(m), ptr(v)]) + [m.stride(0), ptr(targets), n]
+        _call(f"rr_{kind}_fwd_f32", *args, ptr(loss), ptr(part))
         ctx.save_for_backward(m, targets, *([] if v is None else [v]))
+        ctx.meta = (kind, args, [tuple(x.shape)] + ([] if var is None else [tuple(var.shape)]))
         return loss.reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        saved = ctx.saved_tensors
-        m, targets = saved[0], saved[1]
-        v = saved[2] if len(saved) > 2 else None
-        n = m.shape[0]
+        kind, args, shapes = ctx.meta                    # (the saved tensors keep the pointers in `args` alive)
+        m = ctx.saved_tensors[0]
         g = g.reshape(-1).contiguous().float()
-        dm = torch.empty(n, dtype=torch.float32, device=m.device)
-        if v is None:
-            check(lib().rr_mse_bwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), 1, stream()),
-                  "rr_mse_bwd_f32")
-            return dm, None, None
-        dv = torch.empty(n, dtype=torch.float32, device=m.device)
-        check(lib().rr_gauss_nll_bwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), ptr(dv), 1,
-                                         stream()), "rr_gauss_nll_bwd_f32")
-        return dm, dv, None
+        ds = [torch.empty(sh, dtype=torch.float32, device=m.device) for sh in shapes]      # contiguous, in the inputs' shapes
+        _call(f"rr_{kind}_bwd_f32", *args, ptr(g), *[ptr(d) for d in ds], 1)
+        return (None, *ds, *([None] * (3 - len(ds))))
 
 
 class LogCumsumExp(torch.autograd.Function):
@@ -312,7 +261,7 @@ class MLEloss(nn.Module):
 
     def forward(self, score, scope, targets_train, gpu: int = None):
         scope, seg, total, max_len, t = _prep(score, scope, targets_train, gpu)
-        return _ListMLEFn.apply(score, t, seg, len(scope), max_len)
+        return _FusedListFn.apply("listmle", score, t, seg, len(scope), max_len, total)
 
 
 class ListnetLoss(nn.Module):
@@ -320,7 +269,7 @@ class ListnetLoss(nn.Module):
 
     def forward(self, score, scope, targets, gpu: int = None):
         scope, seg, total, max_len, t = _prep(score, scope, targets, gpu)
-        return _ListNetFn.apply(score, t, seg, len(scope), max_len, total)
+        return _FusedListFn.apply("listnet", score, t, seg, len(scope), max_len, total)
 
 
 class evidential_ranking(nn.Module):
@@ -328,7 +277,7 @@ class evidential_ranking(nn.Module):
 
     def forward(self, possibilities, scope, targets, max_coeff=None, epoch=None, epochs=None, gpu: int = None):
         scope, seg, total, max_len, t = _prep(possibilities, scope, targets, gpu)
-        return _EvidentialFn.apply(possibilities, t, seg, len(scope), max_len)
+        return _FusedListFn.apply("evidential_ranking", possibilities, t, seg, len(scope), max_len, total)
 
 
 class GaussDisLoss(nn.Module):
@@ -338,8 +287,7 @@ class GaussDisLoss(nn.Module):
         if gpu is not None:
             torch.cuda.set_device(gpu)
         _lib.require_cuda(mean_scores, "mean_scores")
-        t = torch.as_tensor(targets, dtype=torch.float32).to(mean_scores.device).reshape(-1).contiguous()
-        return _PointwiseFn.apply(mean_scores, std_scores, t)
+        return _PointwiseFn.apply("gauss_nll", mean_scores, std_scores, _targets(targets, mean_scores.device))
 
 
 class MSELoss(nn.Module):
@@ -347,8 +295,7 @@ class MSELoss(nn.Module):
 
     def forward(self, output, targets):
         _lib.require_cuda(output, "output")
-        t = torch.as_tensor(targets, dtype=torch.float32).to(output.device).reshape(-1).contiguous()
-        return _PointwiseFn.apply(output, None, t)
+        return _PointwiseFn.apply("mse", output, None, _targets(targets, output.device))
 
 
 def ranknet_loss(y_pred, scope, targets, sigma: float = 1.0, gpu: int = None):
@@ -535,12 +482,10 @@ def evidential_loss_new(mu, v, alpha, beta, targets, gpu, lam=1, epsilon=1e-4):
     params = (mu, v, alpha, beta)
     shape = tuple(mu.shape)
     t = torch.as_tensor(targets, dtype=torch.float32)
-    if t.device != mu.device:
-        t = t.to(mu.device)
     if t.dim() > 1 or any(tuple(x.shape) != shape for x in params):
         raise ValueError(f"evidential_loss_new: parameters {[tuple(x.shape) for x in params]} with targets {tuple(t.shape)}: "
                          "supported are parameters [M] or [M, 1], all alike, with targets [M]")
-    t = t.reshape(-1).contiguous()
+    t = _targets(t, mu.device)
     M = t.shape[0]
     if len(shape) == 1 and shape[0] == M:
         cross = 0
@@ -563,49 +508,6 @@ def digamma(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
-class _PointwiseExtFn(torch.autograd.Function):
-    """Lognorm (kind 'lognorm': x = scores, var = std_scores) and exp-MSE (kind 'exp_mse', var None); 0-d mean."""
-
-    @staticmethod
-    def forward(ctx, kind, x, var, targets):
-        m = _vec(x.detach())
-        v = None if var is None else _vec(var.detach())
-        if v is not None and v.stride(0) != m.stride(0):
-            v = v.contiguous()
-            m = m.contiguous()
-        n = m.shape[0]
-        if targets.shape[0] != n or (v is not None and v.shape[0] != n):
-            raise RuntimeError(f"{kind}: inputs and targets lengths differ")
-        loss = _f1(m.device)
-        part = torch.empty(int(lib().rr_pointwise_partial_count(n)), dtype=torch.float32, device=m.device)
-        if v is None:
-            check(lib().rr_exp_mse_fwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(loss), ptr(part), stream()),
-                  "rr_exp_mse_fwd_f32")
-        else:
-            check(lib().rr_lognorm_fwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(loss), ptr(part), stream()),
-                  "rr_lognorm_fwd_f32")
-        ctx.save_for_backward(m, targets, *([] if v is None else [v]))
-        ctx.shapes = (tuple(x.shape), None if var is None else tuple(var.shape))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        saved = ctx.saved_tensors
-        m, targets = saved[0], saved[1]
-        v = saved[2] if len(saved) > 2 else None
-        n = m.shape[0]
-        g = g.reshape(-1).contiguous().float()
-        dm = torch.empty(n, dtype=torch.float32, device=m.device)
-        if v is None:
-            check(lib().rr_exp_mse_bwd_f32(ptr(m), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), 1, stream()),
-                  "rr_exp_mse_bwd_f32")
-            return None, dm.reshape(ctx.shapes[0]), None, None
-        dv = torch.empty(n, dtype=torch.float32, device=m.device)
-        check(lib().rr_lognorm_bwd_f32(ptr(m), ptr(v), m.stride(0), ptr(targets), n, ptr(g), ptr(dm), ptr(dv), 1, stream()),
-              "rr_lognorm_bwd_f32")
-        return None, dm.reshape(ctx.shapes[0]), dv.reshape(ctx.shapes[1]), None
-
-
 class Lognorm(nn.Module):
     """Reference train/loss.py:165-184 (0-d mean).  The reference prints the value on every call; this one does not."""
 
@@ -613,8 +515,7 @@ class Lognorm(nn.Module):
         if gpu is not None:
             torch.cuda.set_device(gpu)
         _lib.require_cuda(scores, "scores")
-        t = torch.as_tensor(targets, dtype=torch.float32).to(scores.device).reshape(-1).contiguous()
-        return _PointwiseExtFn.apply("lognorm", scores, std_scores, t)
+        return _PointwiseFn.apply("lognorm", scores, std_scores, _targets(targets, scores.device))
 
 
 class ExpMSELoss(nn.Module):
@@ -623,8 +524,7 @@ class ExpMSELoss(nn.Module):
 
     def forward(self, output, targets):
         _lib.require_cuda(output, "output")
-        t = torch.as_tensor(targets, dtype=torch.float32).to(output.device).reshape(-1).contiguous()
-        return _PointwiseExtFn.apply("exp_mse", output, None, t)
+        return _PointwiseFn.apply("exp_mse", output, None, _targets(targets, output.device))
 
 
 # ---------------------------------------------------------------------------------------------- composite task types in one launch

@@ -325,6 +325,45 @@ def test_fused_loss_step_has_the_bits_of_the_two_kernel_path(scope, parity_log):
                "unit, plain and scaled upstream gradients; 3 launches each)")
 
 
+@pytest.mark.parametrize("kind", ("listmle", "listnet", "evidential_ranking"))
+@pytest.mark.parametrize("scope", [[1, 2, 3, 32, 64, 65, 129, 300], [5, 0, 7, 0], [3]])
+def test_step_entry_points_take_a_preset_ticket_word(kind, scope):
+    """The step kernels test their ticket modulo Q (one finisher for all of them, csrc/loss_list.h): a counter word an earlier
+    launch left at a multiple of Q gives the loss and gradient bits of a zero word, and is zero afterwards."""
+    from reactranker_amd._lib import lib, check, ptr, stream
+    rng = np.random.default_rng(23)
+    m, Q = sum(scope), len(scope)
+    cols = 2 if kind == "evidential_ranking" else 1
+    x = rng.standard_normal((m, cols)).astype(np.float32) * 2
+    if cols == 2:
+        x[:, 1] = np.log1p(np.exp(x[:, 1])) + 1e-3
+    x = torch.tensor(x).cuda()
+    t = torch.tensor(rng.standard_normal(m).astype(np.float32)).cuda()
+    seg, total, max_len = RL._segments(tuple(scope), str(x.device))
+
+    def call(word):
+        counter = torch.full((1,), word, dtype=torch.int32, device="cuda")
+        loss = torch.full((1,), float("nan"), device="cuda")
+        part = torch.full((Q,), float("nan"), device="cuda")
+        d = torch.full_like(x, float("nan"))
+        ins = [ptr(x[:, 0]), ptr(x[:, 1]), x.stride(0)] if cols == 2 else [ptr(x), x.stride(0)]
+        outs = [ptr(d[:, 0]), ptr(d[:, 1]), 2] if cols == 2 else [ptr(d), 1]
+        extra = [total] if kind == "listnet" else []
+        name = f"rr_{kind}_step_f32"
+        check(getattr(lib(), name)(*ins, ptr(t), ptr(seg), Q, max_len, *extra, ptr(loss), ptr(part), ptr(counter), *outs, stream()), name)
+        torch.cuda.synchronize()
+        return loss, d, int(counter)
+
+    loss0, d0, left0 = call(0)
+    assert left0 == 0, "the ticket word was not left at zero"
+    assert bool(torch.isfinite(loss0).all()) and bool(torch.isfinite(d0).all())
+    for word in (Q, 3 * Q):
+        loss1, d1, left1 = call(word)
+        assert left1 == 0, word
+        assert torch.equal(loss1.view(torch.int32), loss0.view(torch.int32)), (word, float(loss0), float(loss1))
+        assert torch.equal(d1.view(torch.int32), d0.view(torch.int32)), word
+
+
 def test_fused_loss_step_inside_a_training_step_reaches_the_model_gradients():
     """the gradient handed out by the fused step drives the model's explicit backward: parameter gradients equal those of the
     two-kernel path bit for bit"""

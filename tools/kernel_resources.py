@@ -8,7 +8,7 @@ for line in open(sys.argv[1]):
         cur = {"name": m.group(1)}
         rows.append(cur)
         continue
-    m = re.search(r"remark: +([A-Za-z ]+?)(?: \[bytes/\w+\])?: (\d+)", line)
+    m = re.search(r"remark: +([A-Za-z ]+?)(?: \[\w+/\w+\])?: (\d+)", line)
     if m and cur is not None:
         cur[m.group(1).strip()] = int(m.group(2))
 names = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.split("\n")
