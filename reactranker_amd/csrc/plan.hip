@@ -101,41 +101,70 @@ constexpr int MAX_TENSORS = 768, MAX_AMAX = 256;
 struct TensorRec { const float* p; int64_t rows, cols, ld; float* amax; };
 
 struct Ctx {
-  bool launch;                        // false: layout pass only (no kernel is enqueued)
-  int status;
-  Arena ar;
-  bool f16;                           // split GEMMs on two f16 terms (needs split)
-  float* amax_base;                   // MAX_AMAX magnitude slots (null in a measuring pass)
-  int namax, ntr;
-  TensorRec tr[MAX_TENSORS];
+  bool launch = false;                // false: layout pass only (no kernel is enqueued)
+  int status = RR_OK;
+  Arena ar = {nullptr, 0, 0, false};
+  bool f16 = false;                   // split GEMMs on two f16 terms (needs split)
+  float* amax_base = nullptr;         // MAX_AMAX magnitude slots (null in a measuring pass)
+  int namax = 0, ntr = 0;
+  TensorRec tr[MAX_TENSORS] = {};
+  bool tracked(const float* p) const { return f16 && p != nullptr && ar.base != nullptr; }
+  TensorRec* find(const float* p) {                     // the record of a tensor, by address
+    if (!tracked(p)) return nullptr;
+    for (int i = 0; i < ntr; ++i)
+      if (tr[i].p == p) return &tr[i];
+    return nullptr;
+  }
   float* alloc(int64_t rows, int64_t cols) {            // arena tensor, remembered for amax_of()
     float* p = ar.f(rows, cols);
     if (f16 && p != nullptr && !ar.overflow) reg(p, rows, cols, cols);
     return p;
   }
   void reg(const float* p, int64_t rows, int64_t cols, int64_t ld) {
-    if (!f16 || p == nullptr || ar.base == nullptr) return;
-    for (int i = 0; i < ntr; ++i)
-      if (tr[i].p == p) return;
+    if (!tracked(p) || find(p) != nullptr) return;
     if (ntr == MAX_TENSORS) { fail(RR_ERR_UNSUPPORTED); return; }
     tr[ntr].p = p; tr[ntr].rows = rows; tr[ntr].cols = cols; tr[ntr].ld = ld; tr[ntr].amax = nullptr;
     ++ntr;
   }
-  Streams s;
-  bool use_side, use_aux, aux_bwd;
-  bool train;                         // RR_PLAN_TRAIN: the forward packs the backward's transposed weights too
-  bool ffn_chain;                     // the FFN head and its input-gradient chain as one launch each (rr_ffn_chain_f32)
-  bool timing;                        // RR_PLAN_TIME: events around the heavy launches
-  bool gather_multi;                  // sums of per-copy tensors ride on the gather over the copies (rr_gather_sum_multi_f32)
-  bool wgrad_early;                   // RR_PLAN_WGRAD_EARLY: W_h weight gradients issued in front of the dX GEMM of their layer
-  bool tail_pass;                     // the encoder pass being enqueued is the last one of the backward call (see wgrad)
-  bool side_joined;                   // the chain has waited for the side stream and nothing was put there since
-  hipStream_t cur;                    // stream of the backward chain being enqueued (main, or aux for the reactant pass)
-  bool split;                         // encoder GEMMs on the bf16 matrix core (three exact bf16 terms per f32 operand)
-  rr_pack_desc pq[RR_MAX_PACK];       // weight packs waiting for flush_packs()
-  int npq;
+  bool claim_slot(TensorRec& r) {                       // slots are handed out in call order
+    if (namax == MAX_AMAX) { fail(RR_ERR_UNSUPPORTED); return false; }
+    r.amax = amax_base + static_cast<size_t>(namax++) * RR_AMAX_FLOATS;
+    return true;
+  }
+  Streams s = {nullptr, nullptr, nullptr};
+  bool use_side = false, use_aux = false, aux_bwd = false;
+  bool train = false;                 // RR_PLAN_TRAIN: the forward packs the backward's transposed weights too
+  bool ffn_chain = true;              // the FFN head and its input-gradient chain as one launch each (rr_ffn_chain_f32)
+  bool timing = false;                // RR_PLAN_TIME: events around the heavy launches
+  bool gather_multi = false;          // sums of per-copy tensors ride on the gather over the copies (rr_gather_sum_multi_f32)
+  bool wgrad_early = false;           // RR_PLAN_WGRAD_EARLY: W_h weight gradients issued in front of the dX GEMM of their layer
+  bool tail_pass = false;             // the encoder pass being enqueued is the last one of the backward call (see wgrad)
+  bool side_joined = false;           // the chain has waited for the side stream and nothing was put there since
+  hipStream_t cur = nullptr;          // stream of the backward chain being enqueued (main, or aux for the reactant pass)
+  bool split = false;                 // encoder GEMMs on the bf16 matrix core (three exact bf16 terms per f32 operand)
+  rr_pack_desc pq[RR_MAX_PACK] = {};  // weight packs waiting for flush_packs()
+  int npq = 0;
   void fail(int st) { if (status == RR_OK && st != RR_OK) status = st; }
 };
+
+// the context of a plan call: what `flags` and the environment select, over the caller's workspace (callers add the streams)
+Ctx make_ctx(int flags, void* workspace, size_t workspace_bytes, bool launch) {
+  Ctx c;
+  c.launch = launch;
+  c.ar.base = static_cast<char*>(workspace);
+  c.ar.cap = workspace_bytes;
+  c.use_side = (flags & RR_PLAN_NO_SIDE_STREAM) == 0;
+  c.use_aux = (flags & RR_PLAN_NO_AUX_STREAM) == 0;
+  c.split = (flags & RR_PLAN_F32_GEMM) == 0;
+  c.f16 = c.split && (flags & RR_PLAN_F16X2_GEMM) != 0;
+  c.aux_bwd = (flags & RR_PLAN_AUX_BACKWARD) != 0;
+  c.train = (flags & RR_PLAN_TRAIN) != 0;
+  c.ffn_chain = (flags & RR_PLAN_NO_FFN_CHAIN) == 0 && !getenv("RR_NO_FFN_CHAIN");
+  c.timing = (flags & RR_PLAN_TIME) != 0;
+  c.gather_multi = !getenv("RR_NO_GATHER_MULTI");
+  c.wgrad_early = (flags & RR_PLAN_WGRAD_EARLY) != 0 || getenv("RR_WGRAD_EARLY") != nullptr;
+  return c;
+}
 
 #define RR_TRY(ctx, expr)                                                                         \
   do {                                                                                            \
@@ -148,35 +177,25 @@ struct Ctx {
 
 // the magnitude slot of tensor t; the first request enqueues its pass on `st` (where t's producer ran or was waited for)
 const float* amax_of(Ctx& c, const float* t, hipStream_t st) {
-  if (!c.f16 || t == nullptr || c.ar.base == nullptr) return nullptr;
-  for (int i = 0; i < c.ntr; ++i) {
-    TensorRec& r = c.tr[i];
-    if (r.p != t) continue;
-    if (r.amax == nullptr) {
-      if (c.namax == MAX_AMAX) { c.fail(RR_ERR_UNSUPPORTED); return nullptr; }
-      r.amax = c.amax_base + static_cast<size_t>(c.namax++) * RR_AMAX_FLOATS;
-      RR_TRY(c, rr_amax_f32(r.p, r.rows, static_cast<int>(r.cols), r.ld, r.amax, st));
-    }
-    return r.amax;
+  if (!c.tracked(t)) return nullptr;
+  TensorRec* r = c.find(t);
+  if (r == nullptr) {
+    if (getenv("RR_PLAN_DEBUG")) fprintf(stderr, "[rr plan] amax_of: unknown tensor %p\n", static_cast<const void*>(t));
+    c.fail(RR_ERR_ARG);
+    return nullptr;
   }
-  if (getenv("RR_PLAN_DEBUG")) fprintf(stderr, "[rr plan] amax_of: unknown tensor %p\n", static_cast<const void*>(t));
-  c.fail(RR_ERR_ARG);
-  return nullptr;
+  if (r->amax == nullptr) {
+    if (!c.claim_slot(*r)) return nullptr;
+    RR_TRY(c, rr_amax_f32(r->p, r->rows, static_cast<int>(r->cols), r->ld, r->amax, st));
+  }
+  return r->amax;
 }
 
 // the slot of a tensor whose PRODUCER maxes its magnitude in as it stores (no pass); null when the mode does not need one
 float* amax_claim(Ctx& c, const float* t) {
-  if (!c.f16 || t == nullptr || c.ar.base == nullptr) return nullptr;
-  for (int i = 0; i < c.ntr; ++i) {
-    TensorRec& r = c.tr[i];
-    if (r.p != t) continue;
-    if (r.amax == nullptr) {
-      if (c.namax == MAX_AMAX) { c.fail(RR_ERR_UNSUPPORTED); return nullptr; }
-      r.amax = c.amax_base + static_cast<size_t>(c.namax++) * RR_AMAX_FLOATS;
-    }
-    return r.amax;
-  }
-  return nullptr;
+  TensorRec* r = c.find(t);
+  if (r == nullptr || (r->amax == nullptr && !c.claim_slot(*r))) return nullptr;
+  return r->amax;
 }
 
 // A tensor that is about to be modified IN PLACE by a kernel without a magnitude output (axpby, the accumulating ReLU
@@ -186,12 +205,10 @@ float* amax_claim(Ctx& c, const float* t) {
 // (Since the shared-prefix tail forms d input in one gather epilogue no plan writes in place any more: the guard stays for
 // whoever adds such a kernel.)
 [[maybe_unused]] void inplace_write(Ctx& c, const float* t) {
-  if (!c.f16 || t == nullptr || c.ar.base == nullptr) return;
-  for (int i = 0; i < c.ntr; ++i) {
-    if (c.tr[i].p != t || c.tr[i].amax == nullptr) continue;
-    if (getenv("RR_PLAN_DEBUG")) fprintf(stderr, "[rr plan] in-place write to %p after its magnitude slot was claimed\n", static_cast<const void*>(t));
-    c.fail(RR_ERR_ARG);
-  }
+  const TensorRec* r = c.find(t);
+  if (r == nullptr || r->amax == nullptr) return;
+  if (getenv("RR_PLAN_DEBUG")) fprintf(stderr, "[rr plan] in-place write to %p after its magnitude slot was claimed\n", static_cast<const void*>(t));
+  c.fail(RR_ERR_ARG);
 }
 
 // RR_PLAN_TIME: HIP events around the heavy launches of a plan call (rr_plan_timing_take reads them)
@@ -313,11 +330,12 @@ void gather_multi(Ctx& c, const float* const* srcs, int n_srcs, int64_t n_src, i
   RR_TRY(c, rr_gather_sum_multi_f32(srcs, n_srcs, n_src, ld_src, idx, n_out, K, H, out, ld_out, st));
 }
 
-// gather-sum whose epilogue applies the ReLU / dropout mask of the activation `y` (sign bits when a split GEMM wrote
-// them, the f32 tensor otherwise; y == nullptr: no mask) and adds `n_adds` row-aligned tensors (rr_gather_sum_epi_f32)
-void gather_epi(Ctx& c, const float* src, int64_t n_src, const int32_t* idx, int64_t n_out, int K, int H, float* out,
-                hipStream_t st, const float* part, int64_t n_part, bool masked, const float* y, const uint8_t* y_bits,
-                float scale, const float* const* adds, int n_adds) {
+// gather-sum into a fresh [n_out, H] tensor whose epilogue applies the ReLU / dropout mask of the activation `y` (sign bits
+// when a split GEMM wrote them, the f32 tensor otherwise; !masked: no mask) and adds `n_adds` row-aligned tensors
+// (rr_gather_sum_epi_f32); row 0 from the column-sum partials `part` of the GEMM that produced `src`.  On the chain's stream.
+float* gather_epi(Ctx& c, const float* src, int64_t n_src, const int32_t* idx, int64_t n_out, int K, int H, const float* part,
+                  bool masked, const float* y, const uint8_t* y_bits, float scale, const float* const* adds, int n_adds) {
+  float* out = c.alloc(n_out, H);
   rr_gather_epi e;
   memset(&e, 0, sizeof(e));
   if (masked) { e.mask = y; e.ld_mask = H; e.mask_bits = y_bits; }
@@ -330,8 +348,9 @@ void gather_epi(Ctx& c, const float* src, int64_t n_src, const int32_t* idx, int
   memset(&ti, 0, sizeof(ti));
   ti.kind = 2; ti.M = n_out; ti.n_src = n_src; ti.N = H; ti.k1 = K; ti.k2 = n_adds;
   ti.mask = masked ? 1 : 0; ti.bits_in = (masked && y_bits != nullptr) ? 1 : 0;
-  Timed t(c, st, ti, n_out >= 8192);
-  RR_TRY(c, rr_gather_sum_epi_f32(src, n_src, H, idx, n_out, K, H, part, n_part, r4(H), &e, out, H, st));
+  Timed t(c, c.cur, ti, n_out >= 8192);
+  RR_TRY(c, rr_gather_sum_epi_f32(src, n_src, H, idx, n_out, K, H, part, rr_linear_colsum_rows(n_src), r4(H), &e, out, H, c.cur));
+  return out;
 }
 
 // weight gradient on the side stream: waits for the main stream's work so far (its operands), returns immediately
@@ -375,25 +394,17 @@ rr_wgrad_args WA(int64_t M, int N, const float* dy, int64_t ld_dy, float* dw, in
 // ------------------------------------------------------------------------------------------------ saved state
 constexpr int MAXD = 16;             // message-passing depth supported by a plan
 
-struct EncSaved {                    // mpn_forward / mpn_forward_shared
+struct MpSaved {                     // one message-passing pass: mpn_forward / mpn_forward_shared / mpndiff_forward
   uint8_t* bits[MAXD];               // sign bits of msgs[i] where a split GEMM produced it (rr_linear_args.mask_bits_out), else null
-  uint8_t* bits_h;
-  float* msgs[MAXD];                 // [nB, H] each (shared mode: msgs[0] unused)
+  uint8_t* bits_out;
+  float* msgs[MAXD];                 // [rows, H] each (shared mode: msgs[0] unused)
   float* amsgs[MAXD];                // [nA, H]
   float* a_last;
-  float* h;                          // [nA, H] atom hiddens (output)
+  float* out;                        // [nA, H] atom hiddens (output of W_o; the difference encoder at depth 0: msgs[0])
   float *msg0_u, *a0_u;              // shared prefix (distinct molecules)
   float* z1_u;                       // ... its pre-dropout output, and the stream the copies' masks were drawn from
   uint64_t seed0;
-};
-struct DiffSaved {
-  uint8_t* bits[MAXD];
-  uint8_t* bits_hid;
-  float* msgs[MAXD];
-  float* amsgs[MAXD];
-  float* a_last;
-  float* hid;
-  float* vecs; int64_t ld_vecs;      // [M, r4(H+F)]
+  float* vecs; int64_t ld_vecs;      // difference encoder: the readout [M, r4(H+F)]
 };
 struct FfnSaved {
   float* hs[RR_MAX_FFN + 1];         // hs[0] = vecs
@@ -410,150 +421,148 @@ struct PackedT {                     // transposed weights of the input-gradient
 struct Plan {
   PackedW pk;
   PackedT T;                         // filled by the forward under RR_PLAN_TRAIN, by the backward otherwise
-  EncSaved r, p;
-  DiffSaved d;
+  MpSaved r, p, d;                   // reactant, product and difference encoder
   FfnSaved f;
   size_t fwd_end;
 };
 
-// ------------------------------------------------------------------------------------------------ forward pieces
+// ------------------------------------------------------------------------------------------------ operand forms
+// first operand of a GEMM / weight gradient: rows of p (through idx) minus rows of sub (through sub_idx)
+struct Operand { const float* p; int64_t ld; int k; const int32_t* idx; const float* sub; int64_t ld_sub; const int32_t* sub_idx; };
+Operand plain(const float* p, int64_t ld, int k) { return {p, ld, k, nullptr, nullptr, 0, nullptr}; }
+Operand minus(const float* p, const int32_t* idx, const float* sub, const int32_t* sub_idx, int H) { return {p, H, H, idx, sub, H, sub_idx}; }
+
+void set_a1(rr_linear_args& a, const Operand& o) {
+  a.a1 = o.p; a.lda1 = o.ld; a.k1 = o.k; a.a1_idx = o.idx; a.a1_sub = o.sub; a.lda1_sub = o.ld_sub; a.a1_sub_idx = o.sub_idx;
+}
+void set_x1(rr_wgrad_args& w, const Operand& o) {
+  w.x1 = o.p; w.ldx1 = o.ld; w.k1 = o.k; w.x1_idx = o.idx; w.x1_sub = o.sub; w.ldx1_sub = o.ld_sub; w.x1_sub_idx = o.sub_idx;
+}
+// output [rows, N] and, where the consumer wants it (bits != null) and W's GEMM writes one, its sign-bit image
+void set_out(Ctx& c, rr_linear_args& a, float* out, int64_t rows, int N, const Packed& W, uint8_t** bits) {
+  a.c = out; a.ldc = N;
+  if (bits != nullptr) { *bits = mask_bits(c, W, rows, N); a.mask_bits_out = *bits; }
+}
+// side output: per-row-block partial sums of npad[r] * c[r] (the pad row's adjoint) -> fresh partials
+float* set_colsum(Ctx& c, rr_linear_args& a, const float* npad) {
+  float* part = c.alloc(rr_linear_colsum_rows(a.M), r4(a.N));
+  a.colsum_w = npad; a.colsum_partial = part; a.ld_partial = r4(a.N);
+  return part;
+}
+
+// What a message-passing loop runs over: bond messages (the reaction encoder) or atom messages (the difference encoder)
+struct Rel {
+  int64_t nA, rows;                  // atoms; messages
+  const int32_t* fwd; int K;         // a_msg[a] = sum of msg over fwd[a, :K]
+  const int32_t* fwd_t; int Kt;      // ... and that gather's adjoint
+  const int32_t* back; int Kb;       // adjoint of gather + message formation: d msg = sum of d_min over back[:, :Kb]
+  const float* npad;                 // pad-row weights of d_min's rows
+  const int32_t *b2a, *b2revb;       // bonds: W_h reads a_msg[b2a] - msg[b2revb]
+  const float* x2; int64_t ld_x2; int k2;   // atoms: W_h reads [a_msg | fb_sum]
+  Operand message(const float* a_msg, const float* msg, int H) const {
+    return b2a != nullptr ? minus(a_msg, b2a, msg, b2revb, H) : plain(a_msg, H, H);
+  }
+};
+Rel bonds(const rr_graph& g) { return {g.nA, g.nB, g.a2b, g.K, g.b2t, 1, g.b2b_t, g.Kb, g.npad_b, g.b2a, g.b2revb, nullptr, 0, 0}; }
+Rel atoms(const rr_graph& g, int FB) { return {g.nA, g.nA, g.a2a, g.K, g.a2a_t, g.K, g.a2a_t, g.K, g.npad, nullptr, nullptr, g.fb_sum, g.ld_fbs, FB}; }
+
+// ------------------------------------------------------------------------------------------------ forward layers
+// W_i: inp = in W^T + b (kept: the residual of every iteration), msg = drop(relu(inp))
+void wi_forward(Ctx& c, int64_t rows, int H, const Operand& in, const Packed& W, const float* bias, float p, uint64_t seed,
+                float*& inp, float*& msg, uint8_t** bits, hipStream_t st) {
+  inp = c.alloc(rows, H);
+  msg = c.alloc(rows, H);
+  rr_linear_args a = LA(rows, H);
+  set_a1(a, in);
+  set_w(a, W); a.bias = bias; a.act = RR_ACT_RELU; a.drop_p = p; a.drop_seed = seed;
+  a.c_pre = inp; a.ld_pre = H;
+  set_out(c, a, msg, rows, H, W, bits);                                                 // relu'(input) for the backward
+  lin(c, a, st);
+}
+
+// one W_h iteration: a_msg = sum of msg over the relation, out = drop(relu(inp[inp_idx] + message W^T + b)).
+// The shared prefix's form has p = 0 and no sign-bit image (bits == null).
+void wh_forward(Ctx& c, const Rel& R, int H, const Packed& W, const float* bias, const float* msg, float*& a_msg, float*& out,
+                uint8_t** bits, const float* inp, const int32_t* inp_idx, float p, uint64_t seed, hipStream_t st) {
+  a_msg = c.alloc(R.nA, H);
+  gather_sum(c, msg, R.rows, H, R.fwd, R.nA, R.K, H, a_msg, H, st);
+  out = c.alloc(R.rows, H);
+  rr_linear_args a = LA(R.rows, H);
+  set_a1(a, R.message(a_msg, msg, H)); a.a2 = R.x2; a.lda2 = R.ld_x2; a.k2 = R.k2;
+  set_w(a, W); a.bias = bias; a.residual = inp; a.ldr = H; a.residual_idx = inp_idx; a.act = RR_ACT_RELU;
+  a.drop_p = p; a.drop_seed = seed;
+  set_out(c, a, out, R.rows, H, W, bits);
+  lin(c, a, st);
+}
+
+// W_o: a_last = sum of the last messages, out = drop(relu([first | a_last] W^T + b))
+void wo_forward(Ctx& c, const Rel& R, int H, const Operand& first, const Packed& W, const float* bias, float p, uint64_t seed,
+                const float* msg, MpSaved& S, hipStream_t st) {
+  S.a_last = c.alloc(R.nA, H);
+  gather_sum(c, msg, R.rows, H, R.fwd, R.nA, R.K, H, S.a_last, H, st);
+  S.out = c.alloc(R.nA, H);
+  rr_linear_args a = LA(R.nA, H);
+  set_a1(a, first); a.a2 = S.a_last; a.lda2 = H; a.k2 = H;
+  set_w(a, W); a.bias = bias; a.act = RR_ACT_RELU; a.drop_p = p; a.drop_seed = seed;
+  set_out(c, a, S.out, R.nA, H, W, &S.bits_out);
+  lin(c, a, st);
+}
+
 // MPN.forward, return_atom_hiddens=True (models/mpn.py:61-108)
-void mpn_forward(Ctx& c, const rr_model& m, const rr_graph& g, const PackedW& pk, float p, uint64_t seed, EncSaved& S,
+void mpn_forward(Ctx& c, const rr_model& m, const rr_graph& g, const PackedW& pk, float p, uint64_t seed, MpSaved& S,
                  hipStream_t st) {
-  const int H = m.H, depth = m.depth, FB = m.bond_fdim;
-  float* inp = c.alloc(g.nB, H);
-  S.msgs[0] = c.alloc(g.nB, H);
-  {
-    rr_linear_args a = LA(g.nB, H);
-    a.a1 = g.f_bonds; a.lda1 = g.ld_fb; a.k1 = FB;
-    set_w(a, pk.enc_wi); a.bias = m.enc_wi.b; a.act = RR_ACT_RELU;
-    a.c = S.msgs[0]; a.ldc = H; a.c_pre = inp; a.ld_pre = H;
-    S.bits[0] = mask_bits(c, pk.enc_wi, g.nB, H); a.mask_bits_out = S.bits[0];           // relu'(input) for the backward
-    lin(c, a, st);                                                              // :80-81
-  }
-  for (int it = 0; it < depth - 1; ++it) {                                              // :84
-    S.amsgs[it] = c.alloc(g.nA, H);
-    gather_sum(c, S.msgs[it], g.nB, H, g.a2b, g.nA, g.K, H, S.amsgs[it], H, st);       // :89-90
-    S.msgs[it + 1] = c.alloc(g.nB, H);
-    rr_linear_args a = LA(g.nB, H);
-    a.a1 = S.amsgs[it]; a.lda1 = H; a.k1 = H; a.a1_idx = g.b2a;
-    a.a1_sub = S.msgs[it]; a.lda1_sub = H; a.a1_sub_idx = g.b2revb;
-    set_w(a, pk.enc_wh); a.bias = m.enc_wh.b; a.residual = inp; a.ldr = H; a.act = RR_ACT_RELU;
-    a.drop_p = p; a.drop_seed = site_seed(seed, it);
-    a.c = S.msgs[it + 1]; a.ldc = H;
-    S.bits[it + 1] = mask_bits(c, pk.enc_wh, g.nB, H); a.mask_bits_out = S.bits[it + 1];
-    lin(c, a, st);                                                              // :91-97
-  }
-  S.a_last = c.alloc(g.nA, H);
-  gather_sum(c, S.msgs[depth - 1], g.nB, H, g.a2b, g.nA, g.K, H, S.a_last, H, st);     // :101-102
-  S.h = c.alloc(g.nA, H);
-  rr_linear_args a = LA(g.nA, H);
-  a.a1 = g.f_atoms; a.lda1 = g.ld_fa; a.k1 = m.atom_fdim; a.a2 = S.a_last; a.lda2 = H; a.k2 = H;
-  set_w(a, pk.enc_wo); a.bias = m.enc_wo.b; a.act = RR_ACT_RELU; a.drop_p = p; a.drop_seed = site_seed(seed, 1000);
-  a.c = S.h; a.ldc = H;
-  S.bits_h = mask_bits(c, pk.enc_wo, g.nA, H); a.mask_bits_out = S.bits_h;
-  lin(c, a, st);                                                              // :103-105
+  const int H = m.H, depth = m.depth;
+  const Rel R = bonds(g);
+  float* inp;
+  wi_forward(c, g.nB, H, plain(g.f_bonds, g.ld_fb, m.bond_fdim), pk.enc_wi, m.enc_wi.b, 0.f, 0, inp, S.msgs[0], &S.bits[0], st);   // :80-81
+  for (int it = 0; it < depth - 1; ++it)                                                // :84, :89-97
+    wh_forward(c, R, H, pk.enc_wh, m.enc_wh.b, S.msgs[it], S.amsgs[it], S.msgs[it + 1], &S.bits[it + 1], inp, nullptr, p,
+               site_seed(seed, it), st);
+  wo_forward(c, R, H, plain(g.f_atoms, g.ld_fa, m.atom_fdim), pk.enc_wo, m.enc_wo.b, p, site_seed(seed, 1000), S.msgs[depth - 1], S,
+             st);                                                                        // :101-105
 }
 
 // the same for a batch whose molecules repeat: the deterministic prefix runs once per distinct molecule
 void mpn_forward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr_graph& g, const int32_t* bmap,
-                        const PackedW& pk, float p, uint64_t seed, EncSaved& S, hipStream_t st) {
-  const int H = m.H, depth = m.depth, FB = m.bond_fdim;
-  float* inp_u = c.alloc(gu.nB, H);
-  S.msg0_u = c.alloc(gu.nB, H);
-  {
-    rr_linear_args a = LA(gu.nB, H);
-    a.a1 = gu.f_bonds; a.lda1 = gu.ld_fb; a.k1 = FB;
-    set_w(a, pk.enc_wi); a.bias = m.enc_wi.b; a.act = RR_ACT_RELU;
-    a.c = S.msg0_u; a.ldc = H; a.c_pre = inp_u; a.ld_pre = H;
-    lin(c, a, st);
-  }
-  S.a0_u = c.alloc(gu.nA, H);
-  gather_sum(c, S.msg0_u, gu.nB, H, gu.a2b, gu.nA, gu.K, H, S.a0_u, H, st);
-  float* z1_u = c.alloc(gu.nB, H);
-  {
-    rr_linear_args a = LA(gu.nB, H);
-    a.a1 = S.a0_u; a.lda1 = H; a.k1 = H; a.a1_idx = gu.b2a;
-    a.a1_sub = S.msg0_u; a.lda1_sub = H; a.a1_sub_idx = gu.b2revb;
-    set_w(a, pk.enc_wh); a.bias = m.enc_wh.b; a.residual = inp_u; a.ldr = H; a.act = RR_ACT_RELU;
-    a.c = z1_u; a.ldc = H;
-    lin(c, a, st);                                                              // pre-dropout, shared
-  }
+                        const PackedW& pk, float p, uint64_t seed, MpSaved& S, hipStream_t st) {
+  const int H = m.H, depth = m.depth;
+  const Rel R = bonds(g);
+  float* inp_u;
+  wi_forward(c, gu.nB, H, plain(gu.f_bonds, gu.ld_fb, m.bond_fdim), pk.enc_wi, m.enc_wi.b, 0.f, 0, inp_u, S.msg0_u, nullptr, st);
+  wh_forward(c, bonds(gu), H, pk.enc_wh, m.enc_wh.b, S.msg0_u, S.a0_u, S.z1_u, nullptr, inp_u, nullptr, 0.f, 0, st);   // pre-dropout, shared
   S.msgs[0] = nullptr;
   S.msgs[1] = c.alloc(g.nB, H);
-  RR_TRY(c, rr_gather_dropout_amax_f32(z1_u, gu.nB, H, bmap, g.nB, H, p, site_seed(seed, 0), S.msgs[1], H, amax_claim(c, S.msgs[1]), st));   // per-copy masks
-  S.z1_u = z1_u;
   S.seed0 = site_seed(seed, 0);
-  for (int it = 1; it < depth - 1; ++it) {
-    S.amsgs[it] = c.alloc(g.nA, H);
-    gather_sum(c, S.msgs[it], g.nB, H, g.a2b, g.nA, g.K, H, S.amsgs[it], H, st);
-    S.msgs[it + 1] = c.alloc(g.nB, H);
-    rr_linear_args a = LA(g.nB, H);
-    a.a1 = S.amsgs[it]; a.lda1 = H; a.k1 = H; a.a1_idx = g.b2a;
-    a.a1_sub = S.msgs[it]; a.lda1_sub = H; a.a1_sub_idx = g.b2revb;
-    set_w(a, pk.enc_wh); a.bias = m.enc_wh.b; a.residual = inp_u; a.ldr = H; a.residual_idx = bmap; a.act = RR_ACT_RELU;
-    a.drop_p = p; a.drop_seed = site_seed(seed, it);
-    a.c = S.msgs[it + 1]; a.ldc = H;
-    S.bits[it + 1] = mask_bits(c, pk.enc_wh, g.nB, H); a.mask_bits_out = S.bits[it + 1];
-    lin(c, a, st);
-  }
-  S.a_last = c.alloc(g.nA, H);
-  gather_sum(c, S.msgs[depth - 1], g.nB, H, g.a2b, g.nA, g.K, H, S.a_last, H, st);
-  S.h = c.alloc(g.nA, H);
-  rr_linear_args a = LA(g.nA, H);
-  a.a1 = g.f_atoms; a.lda1 = g.ld_fa; a.k1 = m.atom_fdim; a.a2 = S.a_last; a.lda2 = H; a.k2 = H;
-  set_w(a, pk.enc_wo); a.bias = m.enc_wo.b; a.act = RR_ACT_RELU; a.drop_p = p; a.drop_seed = site_seed(seed, 1000);
-  a.c = S.h; a.ldc = H;
-  S.bits_h = mask_bits(c, pk.enc_wo, g.nA, H); a.mask_bits_out = S.bits_h;
-  lin(c, a, st);
+  RR_TRY(c, rr_gather_dropout_amax_f32(S.z1_u, gu.nB, H, bmap, g.nB, H, p, S.seed0, S.msgs[1], H, amax_claim(c, S.msgs[1]), st));   // per-copy masks
+  for (int it = 1; it < depth - 1; ++it)
+    wh_forward(c, R, H, pk.enc_wh, m.enc_wh.b, S.msgs[it], S.amsgs[it], S.msgs[it + 1], &S.bits[it + 1], inp_u, bmap, p,
+               site_seed(seed, it), st);
+  wo_forward(c, R, H, plain(g.f_atoms, g.ld_fa, m.atom_fdim), pk.enc_wo, m.enc_wo.b, p, site_seed(seed, 1000), S.msgs[depth - 1], S,
+             st);
 }
 
 // MPNDiff.forward (models/mpn.py:170-240): atom_features = x - x_sub[x_sub_idx]
 void mpndiff_forward(Ctx& c, const rr_model& m, const rr_graph& g, const PackedW& pk, float p, uint64_t seed, const float* x,
-                     const float* x_sub, const int32_t* x_sub_idx, const float* feat, int F, uint64_t out_seed, DiffSaved& S,
+                     const float* x_sub, const int32_t* x_sub_idx, const float* feat, int F, uint64_t out_seed, MpSaved& S,
                      hipStream_t st) {
-  const int H = m.H, depth = m.diff_depth, FB = m.bond_fdim;
-  float* inp = c.alloc(g.nA, H);
-  S.msgs[0] = c.alloc(g.nA, H);
-  {
-    rr_linear_args a = LA(g.nA, H);
-    a.a1 = x; a.lda1 = H; a.k1 = H; a.a1_sub = x_sub; a.lda1_sub = H; a.a1_sub_idx = x_sub_idx;
-    set_w(a, pk.dif_wi); a.bias = m.dif_wi.b; a.act = RR_ACT_RELU;
-    a.drop_p = depth == 0 ? p : 0.f; a.drop_seed = site_seed(seed, 2000);              // :221 (depth 0: dropout(message))
-    a.c = S.msgs[0]; a.ldc = H; a.c_pre = inp; a.ld_pre = H;
-    S.bits[0] = mask_bits(c, pk.dif_wi, g.nA, H); a.mask_bits_out = S.bits[0];
-    lin(c, a, st);                                                              // :194-195
-  }
+  const int H = m.H, depth = m.diff_depth;
+  const Rel R = atoms(g, m.bond_fdim);
+  const Operand feats = minus(x, nullptr, x_sub, x_sub_idx, H);
+  float* inp;
+  wi_forward(c, g.nA, H, feats, pk.dif_wi, m.dif_wi.b, depth == 0 ? p : 0.f, site_seed(seed, 2000), inp, S.msgs[0], &S.bits[0],
+             st);                                                                        // :194-195, :221 (depth 0: dropout(message))
   if (depth > 0) {
-    for (int it = 0; it < depth - 1; ++it) {                                            // :199
-      S.amsgs[it] = c.alloc(g.nA, H);
-      gather_sum(c, S.msgs[it], g.nA, H, g.a2a, g.nA, g.K, H, S.amsgs[it], H, st);     // :201
-      S.msgs[it + 1] = c.alloc(g.nA, H);
-      rr_linear_args a = LA(g.nA, H);
-      a.a1 = S.amsgs[it]; a.lda1 = H; a.k1 = H; a.a2 = g.fb_sum; a.lda2 = g.ld_fbs; a.k2 = FB;
-      set_w(a, pk.dif_wh); a.bias = m.dif_wh.b; a.residual = inp; a.ldr = H; a.act = RR_ACT_RELU;
-      a.drop_p = p; a.drop_seed = site_seed(seed, 2001 + it);
-      a.c = S.msgs[it + 1]; a.ldc = H;
-      S.bits[it + 1] = mask_bits(c, pk.dif_wh, g.nA, H); a.mask_bits_out = S.bits[it + 1];
-      lin(c, a, st);                                                              // :202-213
-    }
-    S.a_last = c.alloc(g.nA, H);
-    gather_sum(c, S.msgs[depth - 1], g.nA, H, g.a2a, g.nA, g.K, H, S.a_last, H, st);   // :215-216
-    S.hid = c.alloc(g.nA, H);
-    rr_linear_args a = LA(g.nA, H);
-    a.a1 = x; a.lda1 = H; a.k1 = H; a.a1_sub = x_sub; a.lda1_sub = H; a.a1_sub_idx = x_sub_idx;
-    a.a2 = S.a_last; a.lda2 = H; a.k2 = H;
-    set_w(a, pk.dif_wo); a.bias = m.dif_wo.b; a.act = RR_ACT_RELU; a.drop_p = p; a.drop_seed = site_seed(seed, 3000);
-    a.c = S.hid; a.ldc = H;
-    S.bits_hid = mask_bits(c, pk.dif_wo, g.nA, H); a.mask_bits_out = S.bits_hid;
-    lin(c, a, st);                                                              // :217-219
+    for (int it = 0; it < depth - 1; ++it)                                              // :199, :201-213
+      wh_forward(c, R, H, pk.dif_wh, m.dif_wh.b, S.msgs[it], S.amsgs[it], S.msgs[it + 1], &S.bits[it + 1], inp, nullptr, p,
+                 site_seed(seed, 2001 + it), st);
+    wo_forward(c, R, H, feats, pk.dif_wo, m.dif_wo.b, p, site_seed(seed, 3000), S.msgs[depth - 1], S, st);   // :215-219
   } else {
     S.a_last = nullptr;
-    S.hid = S.msgs[0];
+    S.out = S.msgs[0];
   }
   S.ld_vecs = r4(H + F);
   S.vecs = c.alloc(g.M, S.ld_vecs);
-  RR_TRY(c, rr_segment_mean_fwd_f32(S.hid, H, g.a_scope, g.M, H, feat, F, p, out_seed, S.vecs, S.ld_vecs, st));   // :224-238
+  RR_TRY(c, rr_segment_mean_fwd_f32(S.out, H, g.a_scope, g.M, H, feat, F, p, out_seed, S.vecs, S.ld_vecs, st));   // :224-238
 }
 
 // FFN.forward after its input dropout (models/base_model.py:32-60).  The whole head is ONE launch where rr_ffn_chain_f32 takes the
@@ -664,7 +673,7 @@ void forward_all(Ctx& c, const rr_model& m, const rr_step& s, Plan& P) {
   else mpn_forward(c, m, s.r, P.pk, p, s_r, P.r, rs);
   mpn_forward(c, m, s.p, P.pk, p, s_p, P.p, main);
   if (c.launch && c.use_aux) c.fail(stream_wait(main, c.s.aux));
-  mpndiff_forward(c, m, s.p, P.pk, p, site_seed(s.seed, 3), P.p.h, P.r.h, s.mode == RR_STEP_DEDUP ? s.amap : nullptr,
+  mpndiff_forward(c, m, s.p, P.pk, p, site_seed(s.seed, 3), P.p.out, P.r.out, s.mode == RR_STEP_DEDUP ? s.amap : nullptr,
                   s.feat, s.F, site_seed(s.seed, 4), P.d, main);
   ffn_forward(c, m, P.pk, s.p.M, p, site_seed(s.seed, 5), P.d.vecs, P.d.ld_vecs, s.out, P.f, main);
   P.fwd_end = c.ar.off;
@@ -673,120 +682,111 @@ void forward_all(Ctx& c, const rr_model& m, const rr_step& s, Plan& P) {
 // ------------------------------------------------------------------------------------------------ backward pieces
 struct EncGrads { float *wi, *bi, *wh, *bh, *wo, *bo; };
 
-// d message = adjoint of the bond message (one gather over b2b_t; row 0 from the GEMM's weighted column sums)
-float* bond_adjoint(Ctx& c, const rr_graph& g, int H, const float* d_min, const float* part, hipStream_t st) {
-  float* d_msg = c.alloc(g.nB, H);
-  gather_sum(c, d_min, g.nB, H, g.b2b_t, g.nB, g.Kb, H, d_msg, H, st, part, rr_linear_colsum_rows(g.nB), r4(H));
-  return d_msg;
+// weight-gradient arguments of a W_h iteration whose masked output gradient is dz (its input: Rel::message and x2)
+rr_wgrad_args wh_wgrad_args(const Rel& R, int H, const float* dz, const float* a_msg, const float* msg, float* gw, float* gb,
+                            int accumulate) {
+  rr_wgrad_args w = WA(R.rows, H, dz, H, gw, H + R.k2, gb, accumulate);
+  set_x1(w, R.message(a_msg, msg, H)); w.x2 = R.x2; w.ldx2 = R.ld_x2; w.k2 = R.k2;
+  return w;
 }
 
-// adjoint of mpn_forward; accumulate = the gradient buffers already hold the other encoder pass
-void mpn_backward(Ctx& c, const rr_model& m, const rr_graph& g, const PackedW& pk, const Packed& wh_t, const Packed& wo_t,
-                  float p, const EncSaved& S, const float* dH, float sign, const EncGrads& G, int accumulate) {
-  const int H = m.H, depth = m.depth;
-  const float ks = 1.0f / (1.0f - p);
-  hipStream_t st = c.cur;
-  float* dz_o = c.alloc(g.nA, H);
-  float* d_a = c.alloc(g.nA, H);
-  float* part = c.alloc(rr_linear_colsum_rows(g.nA), r4(H));
-  {
-    rr_linear_args a = LA(g.nA, H);
-    a.a1 = dH; a.lda1 = H; a.k1 = H; a.a_mask = S.h; a.a_mask_bits = S.bits_h; a.ld_mask = H; a.mask_scale = sign * ks;
-    a.dz_out = dz_o; a.ld_dz = H; set_w(a, wo_t);
-    a.colsum_w = g.npad; a.colsum_partial = part; a.ld_partial = r4(H);
-    a.c = d_a; a.ldc = H;
-    lin(c, a, st);
-  }
-  {
-    rr_wgrad_args w = WA(g.nA, H, dz_o, H, G.wo, m.enc_wo.in, G.bo, accumulate);
-    w.x1 = g.f_atoms; w.ldx1 = g.ld_fa; w.k1 = m.atom_fdim; w.x2 = S.a_last; w.ldx2 = H; w.k2 = H;
-    wgrad(c, w);
-  }
-  // From here on every gradient that reaches a layer is produced ALREADY masked by that layer's ReLU / dropout pattern:
-  // the gather that forms d message applies (y > 0) / (1 - p) of the layer below in its epilogue (rr_gather_sum_epi_f32),
-  // so dZ is the gather's output - the dX GEMMs read it as a plain operand and the weight gradients stream it as is -
-  // and the last gather also adds every iteration's dZ: its output is d input (models/mpn.py:94), no pass of its own.
+// A W_h iteration's input gradient d_min = dz W_h with the column-sum partials of its pad row (-> part), and the layer's
+// weight gradient `w` in front of that GEMM (wgrad_early: it starts with the GEMM that reads the same dZ) or behind it.
+// w == null: the caller has issued it already (the shared prefix).  gather_epi over R.back forms d message from d_min.
+float* wh_backward_dx(Ctx& c, const Rel& R, int H, const Packed& wh_t, const float* dz, rr_wgrad_args* w, float*& part) {
+  float* d_min = c.alloc(R.rows, H);
+  rr_linear_args a = LA(R.rows, H);
+  set_a1(a, plain(dz, H, H)); set_w(a, wh_t);
+  part = set_colsum(c, a, R.npad);
+  a.c = d_min; a.ldc = H;
+  if (w != nullptr && c.wgrad_early) wgrad(c, *w);
+  lin(c, a, c.cur);
+  if (w != nullptr && !c.wgrad_early) wgrad(c, *w);
+  return d_min;
+}
+
+// The masked message-passing backward, from d a_last (with its pad-row partials) to d input.  Every gradient that reaches a
+// layer is produced ALREADY masked by that layer's ReLU / dropout pattern: the gather that forms d message applies
+// (y > 0) / (1 - p) of the layer below in its epilogue (rr_gather_sum_epi_f32), so dZ is the gather's output - the dX GEMMs
+// read it as a plain operand and the weight gradients stream it as is - and the last gather (it == 0: msgs[0] = relu(input),
+// no dropout) also adds every iteration's dZ: its output is d input (models/mpn.py:94), no pass of its own.
+float* mp_backward(Ctx& c, const Rel& R, int H, int depth, const Packed& wh_t, float ks, const MpSaved& S, const float* d_a,
+                   const float* part_a, float* gw, float* gb, int accumulate) {
   const float* dzs[MAXD];
   int ndz = 0;
-  float* cur = c.alloc(g.nB, H);        // dZ of iteration depth-2 (or d input when depth == 1)
-  {
-    const int top = depth - 1;         // the activation whose pattern masks this gradient: msgs[depth-1]
-    gather_epi(c, d_a, g.nA, g.b2t, g.nB, 1, H, cur, st, part, rr_linear_colsum_rows(g.nA), true, S.msgs[top], S.bits[top],
-               top == 0 ? 1.0f : ks, nullptr, 0);
-  }
+  const int top = depth - 1;           // the activation whose pattern masks the first gradient: dZ of iteration depth-2 (or d input)
+  float* cur = gather_epi(c, d_a, R.nA, R.fwd_t, R.rows, R.Kt, H, part_a, true, S.msgs[top], S.bits[top], top == 0 ? 1.0f : ks,
+                          nullptr, 0);
   for (int it = depth - 2; it >= 0; --it) {
-    float* dz = cur;
-    float* d_min = c.alloc(g.nB, H);
-    float* partb = c.alloc(rr_linear_colsum_rows(g.nB), r4(H));
-    rr_linear_args a = LA(g.nB, H);
-    a.a1 = dz; a.lda1 = H; a.k1 = H; set_w(a, wh_t);
-    a.colsum_w = g.npad_b; a.colsum_partial = partb; a.ld_partial = r4(H);
-    a.c = d_min; a.ldc = H;
-    rr_wgrad_args w = WA(g.nB, H, dz, H, G.wh, H, G.bh, (accumulate || it != depth - 2) ? 1 : 0);
-    w.x1 = S.amsgs[it]; w.ldx1 = H; w.k1 = H; w.x1_idx = g.b2a; w.x1_sub = S.msgs[it]; w.ldx1_sub = H; w.x1_sub_idx = g.b2revb;
-    if (c.wgrad_early) wgrad(c, w);                      // (starts with the dX GEMM that reads the same dZ instead of behind it)
-    lin(c, a, st);
-    if (!c.wgrad_early) wgrad(c, w);
+    const float* dz = cur;
+    rr_wgrad_args w = wh_wgrad_args(R, H, dz, S.amsgs[it], S.msgs[it], gw, gb, (accumulate || it != depth - 2) ? 1 : 0);
+    float* part;
+    const float* d_min = wh_backward_dx(c, R, H, wh_t, dz, &w, part);
     dzs[ndz++] = dz;
-    // adjoint of the bond message (one gather over b2b_t; row 0 from the GEMM's weighted column sums), masked by msgs[it];
-    // the last one (it == 0: msgs[0] = relu(input), no dropout) adds the dZ of every iteration -> d input
-    cur = c.alloc(g.nB, H);
-    gather_epi(c, d_min, g.nB, g.b2b_t, g.nB, g.Kb, H, cur, st, partb, rr_linear_colsum_rows(g.nB), true, S.msgs[it], S.bits[it],
-               it == 0 ? 1.0f : ks, dzs, it == 0 ? ndz : 0);
+    cur = gather_epi(c, d_min, R.rows, R.back, R.rows, R.Kb, H, part, true, S.msgs[it], S.bits[it], it == 0 ? 1.0f : ks, dzs,
+                     it == 0 ? ndz : 0);
   }
-  float* d_inp = cur;
-  rr_wgrad_args w = WA(g.nB, H, d_inp, H, G.wi, m.enc_wi.in, G.bi, accumulate);
-  w.x1 = g.f_bonds; w.ldx1 = g.ld_fb; w.k1 = m.bond_fdim;
+  return cur;
+}
+
+// The encoder's W_o layer: the input-gradient GEMM applies the ReLU / dropout mask of the output in its operand loader (dH has
+// two consumers with different masks) and writes the masked gradient dZ as a side output, which the weight gradient streams
+// -> d a_last and its pad-row partials
+float* wo_backward(Ctx& c, const rr_model& m, const rr_graph& g, const Packed& wo_t, float scale, const MpSaved& S, const float* dH,
+                   const EncGrads& G, int accumulate, float*& part) {
+  const int H = m.H;
+  float* dz_o = c.alloc(g.nA, H);
+  float* d_a = c.alloc(g.nA, H);
+  rr_linear_args a = LA(g.nA, H);
+  set_a1(a, plain(dH, H, H)); a.a_mask = S.out; a.a_mask_bits = S.bits_out; a.ld_mask = H; a.mask_scale = scale;
+  a.dz_out = dz_o; a.ld_dz = H; set_w(a, wo_t);
+  part = set_colsum(c, a, g.npad);
+  a.c = d_a; a.ldc = H;
+  lin(c, a, c.cur);
+  rr_wgrad_args w = WA(g.nA, H, dz_o, H, G.wo, m.enc_wo.in, G.bo, accumulate);
+  set_x1(w, plain(g.f_atoms, g.ld_fa, m.atom_fdim)); w.x2 = S.a_last; w.ldx2 = H; w.k2 = H;
+  wgrad(c, w);
+  return d_a;
+}
+
+// the last weight gradient of an encoder pass: W_i's
+void wi_wgrad(Ctx& c, const rr_model& m, const rr_graph& g, const float* d_inp, const EncGrads& G, int accumulate) {
+  rr_wgrad_args w = WA(g.nB, m.H, d_inp, m.H, G.wi, m.enc_wi.in, G.bi, accumulate);
+  set_x1(w, plain(g.f_bonds, g.ld_fb, m.bond_fdim));
   wgrad(c, w, /*tail=*/true);
 }
 
+// adjoint of mpn_forward; accumulate = the gradient buffers already hold the other encoder pass
+void mpn_backward(Ctx& c, const rr_model& m, const rr_graph& g, const Packed& wh_t, const Packed& wo_t, float p, const MpSaved& S,
+                  const float* dH, float sign, const EncGrads& G, int accumulate) {
+  const float ks = 1.0f / (1.0f - p);
+  float* part;
+  const float* d_a = wo_backward(c, m, g, wo_t, sign * ks, S, dH, G, accumulate, part);
+  const float* d_inp = mp_backward(c, bonds(g), m.H, m.depth, wh_t, ks, S, d_a, part, G.wh, G.bh, accumulate);
+  wi_wgrad(c, m, g, d_inp, G, accumulate);
+}
+
 void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr_graph& g, const int32_t* bmap_t, int bmap_t_cols,
-                         const Packed& wh_t, const Packed& wo_t, float p, const EncSaved& S, const float* dH, float sign,
+                         const Packed& wh_t, const Packed& wo_t, float p, const MpSaved& S, const float* dH, float sign,
                          const EncGrads& G, int accumulate) {
   const int H = m.H, depth = m.depth;
   const float ks = 1.0f / (1.0f - p);
+  const Rel R = bonds(g), Ru = bonds(gu);
   hipStream_t st = c.cur;
-  float* dz_o = c.alloc(g.nA, H);
-  float* d_a = c.alloc(g.nA, H);
-  float* part = c.alloc(rr_linear_colsum_rows(g.nA), r4(H));
-  {
-    rr_linear_args a = LA(g.nA, H);
-    a.a1 = dH; a.lda1 = H; a.k1 = H; a.a_mask = S.h; a.a_mask_bits = S.bits_h; a.ld_mask = H; a.mask_scale = sign * ks;
-    a.dz_out = dz_o; a.ld_dz = H; set_w(a, wo_t);
-    a.colsum_w = g.npad; a.colsum_partial = part; a.ld_partial = r4(H);
-    a.c = d_a; a.ldc = H;
-    lin(c, a, st);
-  }
-  {
-    rr_wgrad_args w = WA(g.nA, H, dz_o, H, G.wo, m.enc_wo.in, G.bo, accumulate);
-    w.x1 = g.f_atoms; w.ldx1 = g.ld_fa; w.k1 = m.atom_fdim; w.x2 = S.a_last; w.ldx2 = H; w.k2 = H;
-    wgrad(c, w);
-  }
-  // per-copy W_h layers (it >= 1): gradients arrive masked from the gather that forms them (see mpn_backward); the one
+  float* part;
+  const float* d_a = wo_backward(c, m, g, wo_t, sign * ks, S, dH, G, accumulate, part);
+  // per-copy W_h layers (it >= 1): gradients arrive masked from the gather that forms them (see mp_backward); the one
   // that reaches the shared prefix stays unmasked - rr_gather_sum_masked_f32 masks it while summing over the copies
-  float* d_msg = c.alloc(g.nB, H);
-  {
-    const bool per_copy = depth - 2 >= 1;
-    gather_epi(c, d_a, g.nA, g.b2t, g.nB, 1, H, d_msg, st, part, rr_linear_colsum_rows(g.nA), per_copy, S.msgs[depth - 1],
-               S.bits[depth - 1], ks, nullptr, 0);
-  }
+  float* d_msg = gather_epi(c, d_a, g.nA, R.fwd_t, g.nB, R.Kt, H, part, depth - 2 >= 1, S.msgs[depth - 1], S.bits[depth - 1], ks,
+                            nullptr, 0);
   const float* fulls[RR_MAX_GATHER_SRCS];   // the per-copy layers' dZ, oldest first (counted, not pointer-tested: a layout pass
   int n_full = 0;                           // hands out null pointers)
   const bool multi = H % 4 == 0 && c.gather_multi;
   int wh_started = accumulate;
   for (int it = depth - 2; it >= 1; --it) {                                             // per-copy W_h layers
-    float* dz = d_msg;
-    float* d_min = c.alloc(g.nB, H);
-    float* partb = c.alloc(rr_linear_colsum_rows(g.nB), r4(H));
-    rr_linear_args a = LA(g.nB, H);
-    a.a1 = dz; a.lda1 = H; a.k1 = H; set_w(a, wh_t);
-    a.colsum_w = g.npad_b; a.colsum_partial = partb; a.ld_partial = r4(H);
-    a.c = d_min; a.ldc = H;
-    rr_wgrad_args w = WA(g.nB, H, dz, H, G.wh, H, G.bh, wh_started);
-    w.x1 = S.amsgs[it]; w.ldx1 = H; w.k1 = H; w.x1_idx = g.b2a; w.x1_sub = S.msgs[it]; w.ldx1_sub = H; w.x1_sub_idx = g.b2revb;
-    if (c.wgrad_early) wgrad(c, w);
-    lin(c, a, st);
-    if (!c.wgrad_early) wgrad(c, w);
+    const float* dz = d_msg;
+    rr_wgrad_args w = wh_wgrad_args(R, H, dz, S.amsgs[it], S.msgs[it], G.wh, G.bh, wh_started);
+    const float* d_min = wh_backward_dx(c, R, H, wh_t, dz, &w, part);
     wh_started = 1;
     // d input of a copy = the sum of these dZ; only its sum over the copies is needed (below).  Up to RR_MAX_GATHER_SRCS
     // addends ride on that gather (rr_gather_sum_multi_f32); beyond that - or with rows that are not whole 16-byte chunks -
@@ -802,9 +802,7 @@ void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr
         fulls[n_full - 1] = dz;
       }
     }
-    d_msg = c.alloc(g.nB, H);
-    gather_epi(c, d_min, g.nB, g.b2b_t, g.nB, g.Kb, H, d_msg, st, partb, rr_linear_colsum_rows(g.nB), it - 1 >= 1, S.msgs[it],
-               S.bits[it], ks, nullptr, 0);
+    d_msg = gather_epi(c, d_min, g.nB, R.back, g.nB, R.Kb, H, part, it - 1 >= 1, S.msgs[it], S.bits[it], ks, nullptr, 0);
   }
   // ---- shared prefix: msgs[1] = drop_copy(z1_u[bmap]),  z1_u = relu(inp_u + m_in0_u W_h^T + b_h)
   // dz1 of every copy is read once, by the sum over the copies: mask and gather in one pass (no [nB, H] round trip), the
@@ -818,8 +816,7 @@ void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr
   // weight-gradient stream's tail (this one, then W_i's) ends ~40 us earlier in front of the optimizer (same order among the
   // weight gradients, so the accumulation order - and every bit - is unchanged)
   {
-    rr_wgrad_args w = WA(gu.nB, H, dz1_u, H, G.wh, H, G.bh, wh_started);
-    w.x1 = S.a0_u; w.ldx1 = H; w.k1 = H; w.x1_idx = gu.b2a; w.x1_sub = S.msg0_u; w.ldx1_sub = H; w.x1_sub_idx = gu.b2revb;
+    rr_wgrad_args w = wh_wgrad_args(Ru, H, dz1_u, S.a0_u, S.msg0_u, G.wh, G.bh, wh_started);
     wgrad(c, w);
   }
   // d input of the distinct bonds = sum over the copies of the per-copy layers' dZ  +  dz1_u  +  relu'(msg0_u) (.) d msg0_u.
@@ -835,89 +832,48 @@ void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr
     adds[n_adds++] = over_copies;
   }
   adds[n_adds++] = dz1_u;
-  float* d_min_u = c.alloc(gu.nB, H);
-  float* part_u = c.alloc(rr_linear_colsum_rows(gu.nB), r4(H));
-  {
-    rr_linear_args a = LA(gu.nB, H);
-    a.a1 = dz1_u; a.lda1 = H; a.k1 = H; set_w(a, wh_t);
-    a.colsum_w = gu.npad_b; a.colsum_partial = part_u; a.ld_partial = r4(H);
-    a.c = d_min_u; a.ldc = H;
-    lin(c, a, st);
-  }
-  float* d_inp_u = c.alloc(gu.nB, H);
-  gather_epi(c, d_min_u, gu.nB, gu.b2b_t, gu.nB, gu.Kb, H, d_inp_u, st, part_u, rr_linear_colsum_rows(gu.nB), true, S.msg0_u, nullptr,
-             1.0f, adds, n_adds);                          // msg0 = relu(inp): no dropout, no sign-bit image
-  rr_wgrad_args w = WA(gu.nB, H, d_inp_u, H, G.wi, m.enc_wi.in, G.bi, accumulate);
-  w.x1 = gu.f_bonds; w.ldx1 = gu.ld_fb; w.k1 = m.bond_fdim;
-  wgrad(c, w, /*tail=*/true);
+  float* part_u;
+  const float* d_min_u = wh_backward_dx(c, Ru, H, wh_t, dz1_u, nullptr, part_u);
+  const float* d_inp_u = gather_epi(c, d_min_u, gu.nB, Ru.back, gu.nB, Ru.Kb, H, part_u, true, S.msg0_u, nullptr, 1.0f, adds,
+                                    n_adds);                   // msg0 = relu(inp): no dropout, no sign-bit image
+  wi_wgrad(c, m, gu, d_inp_u, G, accumulate);
 }
 
 // adjoint of mpndiff_forward -> d_x [nA, H]
-float* mpndiff_backward(Ctx& c, const rr_model& m, const rr_graph& g, float p, const DiffSaved& S, const float* x, const float* x_sub,
+float* mpndiff_backward(Ctx& c, const rr_model& m, const rr_graph& g, float p, const MpSaved& S, const float* x, const float* x_sub,
                         const int32_t* x_sub_idx, const float* dvecs, int64_t ld_dvecs, int F, uint64_t out_seed,
                         const rr_grads& G, const PackedT& T) {
-  const int H = m.H, depth = m.diff_depth, FB = m.bond_fdim;
+  const int H = m.H, depth = m.diff_depth;
   const float ks = 1.0f / (1.0f - p);
-  hipStream_t st = c.s.main;
+  const Operand feats = minus(x, nullptr, x_sub, x_sub_idx, H);
+  hipStream_t st = c.s.main;           // (= c.cur: the difference encoder's backward runs before the chains fork)
   float* d_hid = c.alloc(g.nA, H);
   float* d_x = nullptr;
   float* d_inp = nullptr;
   if (depth > 0) {
     // hid = drop(relu(.)): the readout's adjoint applies that pattern as it writes (dZ of W_o), so both column blocks
-    // of W_o read a plain operand; the message-passing iterations below follow mpn_backward
+    // of W_o read a plain operand; the message-passing iterations follow the encoder's (mp_backward)
     float* dz_o = d_hid;
-    RR_TRY(c, rr_segment_mean_bwd_masked_amax_f32(dvecs, ld_dvecs, g.a_scope, g.atom2mol, g.nA, H, F, p, out_seed, S.hid, H, S.bits_hid,
+    RR_TRY(c, rr_segment_mean_bwd_masked_amax_f32(dvecs, ld_dvecs, g.a_scope, g.atom2mol, g.nA, H, F, p, out_seed, S.out, H, S.bits_out,
                                                   ks, dz_o, H, amax_claim(c, dz_o), st));
-    const Packed wo_x = T.dif_wo_x, wo_a = T.dif_wo_a;
     d_x = c.alloc(g.nA, H);
     {
       rr_linear_args a = LA(g.nA, H);
-      a.a1 = dz_o; a.lda1 = H; a.k1 = H; set_w(a, wo_x); a.c = d_x; a.ldc = H;
+      set_a1(a, plain(dz_o, H, H)); set_w(a, T.dif_wo_x); a.c = d_x; a.ldc = H;
       lin(c, a, st);
     }
     {
       rr_wgrad_args w = WA(g.nA, H, dz_o, H, G.w[RR_G_DIF_WO], 2 * H, G.b[RR_G_DIF_WO], 0);
-      w.x1 = x; w.ldx1 = H; w.k1 = H; w.x1_sub = x_sub; w.ldx1_sub = H; w.x1_sub_idx = x_sub_idx;
-      w.x2 = S.a_last; w.ldx2 = H; w.k2 = H;
+      set_x1(w, feats); w.x2 = S.a_last; w.ldx2 = H; w.k2 = H;
       wgrad(c, w);
     }
     float* d_a = c.alloc(g.nA, H);
-    float* part = c.alloc(rr_linear_colsum_rows(g.nA), r4(H));
-    {
-      rr_linear_args a = LA(g.nA, H);
-      a.a1 = dz_o; a.lda1 = H; a.k1 = H;
-      set_w(a, wo_a); a.colsum_w = g.npad; a.colsum_partial = part; a.ld_partial = r4(H);
-      a.c = d_a; a.ldc = H;
-      lin(c, a, st);
-    }
-    const float* dzs[MAXD];
-    int ndz = 0;
-    float* cur = c.alloc(g.nA, H);
-    {
-      const int top = depth - 1;
-      gather_epi(c, d_a, g.nA, g.a2a_t, g.nA, g.K, H, cur, st, part, rr_linear_colsum_rows(g.nA), true, S.msgs[top], S.bits[top],
-                 top == 0 ? 1.0f : ks, nullptr, 0);
-    }
-    const Packed wh_t = T.dif_wh;
-    for (int it = depth - 2; it >= 0; --it) {
-      float* dz = cur;
-      float* d_a2 = c.alloc(g.nA, H);
-      float* part2 = c.alloc(rr_linear_colsum_rows(g.nA), r4(H));
-      rr_linear_args a = LA(g.nA, H);
-      a.a1 = dz; a.lda1 = H; a.k1 = H; set_w(a, wh_t);
-      a.colsum_w = g.npad; a.colsum_partial = part2; a.ld_partial = r4(H);
-      a.c = d_a2; a.ldc = H;
-      rr_wgrad_args w = WA(g.nA, H, dz, H, G.w[RR_G_DIF_WH], H + FB, G.b[RR_G_DIF_WH], it != depth - 2 ? 1 : 0);
-      w.x1 = S.amsgs[it]; w.ldx1 = H; w.k1 = H; w.x2 = g.fb_sum; w.ldx2 = g.ld_fbs; w.k2 = FB;
-      if (c.wgrad_early) wgrad(c, w);
-      lin(c, a, st);
-      if (!c.wgrad_early) wgrad(c, w);
-      dzs[ndz++] = dz;
-      cur = c.alloc(g.nA, H);
-      gather_epi(c, d_a2, g.nA, g.a2a_t, g.nA, g.K, H, cur, st, part2, rr_linear_colsum_rows(g.nA), true, S.msgs[it], S.bits[it],
-                 it == 0 ? 1.0f : ks, dzs, it == 0 ? ndz : 0);
-    }
-    d_inp = cur;
+    rr_linear_args a = LA(g.nA, H);
+    set_a1(a, plain(dz_o, H, H)); set_w(a, T.dif_wo_a);
+    const float* part = set_colsum(c, a, g.npad);
+    a.c = d_a; a.ldc = H;
+    lin(c, a, st);
+    d_inp = mp_backward(c, atoms(g, m.bond_fdim), H, depth, T.dif_wh, ks, S, d_a, part, G.w[RR_G_DIF_WH], G.b[RR_G_DIF_WH], 0);
   } else {
     RR_TRY(c, rr_segment_mean_bwd_f32(dvecs, ld_dvecs, g.a_scope, g.atom2mol, g.nA, H, F, p, out_seed, d_hid, H, st));
     d_inp = c.alloc(g.nA, H);
@@ -925,12 +881,11 @@ float* mpndiff_backward(Ctx& c, const rr_model& m, const rr_graph& g, float p, c
   }
   {
     rr_wgrad_args w = WA(g.nA, H, d_inp, H, G.w[RR_G_DIF_WI], H, G.b[RR_G_DIF_WI], 0);
-    w.x1 = x; w.ldx1 = H; w.k1 = H; w.x1_sub = x_sub; w.ldx1_sub = H; w.x1_sub_idx = x_sub_idx;
+    set_x1(w, feats);
     wgrad(c, w);
   }
-  const Packed wi_t = T.dif_wi;
   rr_linear_args a = LA(g.nA, H);
-  a.a1 = d_inp; a.lda1 = H; a.k1 = H; set_w(a, wi_t);
+  set_a1(a, plain(d_inp, H, H)); set_w(a, T.dif_wi);
   if (depth == 0) {
     d_x = c.alloc(g.nA, H);
   } else {
@@ -1038,7 +993,7 @@ void backward_all(Ctx& c, const rr_model& m, const rr_step& s, Plan& P, const fl
   int64_t ld_dvecs = 0;
   float* dvecs = ffn_backward(c, m, s.p.M, p, P.f, dout, G, T, &ld_dvecs);
   const int32_t* xsi = s.mode == RR_STEP_DEDUP ? s.amap : nullptr;
-  float* d_diff = mpndiff_backward(c, m, s.p, p, P.d, P.p.h, P.r.h, xsi, dvecs, ld_dvecs, s.F, site_seed(s.seed, 4), G, T);
+  float* d_diff = mpndiff_backward(c, m, s.p, p, P.d, P.p.out, P.r.out, xsi, dvecs, ld_dvecs, s.F, site_seed(s.seed, 4), G, T);
   // de-duplicated reactants: d r_h[u] = -(sum over the copies of atom u of d_diff) (fixed-order segment sum)
   const float* d_r = d_diff;
   if (s.mode == RR_STEP_DEDUP) {
@@ -1062,11 +1017,11 @@ void backward_all(Ctx& c, const rr_model& m, const rr_step& s, Plan& P, const fl
     amax_of(c, d_r, main);
   }
   if (c.launch && fork) c.fail(stream_wait(c.s.aux, main));
-  mpn_backward(c, m, s.p, P.pk, wh_t, wo_t, p, P.p, d_diff, 1.0f, E, 0);
+  mpn_backward(c, m, s.p, wh_t, wo_t, p, P.p, d_diff, 1.0f, E, 0);
   if (fork) c.cur = c.s.aux;
   c.tail_pass = !fork;
   if (s.mode == RR_STEP_PREFIX) mpn_backward_shared(c, m, s.u, s.r, s.bmap_t, s.bmap_t_cols, wh_t, wo_t, p, P.r, d_r, -1.0f, E, 1);
-  else mpn_backward(c, m, s.r, P.pk, wh_t, wo_t, p, P.r, d_r, -1.0f, E, 1);
+  else mpn_backward(c, m, s.r, wh_t, wo_t, p, P.r, d_r, -1.0f, E, 1);
   c.cur = main;
   c.tail_pass = false;
   if (c.launch && fork) c.fail(stream_wait(main, c.s.aux));
@@ -1120,21 +1075,13 @@ size_t rr_reaction_workspace_bytes(const rr_model* model, const rr_step* step) {
   if (check(model, step) != RR_OK) return 0;
   size_t need = 0;
   for (int v = 0; v < 6; ++v) {                        // every GEMM path (f32, three bf16 terms, two f16 terms), with or without RR_PLAN_TRAIN, must fit
-    Ctx c;
-    c.launch = false; c.status = RR_OK; c.ar.base = nullptr; c.ar.off = 0; c.ar.cap = 0; c.ar.overflow = false; c.npq = 0;
+    Ctx c = make_ctx(0, nullptr, 0, false);
     c.use_side = c.use_aux = false;
-    c.aux_bwd = false;
-    c.cur = nullptr;
-    c.s.main = c.s.side = c.s.aux = nullptr;
     c.split = (v >> 1) != 0;
     c.f16 = (v >> 1) == 2;
-    c.ntr = c.namax = 0; c.amax_base = nullptr;
     c.train = (v & 1) != 0;
     c.ffn_chain = true;
-    c.timing = false;
     c.gather_multi = false;             // (the layout with the pre-summed buffers: the larger one)
-    c.tail_pass = c.side_joined = false;
-    c.wgrad_early = false;
     Plan P;
     memset(&P, 0, sizeof(P));
     forward_all(c, *model, *step, P);
@@ -1150,21 +1097,7 @@ int rr_reaction_forward(const rr_model* model, const rr_step* step, int flags, r
   int st = check(model, step);
   if (st != RR_OK) return st;
   RR_CHECK_ARG(step->workspace && rr_aligned16(step->workspace));
-  Ctx c;
-  c.launch = true; c.status = RR_OK; c.npq = 0;
-  c.ar.base = static_cast<char*>(step->workspace); c.ar.off = 0; c.ar.cap = step->workspace_bytes; c.ar.overflow = false;
-  c.use_side = (flags & RR_PLAN_NO_SIDE_STREAM) == 0;
-  c.use_aux = (flags & RR_PLAN_NO_AUX_STREAM) == 0;
-  c.split = (flags & RR_PLAN_F32_GEMM) == 0;
-  c.f16 = c.split && (flags & RR_PLAN_F16X2_GEMM) != 0;
-  c.ntr = c.namax = 0; c.amax_base = nullptr;
-  c.aux_bwd = (flags & RR_PLAN_AUX_BACKWARD) != 0;
-  c.train = (flags & RR_PLAN_TRAIN) != 0;
-  c.ffn_chain = (flags & RR_PLAN_NO_FFN_CHAIN) == 0 && !getenv("RR_NO_FFN_CHAIN");
-  c.timing = (flags & RR_PLAN_TIME) != 0;
-  c.gather_multi = !getenv("RR_NO_GATHER_MULTI");
-  c.tail_pass = c.side_joined = false;
-  c.wgrad_early = (flags & RR_PLAN_WGRAD_EARLY) != 0 || getenv("RR_WGRAD_EARLY") != nullptr;
+  Ctx c = make_ctx(flags, step->workspace, step->workspace_bytes, true);
   st = get_streams(static_cast<hipStream_t>(stream), &c.s);
   if (st != RR_OK) return st;
   c.cur = c.s.main;
@@ -1193,21 +1126,7 @@ int rr_reaction_backward(const rr_model* model, const rr_step* step, const float
                           (i == RR_G_DIF_WO && model->diff_depth == 0));
     RR_CHECK_ARG(!needed || grads->w[i]);
   }
-  Ctx c;
-  c.launch = false; c.status = RR_OK; c.npq = 0;
-  c.ar.base = static_cast<char*>(step->workspace); c.ar.off = 0; c.ar.cap = step->workspace_bytes; c.ar.overflow = false;
-  c.use_side = (flags & RR_PLAN_NO_SIDE_STREAM) == 0;
-  c.use_aux = (flags & RR_PLAN_NO_AUX_STREAM) == 0;
-  c.split = (flags & RR_PLAN_F32_GEMM) == 0;
-  c.f16 = c.split && (flags & RR_PLAN_F16X2_GEMM) != 0;
-  c.ntr = c.namax = 0; c.amax_base = nullptr;
-  c.aux_bwd = (flags & RR_PLAN_AUX_BACKWARD) != 0;
-  c.train = (flags & RR_PLAN_TRAIN) != 0;
-  c.ffn_chain = (flags & RR_PLAN_NO_FFN_CHAIN) == 0 && !getenv("RR_NO_FFN_CHAIN");
-  c.timing = (flags & RR_PLAN_TIME) != 0;
-  c.gather_multi = !getenv("RR_NO_GATHER_MULTI");
-  c.tail_pass = c.side_joined = false;
-  c.wgrad_early = (flags & RR_PLAN_WGRAD_EARLY) != 0 || getenv("RR_WGRAD_EARLY") != nullptr;
+  Ctx c = make_ctx(flags, step->workspace, step->workspace_bytes, false);
   st = get_streams(static_cast<hipStream_t>(stream), &c.s);
   if (st != RR_OK) return st;
   c.cur = c.s.main;
@@ -1260,23 +1179,7 @@ int rr_reaction_saved_f32(const rr_model* model, const rr_step* step, int flags,
   int st = check(model, step);
   if (st != RR_OK) return st;
   RR_CHECK_ARG(step->workspace && ptr && rows && ld && index >= 0 && index < MAXD);
-  Ctx c;
-  c.launch = false; c.status = RR_OK; c.npq = 0;
-  c.ar.base = static_cast<char*>(step->workspace); c.ar.off = 0; c.ar.cap = step->workspace_bytes; c.ar.overflow = false;
-  c.use_side = (flags & RR_PLAN_NO_SIDE_STREAM) == 0;
-  c.use_aux = (flags & RR_PLAN_NO_AUX_STREAM) == 0;
-  c.split = (flags & RR_PLAN_F32_GEMM) == 0;
-  c.f16 = c.split && (flags & RR_PLAN_F16X2_GEMM) != 0;
-  c.ntr = c.namax = 0; c.amax_base = nullptr;
-  c.aux_bwd = (flags & RR_PLAN_AUX_BACKWARD) != 0;
-  c.train = (flags & RR_PLAN_TRAIN) != 0;
-  c.ffn_chain = (flags & RR_PLAN_NO_FFN_CHAIN) == 0 && !getenv("RR_NO_FFN_CHAIN");
-  c.timing = (flags & RR_PLAN_TIME) != 0;
-  c.gather_multi = !getenv("RR_NO_GATHER_MULTI");
-  c.tail_pass = c.side_joined = false;
-  c.wgrad_early = (flags & RR_PLAN_WGRAD_EARLY) != 0 || getenv("RR_WGRAD_EARLY") != nullptr;
-  c.s.main = c.s.side = c.s.aux = nullptr;
-  c.cur = nullptr;
+  Ctx c = make_ctx(flags, step->workspace, step->workspace_bytes, false);   // (null streams: layout pass only)
   Plan P;
   memset(&P, 0, sizeof(P));
   forward_all(c, *model, *step, P);                      // layout pass only
@@ -1286,11 +1189,11 @@ int rr_reaction_saved_f32(const rr_model* model, const rr_step* step, int flags,
   int64_t r = 0, l = H;
   switch (which) {
     case RR_SAVED_R_MSG: if (index < model->depth) { q = P.r.msgs[index]; r = step->r.nB; } break;
-    case RR_SAVED_R_H: q = P.r.h; r = step->r.nA; break;
+    case RR_SAVED_R_H: q = P.r.out; r = step->r.nA; break;
     case RR_SAVED_P_MSG: if (index < model->depth) { q = P.p.msgs[index]; r = step->p.nB; } break;
-    case RR_SAVED_P_H: q = P.p.h; r = step->p.nA; break;
+    case RR_SAVED_P_H: q = P.p.out; r = step->p.nA; break;
     case RR_SAVED_D_MSG: if (index < (model->diff_depth > 0 ? model->diff_depth : 1)) { q = P.d.msgs[index]; r = step->p.nA; } break;
-    case RR_SAVED_D_HID: q = P.d.hid; r = step->p.nA; break;
+    case RR_SAVED_D_HID: q = P.d.out; r = step->p.nA; break;
     case RR_SAVED_VECS: q = P.d.vecs; r = step->p.M; l = P.d.ld_vecs; break;
     case RR_SAVED_FFN_H: if (index >= 1 && index < model->n_ffn) { q = P.f.hs[index]; r = step->p.M; l = P.f.ld_hs[index]; } break;
     case RR_SAVED_R_MSG0_U: if (step->mode == RR_STEP_PREFIX) { q = P.r.msg0_u; r = step->u.nB; } break;

@@ -565,24 +565,59 @@ def _site_seed(seed: int, site: int) -> int:
     return (int(seed) * 0x9E3779B97F4A7C15 + site * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
 
 
+class _Rel:
+    """What a message-passing loop runs over: bond messages (reaction encoder; W_h reads a_msg[b2a] - msg[b2revb]) or atom
+    messages (difference encoder; W_h reads [a_msg | fb_sum]).  fwd: a_msg = sum of msg over it; fwd_t: that gather's adjoint;
+    back: the adjoint of gather + message formation as one table; npad: the pad row's weights in it."""
+
+    def __init__(self, g, H: int, bonds: bool, depth: int = 0):
+        self.nA, self.H, self.npad_a = g.nA, H, g.npad
+        if bonds:
+            self.rows, self.fwd, self.fwd_t, self.back, self.npad = g.nB, g.a2b, g.b2t, g.b2b_t, g.npad_b
+            self.idx, self.sub_idx, self.second, self.k2 = g.b2a, g.b2revb, None, 0
+        else:                                                        # (the neighbour relation is symmetric)
+            self.rows, self.fwd, self.fwd_t, self.back, self.npad = g.nA, g.a2a, g.a2a_t, g.a2a_t, g.npad
+            self.idx, self.sub_idx, self.second, self.k2 = None, None, (g.fb_sum() if depth > 1 else None), FBOND
+
+    def message(self, pre: str, a_msg, msg):
+        """W_h's input as keyword arguments of linear() (pre = "a") / wgrad() (pre = "x")."""
+        return {pre + "1": a_msg, "k1": self.H, pre + "1_idx": self.idx, pre + "1_sub": msg if self.idx is not None else None,
+                pre + "1_sub_idx": self.sub_idx, pre + "2": self.second, "k2": self.k2}
+
+    def wgrad(self, dz, a_msg, msg, gWh, gbh, accumulate: bool):
+        wgrad(self.rows, self.H, dz, gWh, dbias=gbh, accumulate=accumulate, side=True, **self.message("x", a_msg, msg))
+
+
+def _wh_forward(R: _Rel, Wh: LinW, msg, inp, p: float, seed: int, **kw):
+    """One W_h iteration (models/mpn.py:89-97, :201-213) -> (a_msg, drop(relu(inp + message W_h^T + b_h)))."""
+    a_msg = gather_sum(msg, R.fwd, R.H)                                                              # :89-90, :201
+    new = linear(R.rows, R.H, Wh.pk(R.H, R.k2), w_packed=True, bias=Wh.b, residual=inp, act=ACT_RELU, drop_p=p, seed=seed,
+                 **R.message("a", a_msg, msg), **kw)                                                 # :91-97, :202-213
+    return a_msg, new
+
+
+def _wo_forward(R: _Rel, Wo: LinW, first, k1: int, msg, p: float, seed: int, **sub):
+    """The W_o layer (models/mpn.py:101-105, :215-219) -> (a_last, drop(relu([first | a_last] W_o^T + b_o)))."""
+    a_last = gather_sum(msg, R.fwd, R.H)                                                             # :101-102, :215-216
+    out = linear(R.nA, R.H, Wo.pk(k1, R.H), w_packed=True, a1=first, k1=k1, a2=a_last, k2=R.H, bias=Wo.b, act=ACT_RELU, drop_p=p,
+                 seed=seed, want_bits=True, **sub)                                                   # :103-105, :217-219
+    return a_last, out
+
+
 def mpn_forward(g, H: int, depth: int, Wi: LinW, Wh: Optional[LinW], Wo: LinW, p: float, seed: int):
     """MPN.forward, return_atom_hiddens=True (models/mpn.py:61-108) -> (atom_hiddens [nA,H], saved)."""
-    nA, nB = g.nA, g.nB
-    inp = _new(g.f_bonds, nB, H)
-    msg = _new(g.f_bonds, nB, H)
-    linear(nB, H, Wi.pk(FBOND), w_packed=True, a1=g.f_bonds, k1=FBOND, bias=Wi.b, act=ACT_RELU, out=msg, c_pre=inp,
+    R = _Rel(g, H, bonds=True)
+    inp = _new(g.f_bonds, g.nB, H)
+    msg = _new(g.f_bonds, g.nB, H)
+    linear(g.nB, H, Wi.pk(FBOND), w_packed=True, a1=g.f_bonds, k1=FBOND, bias=Wi.b, act=ACT_RELU, out=msg, c_pre=inp,
            want_bits=True)                                                                           # :80-81
     msgs, amsgs = [msg], []
     for it in range(depth - 1):                                                                      # :84
-        a_msg = gather_sum(msgs[-1], g.a2b, H)                                                       # :89-90
-        new = linear(nB, H, Wh.pk(H), w_packed=True, a1=a_msg, k1=H, a1_idx=g.b2a, a1_sub=msgs[-1], a1_sub_idx=g.b2revb,
-                     bias=Wh.b, residual=inp, act=ACT_RELU, drop_p=p, seed=_site_seed(seed, it), want_bits=True)     # :91-97
+        a_msg, new = _wh_forward(R, Wh, msgs[-1], inp, p, _site_seed(seed, it), want_bits=True)
         amsgs.append(a_msg)
         msgs.append(new)
     del inp
-    a_last = gather_sum(msgs[-1], g.a2b, H)                                                          # :101-102
-    h = linear(nA, H, Wo.pk(ATOM_FDIM, H), w_packed=True, a1=g.f_atoms, k1=ATOM_FDIM, a2=a_last, k2=H, bias=Wo.b, act=ACT_RELU, drop_p=p,
-               seed=_site_seed(seed, 1000), want_bits=True)                                                          # :103-105
+    a_last, h = _wo_forward(R, Wo, g.f_atoms, ATOM_FDIM, msgs[-1], p, _site_seed(seed, 1000))
     return h, (msgs, amsgs, a_last, h)
 
 
@@ -599,81 +634,89 @@ def bond_message_adjoint(d_min, g, H: int, partial=None, *, mask=None, mask_scal
     return d_msg
 
 
-def _pad_row_fix(d_src, d_out, g, H):
-    """Row 0 of every gathered source is read npad[a] times by atom a (a2b is right-padded with
-    bond/atom 0, features/featurization.py:286): add sum_a npad[a] * d_out[a] to d_src[0]."""
-    weighted_colsum(d_out, g.npad, H, d_src[0], accumulate=True)
+def _enc_grads(Wi: LinW, Wh: Optional[LinW], Wo: Optional[LinW], into=None):
+    """Gradient buffers of an encoder pass: `into` (they already hold the OTHER pass - the two share weights - and this
+    one accumulates instead of returning fresh buffers that would have to be added afterwards) or fresh ones."""
+    if into is not None:
+        return into
+    (gWi, gbi), (gWh, gbh), (gWo, gbo) = [(W.grads() if W is not None else (None, None)) for W in (Wi, Wh, Wo)]
+    return gWi, gbi, gWh, gbh, gWo, gbo
+
+
+def _wo_backward(g, H: int, Wo: LinW, h, a_last, dH, scale: float, gWo, gbo, acc0: bool):
+    """Fused W_o layer of the encoder, atom_hiddens = drop(relu([f_atoms | a_last] W_o^T + b_o)): the input-gradient GEMM applies
+    the ReLU/dropout mask in its operand loader (dH has two consumers with different masks - the product and the reactant encoder)
+    and writes the masked gradient dZ as a side output; the weight-gradient GEMM (other stream) streams dZ as is.
+    -> (d a_last, the padding row's adjoint sum_a npad[a] * d_a[a] as per-row-block partial sums (colsum_w))."""
+    dz_o = torch.empty_like(dH)
+    d_a, part = linear(g.nA, H, Wo.pk_t(ATOM_FDIM, ATOM_FDIM + H), w_packed=True, a1=dH, k1=H, a_mask=h, mask_scale=scale,
+                       dz_out=dz_o, colsum_w=g.npad)
+    wgrad(g.nA, H, dz_o, gWo, dbias=gbo, x1=g.f_atoms, k1=ATOM_FDIM, x2=a_last, k2=H, accumulate=acc0, side=True)
+    return d_a, part
+
+
+def _mp_backward(R: _Rel, depth: int, Wh, ks: float, msgs, amsgs, d_a, part, gWh, gbh, acc0: bool):
+    """Fused message-passing backward, d a_last -> d input.  a_last[a] = sum_k msg[fwd[a,k]]  ->  d_msg = gather of d_a over
+    fwd_t.  Every gradient that reaches a layer is produced ALREADY masked by that layer's ReLU / dropout pattern: the gather
+    that forms d message applies (y > 0) / (1 - p) of the layer below in its epilogue, so dZ is the gather's output (the dX
+    GEMM reads a plain operand, the weight gradient streams it as is), and the last gather also adds every iteration's dZ."""
+    H, top = R.H, depth - 1
+    cur = gather_sum(d_a, R.fwd_t, H, row0_partial=part, mask=msgs[top], mask_scale=(1.0 if top == 0 else ks))
+    dzs = []
+    for it in reversed(range(depth - 1)):
+        dz = cur
+        d_min, part = linear(R.rows, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H, colsum_w=R.npad)
+        R.wgrad(dz, amsgs[it], msgs[it], gWh, gbh, acc0 or it != depth - 2)
+        dzs.append(dz)
+        cur = gather_sum(d_min, R.back, H, row0_partial=part, mask=msgs[it], mask_scale=(1.0 if it == 0 else ks),
+                         adds=(dzs if it == 0 else ()))
+    return cur                                                       # sum_it dZ_it + relu'(inp) * d msgs[0]  (:94)
+
+
+def _mp_backward_unfused(R: _Rel, depth: int, Wh, ks: float, msgs, amsgs, d_a, gWh, gbh, acc0: bool):
+    """H % 4 != 0: separate ReLU-backward passes, d a_last -> d input.  dz is read by the weight-gradient stream, so
+    every iteration gets a fresh buffer and d_inp accumulates in a buffer that stream never reads before the final W_i launch
+    (which is ordered after all main-stream writes)."""
+    H = R.H
+    # row 0 of every gathered source is read npad[a] times by atom a (a2b is right-padded with bond/atom 0,
+    # features/featurization.py:286): its adjoint is the weighted column sum over the gather's output gradient
+    d_msg = gather_sum(d_a, R.fwd_t, H)
+    weighted_colsum(d_a, R.npad_a, H, d_msg[0], accumulate=True)
+    d_inp = None
+    for it in reversed(range(depth - 1)):
+        # msgs[it+1] = drop(relu(inp + m_in W_h^T + b_h)),  m_in = the relation's message of (amsgs[it], msgs[it])
+        if d_inp is None:
+            d_inp = torch.zeros_like(d_msg)
+        dz = relu_bwd(d_msg, msgs[it + 1], ks, dz=torch.empty_like(d_msg), acc=d_inp)
+        R.wgrad(dz, amsgs[it], msgs[it], gWh, gbh, acc0 or it != depth - 2)
+        d_min = linear(R.rows, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H)
+        d_msg = gather_sum(d_min, R.back, H)                         # fresh buffer (side-stream readers)
+        weighted_colsum(d_min, R.npad, H, d_msg[0], accumulate=True)   # the padding row's adjoint (see bond_message_adjoint)
+    # msgs[0] = relu(inp);  d inp = sum_it dZ_it + relu'(inp) * d msgs[0]   (inp is the residual of every iteration, :94)
+    if d_inp is None:
+        return relu_bwd(d_msg, msgs[0], 1.0)
+    relu_bwd(d_msg, msgs[0], 1.0, acc=d_inp, want_dz=False)
+    return d_inp
 
 
 def mpn_backward(g, H: int, depth: int, Wi: LinW, Wh: Optional[LinW], Wo: LinW, p: float, saved, dH, sign: float, into=None):
     """Adjoint of mpn_forward.  `dH` is d loss / d atom_hiddens times `sign` (the reactant encoder
     sees -d_diff, models/base_model.py:168).  Returns grads (gWi, gbi, gWh, gbh, gWo, gbo).
-    into: gradient buffers that already hold the OTHER encoder pass (the two passes share weights): this pass
-    accumulates into them instead of returning fresh buffers that would have to be added afterwards."""
+    into: gradient buffers that already hold the OTHER encoder pass (see _enc_grads)."""
     msgs, amsgs, a_last, h = saved
-    nA, nB = g.nA, g.nB
+    R = _Rel(g, H, bonds=True)
     ks = 1.0 / (1.0 - p)
     acc0 = into is not None
-    if acc0:
-        gWi, gbi, gWh, gbh, gWo, gbo = into
+    gWi, gbi, gWh, gbh, gWo, gbo = _enc_grads(Wi, Wh, Wo, into)
+    if H % 4 == 0:                                                   # ReLU backward fused into producers / operand loads
+        d_a, part = _wo_backward(g, H, Wo, h, a_last, dH, sign * ks, gWo, gbo, acc0)
+        d_inp = _mp_backward(R, depth, Wh, ks, msgs, amsgs, d_a, part, gWh, gbh, acc0)
     else:
-        gWi, gbi = Wi.grads()
-        gWo, gbo = Wo.grads()
-        gWh, gbh = (Wh.grads() if Wh is not None else (None, None))
-    # atom_hiddens = drop(relu([f_atoms | a_last] W_o^T + b_o))
-    fused = (H % 4 == 0)                                             # ReLU backward fused into producers / operand loads
-    # Fused form, W_o layer: the input-gradient GEMM applies the ReLU/dropout mask in its operand loader (dH has two
-    # consumers with different masks - the product and the reactant encoder) and writes the masked gradient dZ as a side
-    # output; the weight-gradient GEMM (other stream) streams dZ as is.
-    if fused:
-        dz_o = torch.empty_like(dH)
-        # ... and the padding row's adjoint sum_a npad[a] * d_a[a] as per-row-block partial sums (colsum_w)
-        d_a, part = linear(nA, H, Wo.pk_t(ATOM_FDIM, ATOM_FDIM + H), w_packed=True, a1=dH, k1=H, a_mask=h,
-                           mask_scale=sign * ks, dz_out=dz_o, colsum_w=g.npad)
-        wgrad(nA, H, dz_o, gWo, dbias=gbo, x1=g.f_atoms, k1=ATOM_FDIM, x2=a_last, k2=H, accumulate=acc0, side=True)
-        # a_last[a] = sum_k msg[a2b[a,k]]  ->  d_msg[b] = d_a[target(b)].  From here on every gradient that reaches a layer
-        # is produced ALREADY masked by that layer's ReLU / dropout pattern: the gather that forms d message applies
-        # (y > 0) / (1 - p) of the layer below in its epilogue, so dZ is the gather's output (the dX GEMM reads a plain
-        # operand, the weight gradient streams it as is), and the last gather also adds every iteration's dZ -> d input.
-        top = depth - 1
-        cur = gather_sum(d_a, g.b2t, H, row0_partial=part, mask=msgs[top], mask_scale=(1.0 if top == 0 else ks))
-        dzs = []
-        for it in reversed(range(depth - 1)):
-            dz = cur
-            d_min, part = linear(nB, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H, colsum_w=g.npad_b)
-            wgrad(nB, H, dz, gWh, dbias=gbh, x1=amsgs[it], k1=H, x1_idx=g.b2a, x1_sub=msgs[it], x1_sub_idx=g.b2revb,
-                  accumulate=(acc0 or it != depth - 2), side=True)
-            dzs.append(dz)
-            cur = bond_message_adjoint(d_min, g, H, part, mask=msgs[it], mask_scale=(1.0 if it == 0 else ks),
-                                       adds=(dzs if it == 0 else ()))
-        d_inp = cur                                                  # sum_it dZ_it + relu'(inp) * d msgs[0]  (:94)
-        wgrad(nB, H, d_inp, gWi, dbias=gbi, x1=g.f_bonds, k1=FBOND, accumulate=acc0, side=True)
-        return gWi, gbi, gWh, gbh, gWo, gbo
-    else:
-        wgrad(nA, H, dH, gWo, dbias=gbo, mask=h, mask_scale=sign * ks, x1=g.f_atoms, k1=ATOM_FDIM, x2=a_last, k2=H,
+        wgrad(g.nA, H, dH, gWo, dbias=gbo, mask=h, mask_scale=sign * ks, x1=g.f_atoms, k1=ATOM_FDIM, x2=a_last, k2=H,
               accumulate=acc0, side=True)
-        d_a = linear(nA, H, Wo.pk_t(ATOM_FDIM, ATOM_FDIM + H), w_packed=True, a1=dH, k1=H, a_mask=h, mask_scale=sign * ks)
-        d_msg = gather_sum(d_a, g.b2t, H)
-        _pad_row_fix(d_msg, d_a, g, H)
-    # H % 4 != 0: separate ReLU-backward passes.  dz is read by the weight-gradient stream, so every iteration gets a fresh
-    # buffer and d_inp accumulates in a buffer that stream never reads before the final W_i launch (which is ordered
-    # after all main-stream writes).
-    d_inp = None
-    for it in reversed(range(depth - 1)):
-        # msgs[it+1] = drop(relu(inp + m_in W_h^T + b_h)),  m_in = amsgs[it][b2a] - msgs[it][b2revb]
-        if d_inp is None:
-            d_inp = torch.zeros_like(d_msg)
-        dz = relu_bwd(d_msg, msgs[it + 1], ks, dz=torch.empty_like(d_msg), acc=d_inp)
-        wgrad(nB, H, dz, gWh, dbias=gbh, x1=amsgs[it], k1=H, x1_idx=g.b2a, x1_sub=msgs[it],
-              x1_sub_idx=g.b2revb, accumulate=(acc0 or it != depth - 2), side=True)
-        d_min = linear(nB, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H)
-        d_msg = bond_message_adjoint(d_min, g, H)
-    # msgs[0] = relu(inp);  d inp = sum_it dZ_it + relu'(inp) * d msgs[0]   (inp is the residual of every iteration, :94)
-    if d_inp is None:
-        d_inp = relu_bwd(d_msg, msgs[0], 1.0)
-    else:
-        relu_bwd(d_msg, msgs[0], 1.0, acc=d_inp, want_dz=False)
-    wgrad(nB, H, d_inp, gWi, dbias=gbi, x1=g.f_bonds, k1=FBOND, accumulate=acc0, side=True)
+        d_a = linear(g.nA, H, Wo.pk_t(ATOM_FDIM, ATOM_FDIM + H), w_packed=True, a1=dH, k1=H, a_mask=h, mask_scale=sign * ks)
+        d_inp = _mp_backward_unfused(R, depth, Wh, ks, msgs, amsgs, d_a, gWh, gbh, acc0)
+    wgrad(g.nB, H, d_inp, gWi, dbias=gbi, x1=g.f_bonds, k1=FBOND, accumulate=acc0, side=True)
     return gWi, gbi, gWh, gbh, gWo, gbo
 
 
@@ -684,25 +727,19 @@ def mpn_forward_shared(gu, g, bmap, H: int, depth: int, Wi: LinW, Wh: LinW, Wo: 
     runs once per distinct molecule (graph `gu`) and is expanded with each copy's own dropout mask
     (`bmap`: full bond row -> distinct bond row).  The mask stream and indices are those of the
     plain path, so results are the same numbers.  Needs depth >= 2."""
-    nA, nB, nBu = g.nA, g.nB, gu.nB
-    inp_u = _new(gu.f_bonds, nBu, H)
-    msg0_u = _new(gu.f_bonds, nBu, H)
-    linear(nBu, H, Wi.pk(FBOND), w_packed=True, a1=gu.f_bonds, k1=FBOND, bias=Wi.b, act=ACT_RELU, out=msg0_u, c_pre=inp_u)
-    a0_u = gather_sum(msg0_u, gu.a2b, H)
-    z1_u = linear(nBu, H, Wh.pk(H), w_packed=True, a1=a0_u, k1=H, a1_idx=gu.b2a, a1_sub=msg0_u, a1_sub_idx=gu.b2revb,
-                  bias=Wh.b, residual=inp_u, act=ACT_RELU)                          # pre-dropout, shared
+    R, Ru = _Rel(g, H, bonds=True), _Rel(gu, H, bonds=True)
+    inp_u = _new(gu.f_bonds, gu.nB, H)
+    msg0_u = _new(gu.f_bonds, gu.nB, H)
+    linear(gu.nB, H, Wi.pk(FBOND), w_packed=True, a1=gu.f_bonds, k1=FBOND, bias=Wi.b, act=ACT_RELU, out=msg0_u, c_pre=inp_u)
+    a0_u, z1_u = _wh_forward(Ru, Wh, msg0_u, inp_u, 0.0, 0)                          # pre-dropout, shared
     msgs = [None, gather_dropout(z1_u, bmap, H, p, _site_seed(seed, 0))]             # per-copy masks (:97)
     amsgs = [None]
     for it in range(1, depth - 1):
-        a_msg = gather_sum(msgs[-1], g.a2b, H)
-        new = linear(nB, H, Wh.pk(H), w_packed=True, a1=a_msg, k1=H, a1_idx=g.b2a, a1_sub=msgs[-1], a1_sub_idx=g.b2revb,
-                     bias=Wh.b, residual=inp_u, residual_idx=bmap, act=ACT_RELU, drop_p=p, seed=_site_seed(seed, it), want_bits=True)
+        a_msg, new = _wh_forward(R, Wh, msgs[-1], inp_u, p, _site_seed(seed, it), residual_idx=bmap, want_bits=True)
         amsgs.append(a_msg)
         msgs.append(new)
     del inp_u
-    a_last = gather_sum(msgs[-1], g.a2b, H)
-    h = linear(nA, H, Wo.pk(ATOM_FDIM, H), w_packed=True, a1=g.f_atoms, k1=ATOM_FDIM, a2=a_last, k2=H, bias=Wo.b,
-               act=ACT_RELU, drop_p=p, seed=_site_seed(seed, 1000), want_bits=True)
+    a_last, h = _wo_forward(R, Wo, g.f_atoms, ATOM_FDIM, msgs[-1], p, _site_seed(seed, 1000))
     return h, (msgs, amsgs, a_last, h, (msg0_u, a0_u, z1_u, _site_seed(seed, 0)))
 
 
@@ -713,20 +750,12 @@ def mpn_backward_shared(gu, g, bmap_t, H: int, depth: int, Wi: LinW, Wh: LinW, W
     back-propagated once on the distinct molecules — every op there is linear in the gradient, so the sum
     commutes with it."""
     msgs, amsgs, a_last, h, (msg0_u, a0_u, z1_u, seed0) = saved
-    nA, nB, nBu = g.nA, g.nB, gu.nB
+    R, Ru = _Rel(g, H, bonds=True), _Rel(gu, H, bonds=True)
     ks = 1.0 / (1.0 - p)
     acc0 = into is not None                                          # see mpn_backward
-    if acc0:
-        gWi, gbi, gWh, gbh, gWo, gbo = into
-    else:
-        gWi, gbi = Wi.grads()
-        gWo, gbo = Wo.grads()
-        gWh, gbh = Wh.grads()
-    dz_o = torch.empty_like(dH)                                      # masked gradient as a side output (see mpn_backward)
-    d_a, part = linear(nA, H, Wo.pk_t(ATOM_FDIM, ATOM_FDIM + H), w_packed=True, a1=dH, k1=H, a_mask=h, mask_scale=sign * ks,
-                       dz_out=dz_o, colsum_w=g.npad)
-    wgrad(nA, H, dz_o, gWo, dbias=gbo, x1=g.f_atoms, k1=ATOM_FDIM, x2=a_last, k2=H, accumulate=acc0, side=True)
-    # per-copy W_h layers (it >= 1): gradients arrive masked from the gather that forms them (see mpn_backward); the one that
+    gWi, gbi, gWh, gbh, gWo, gbo = _enc_grads(Wi, Wh, Wo, into)
+    d_a, part = _wo_backward(g, H, Wo, h, a_last, dH, sign * ks, gWo, gbo, acc0)
+    # per-copy W_h layers (it >= 1): gradients arrive masked from the gather that forms them (see _mp_backward); the one that
     # reaches the shared prefix stays unmasked - gather_sum_masked masks it while summing over the copies
     per_copy = depth - 2 >= 1
     d_msg = gather_sum(d_a, g.b2t, H, row0_partial=part, mask=(msgs[depth - 1] if per_copy else None), mask_scale=ks)
@@ -734,9 +763,8 @@ def mpn_backward_shared(gu, g, bmap_t, H: int, depth: int, Wi: LinW, Wh: LinW, W
     wh_started = acc0
     for it in reversed(range(1, depth - 1)):                         # per-copy W_h layers
         dz = d_msg
-        d_min, part = linear(nB, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H, colsum_w=g.npad_b)
-        wgrad(nB, H, dz, gWh, dbias=gbh, x1=amsgs[it], k1=H, x1_idx=g.b2a, x1_sub=msgs[it], x1_sub_idx=g.b2revb,
-              accumulate=wh_started, side=True)
+        d_min, part = linear(g.nB, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H, colsum_w=g.npad_b)
+        R.wgrad(dz, amsgs[it], msgs[it], gWh, gbh, wh_started)
         wh_started = True
         fulls.append(dz)
         d_msg = bond_message_adjoint(d_min, g, H, part, mask=(msgs[it] if it - 1 >= 1 else None), mask_scale=ks)
@@ -750,11 +778,10 @@ def mpn_backward_shared(gu, g, bmap_t, H: int, depth: int, Wi: LinW, Wh: LinW, W
     # d input of the distinct bonds = (the per-copy layers' dZ summed over layers and copies) + dz1_u + relu'(msg0_u) * d msg0_u:
     # the last two ride on the epilogue of the gather that forms d msg0_u (addends in this order, the masked gather last)
     adds = ([gather_sum_multi(fulls, bmap_t, H)] if fulls else []) + [dz1_u]
-    wgrad(nBu, H, dz1_u, gWh, dbias=gbh, x1=a0_u, k1=H, x1_idx=gu.b2a, x1_sub=msg0_u, x1_sub_idx=gu.b2revb,
-          accumulate=wh_started, side=True)
-    d_min_u, part_u = linear(nBu, H, Wh.pk_t(0, H), w_packed=True, a1=dz1_u, k1=H, colsum_w=gu.npad_b)
+    Ru.wgrad(dz1_u, a0_u, msg0_u, gWh, gbh, wh_started)
+    d_min_u, part_u = linear(gu.nB, H, Wh.pk_t(0, H), w_packed=True, a1=dz1_u, k1=H, colsum_w=gu.npad_b)
     d_inp_u = bond_message_adjoint(d_min_u, gu, H, part_u, mask=msg0_u, mask_scale=1.0, adds=adds)   # msg0 = relu(inp)
-    wgrad(nBu, H, d_inp_u, gWi, dbias=gbi, x1=gu.f_bonds, k1=FBOND, accumulate=acc0, side=True)
+    wgrad(gu.nB, H, d_inp_u, gWi, dbias=gbi, x1=gu.f_bonds, k1=FBOND, accumulate=acc0, side=True)
     return gWi, gbi, gWh, gbh, gWo, gbo
 
 
@@ -773,17 +800,12 @@ def mpndiff_forward(g, H: int, depth: int, Wi: LinW, Wh: Optional[LinW], Wo: Opt
     msgs, amsgs = [msg], []
     a_last = None
     if depth > 0:
-        fb = g.fb_sum() if depth > 1 else None
+        R = _Rel(g, H, bonds=False, depth=depth)
         for it in range(depth - 1):                                                      # :199
-            a_msg = gather_sum(msgs[-1], g.a2a, H)                                       # :201
-            new = linear(nA, H, Wh.pk(H, FBOND), w_packed=True, a1=a_msg, k1=H, a2=fb, k2=FBOND, bias=Wh.b, residual=inp, act=ACT_RELU,
-                         drop_p=p, seed=_site_seed(seed, 2001 + it), want_bits=True)     # :202-213
+            a_msg, new = _wh_forward(R, Wh, msgs[-1], inp, p, _site_seed(seed, 2001 + it), want_bits=True)
             amsgs.append(a_msg)
             msgs.append(new)
-        a_last = gather_sum(msgs[-1], g.a2a, H)                                          # :215-216
-        hid = linear(nA, H, Wo.pk(Hin, H), w_packed=True, a1=x, k1=Hin, a1_sub=x_sub, a1_sub_idx=x_sub_idx, a2=a_last, k2=H,
-                     bias=Wo.b, act=ACT_RELU, drop_p=p,
-                     seed=_site_seed(seed, 3000), want_bits=True)                        # :217-219
+        a_last, hid = _wo_forward(R, Wo, x, Hin, msgs[-1], p, _site_seed(seed, 3000), a1_sub=x_sub, a1_sub_idx=x_sub_idx)
     else:
         hid = msg
     del inp
@@ -798,52 +820,24 @@ def mpndiff_backward(g, H: int, depth: int, Wi: LinW, Wh, Wo, p: float, saved, x
     nA = g.nA
     Hin = x.shape[1]
     ks = 1.0 / (1.0 - p)
-    gWi, gbi = Wi.grads()
-    gWh, gbh = (Wh.grads() if Wh is not None else (None, None))
-    gWo, gbo = (Wo.grads() if Wo is not None else (None, None))
+    gWi, gbi, gWh, gbh, gWo, gbo = _enc_grads(Wi, Wh, Wo)
+    R = _Rel(g, H, bonds=False, depth=depth)
     d_x = None
-    fused = depth > 0 and H % 4 == 0
-    if fused:
+    if depth > 0 and H % 4 == 0:
         # hid = drop(relu(.)): the readout's adjoint applies that pattern as it writes (dZ of W_o), so the dX GEMMs over both
-        # column segments of W_o ([d_x | d_a]) read a plain operand; the iterations below follow mpn_backward's fused form
+        # column segments of W_o ([d_x | d_a]) read a plain operand; the iterations follow the encoder's fused form
         dz_o = segment_mean_bwd(dvecs, g, H, F, out_drop_p, out_seed, mask=hid, mask_scale=ks)
         d_x = linear(nA, Hin, Wo.pk_t(0, Hin), w_packed=True, a1=dz_o, k1=H)
         wgrad(nA, H, dz_o, gWo, dbias=gbo, x1=x, k1=Hin, x1_sub=x_sub, x1_sub_idx=x_sub_idx, x2=a_last, k2=H, side=True)
         d_a, part = linear(nA, H, Wo.pk_t(Hin, Hin + H), w_packed=True, a1=dz_o, k1=H, colsum_w=g.npad)
-        top = depth - 1
-        cur = gather_sum(d_a, g.a2a_t, H, row0_partial=part, mask=msgs[top], mask_scale=(1.0 if top == 0 else ks))  # neighbour relation is symmetric
-        dzs = []
-        fb = g.fb_sum() if depth > 1 else None
-        for it in reversed(range(depth - 1)):
-            dz = cur
-            d_a, part = linear(nA, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H, colsum_w=g.npad)
-            wgrad(nA, H, dz, gWh, dbias=gbh, x1=amsgs[it], k1=H, x2=fb, k2=FBOND, accumulate=(it != depth - 2), side=True)
-            dzs.append(dz)
-            cur = gather_sum(d_a, g.a2a_t, H, row0_partial=part, mask=msgs[it], mask_scale=(1.0 if it == 0 else ks),
-                             adds=(dzs if it == 0 else ()))
-        d_inp = cur
+        d_inp = _mp_backward(R, depth, Wh, ks, msgs, amsgs, d_a, part, gWh, gbh, False)
     elif depth > 0:
         d_hid = segment_mean_bwd(dvecs, g, H, F, out_drop_p, out_seed)                    # [nA,H]
         wgrad(nA, H, d_hid, gWo, dbias=gbo, mask=hid, mask_scale=ks, x1=x, k1=Hin, x1_sub=x_sub, x1_sub_idx=x_sub_idx,
               x2=a_last, k2=H, side=True)
         d_x = linear(nA, Hin, Wo.pk_t(0, Hin), w_packed=True, a1=d_hid, k1=H, a_mask=hid, mask_scale=ks)
         d_a = linear(nA, H, Wo.pk_t(Hin, Hin + H), w_packed=True, a1=d_hid, k1=H, a_mask=hid, mask_scale=ks)
-        d_msg = gather_sum(d_a, g.a2a_t, H)
-        _pad_row_fix(d_msg, d_a, g, H)
-        d_inp = None
-        fb = g.fb_sum() if depth > 1 else None
-        for it in reversed(range(depth - 1)):
-            if d_inp is None:                                        # see mpn_backward: fresh dz per iteration
-                d_inp = torch.zeros_like(d_msg)
-            dz = relu_bwd(d_msg, msgs[it + 1], ks, dz=torch.empty_like(d_msg), acc=d_inp)
-            wgrad(nA, H, dz, gWh, dbias=gbh, x1=amsgs[it], k1=H, x2=fb, k2=FBOND, accumulate=(it != depth - 2), side=True)
-            d_a = linear(nA, H, Wh.pk_t(0, H), w_packed=True, a1=dz, k1=H)
-            d_msg = gather_sum(d_a, g.a2a_t, H)                     # fresh buffer (side-stream readers)
-            _pad_row_fix(d_msg, d_a, g, H)
-        if d_inp is None:
-            d_inp = relu_bwd(d_msg, msgs[0], 1.0)
-        else:
-            relu_bwd(d_msg, msgs[0], 1.0, acc=d_inp, want_dz=False)
+        d_inp = _mp_backward_unfused(R, depth, Wh, ks, msgs, amsgs, d_a, gWh, gbh, False)
     else:
         d_hid = segment_mean_bwd(dvecs, g, H, F, out_drop_p, out_seed)                    # [nA,H]
         d_inp = relu_bwd(d_hid, msgs[0], ks)                        # hid = drop(relu(inp))
