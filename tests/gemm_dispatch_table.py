@@ -1,9 +1,9 @@
-"""The kernel instantiations the split-GEMM dispatchers of reactranker_amd/csrc/linear.hip can reach, written out by hand,
+"""The kernel instantiations the split-GEMM dispatchers of reactranker_amd/csrc (linear_split.hip, wgrad.hip) can reach, by hand,
 and a pure-Python restatement of the rules that pick one (no GPU, no library needed: tests/test_gemm_dispatch_table_cpu.py
 holds the tables against the sources, tests/test_gpu_gemm_dispatch.py runs every entry against f64).
 
-Rules restated (linear.hip):
-  rr_linear_f32, w_packed = 2 / 3 block: the geometry <NTP, NT, WAVES> by N and M
+Rules restated (linear_split.hip; the last one wgrad.hip):
+  launch_split_geometry (rr_linear_f32 with w_packed = 2 / 3): the geometry <NTP, NT, WAVES> by N and M
       N <= 64 -> <4,4,8>;  N <= 160 -> <10,10,8>;  N <= 304 and M <= 8192 -> <19,5,8>;  N <= 304 -> <19,19,12>;  else <38,19,12>
   launch_split: MODE 3 (a_mask_bits) before 2 (a_mask) before 1 (a1_sub) before 0
   launch_split_one: the 12-wave geometry, MODE 0 / 1 only - EPI 1 / 3 with a residual (RR_EPI_MODE 1), EPI 2 / 3 when a

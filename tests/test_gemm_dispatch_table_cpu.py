@@ -1,16 +1,16 @@
 """Drift guard: the split-GEMM instantiations that tests/gemm_dispatch_table.py lists (and tests/test_gpu_gemm_dispatch.py
-runs against f64) are the ones reactranker_amd/csrc/linear.hip launches.  A new geometry, mode or epilogue variant in the
-dispatcher fails here until the table - and with it the GPU sweep - covers it."""
+runs against f64) are the ones reactranker_amd/csrc/linear_split.hip and wgrad.hip launch.  A new geometry, mode or
+epilogue variant in the dispatchers fails here until the table - and with it the GPU sweep - covers it."""
 import os
 import re
 
 from tests import gemm_dispatch_table as T
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reactranker_amd", "csrc", "linear.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "reactranker_amd", "csrc")
 
 
-def _source():
-    with open(SRC) as f:
+def _source(name):
+    with open(os.path.join(CSRC, name)) as f:
         return f.read()
 
 
@@ -26,23 +26,25 @@ def _block(text, start):
     raise AssertionError(f"unbalanced block after {start!r}")
 
 
-def _geometries(block, f16):
-    suffix = r",\s*true" if f16 else ""
-    found = re.findall(r"launch_split<(\d+),\s*(\d+),\s*(\d+)" + suffix + r">\(P,\s*s\)", block)
-    assert found, "no launch_split<...> call found"
-    return [tuple(int(v) for v in g) for g in found]
-
-
 def test_split_geometries_are_the_table_s():
-    text = _source()
-    fn = _block(text, "int rr_linear_f32(")
-    for wp, f16 in ((2, False), (3, True)):
-        blk = _block(fn, f"if (a.w_packed == {wp})")
-        assert _geometries(blk, f16) == T.GEOMETRIES, (wp, _geometries(blk, f16))
+    # one ladder, a template over the arithmetic form; both forms (w_packed = 2: three bf16 terms, 3: two f16 terms) take it
+    text = _source("linear_split.hip")
+    ladder = _block(text, "int launch_split_geometry(")
+    assert re.search(r"template <bool F16>\s*int launch_split_geometry\(", text)
+    found = re.findall(r"launch_split<(\d+),\s*(\d+),\s*(\d+),\s*F16>\(P,\s*s\)", ladder)
+    assert [tuple(int(v) for v in g) for g in found] == T.GEOMETRIES, found
+    assert len(re.findall(r"launch_split<", ladder)) == len(T.GEOMETRIES)
+    assert len(re.findall(r"launch_split<\d", text)) == len(T.GEOMETRIES)          # no second ladder anywhere
+    entry = _block(text, "int rr_linear_split_launch(")
+    assert "return two_f16 ? launch_split_geometry<true>(P, s) : launch_split_geometry<false>(P, s);" in entry
+    fn = _block(_source("linear.hip"), "int rr_linear_f32(")
+    blk = _block(fn, "if (a.w_packed >= 2)")
+    assert "return rr_linear_split_launch(args, a.w_packed == 3, stream);" in blk
+    assert "launch_split" not in fn.replace("rr_linear_split_launch", "")
 
 
 def test_split_modes_epilogues_and_persistence_are_the_table_s():
-    text = _source()
+    text = _source("linear_split.hip")
     # launch_split: one launch_split_one per operand MODE
     ls = _block(text, "int launch_split(")
     modes = sorted(int(m) for m in re.findall(r"launch_split_one<NTP,\s*NT,\s*(\d),", ls))
@@ -53,7 +55,12 @@ def test_split_modes_epilogues_and_persistence_are_the_table_s():
     assert "WAVES == 12 && (MODE == 0 || MODE == 1)" in one
     assert re.search(r"E1\s*=\s*\(WAVES == 12 && \(MODE == 0 \|\| MODE == 1\)\) \? 1 : 0", one)
     assert re.search(r"G\s*=\s*\(WAVES == 12 && \(MODE == 0 \|\| MODE == 1\)\) \? 2 : 0", one)
-    assert "P.a.k1 + SK <= RR_ZERO_ROW && P.a.k2 + SK <= RR_ZERO_ROW" in one
+    # the lean condition: one predicate, used by launch_split_one, launch_split_epi and the kernel
+    assert ("constexpr bool split_lean(int k1, int k2) { return k1 + SK <= RR_ZERO_ROW && k2 + SK <= RR_ZERO_ROW; }") in text
+    assert text.count("RR_ZERO_ROW && ") == 1                 # written nowhere else
+    assert "const bool lean = split_lean(P.a.k1, P.a.k2);" in one
+    kernel = _block(text, "linear_split_kernel(const LinearParams P)")
+    assert "(LEAN_ONLY || split_lean(a.k1, a.k2))" in kernel
     for leaf in T.LINEAR_LEAVES:
         ntp, nt, mode, waves, epi, persistent = leaf
         assert (ntp, nt, waves) in T.GEOMETRIES
@@ -61,25 +68,42 @@ def test_split_modes_epilogues_and_persistence_are_the_table_s():
     assert sorted({l[4] for l in T.LINEAR_LEAVES if l[3] == 12 and l[2] in (0, 1)}) == [0, 1, 2, 3]
     # launch_split_epi: the persistent form's condition
     epi = _block(text, "int launch_split_epi(")
-    assert "can_persist = MODE == 0 && WAVES == 12 && NT == NTP && EPI == 0" in epi
-    assert "nblk > cus && nk >= 2 && nk % 2 == 0 && lean" in epi
+    assert re.search(r"constexpr bool split_can_persist\(int NTP, int NT, int MODE, int WAVES, int EPI\) \{\s*"
+                     r"return MODE == 0 && WAVES == 12 && NT == NTP && EPI == 0;\s*\}", text)
+    assert "constexpr bool can_persist = split_can_persist(NTP, NT, MODE, WAVES, EPI);" in epi
+    assert "constexpr bool CAN_PERSIST = split_can_persist(NTP, NT, MODE, WAVES, EPI);" in kernel
+    assert "if (can_persist) {" in epi
+    assert "nblk > cus && nk >= 2 && nk % 2 == 0 && split_lean(P.a.k1, P.a.k2)" in epi
     assert "(P.a.M + 16 * WAVES - 1) / (16 * WAVES)" in epi
     assert [l for l in T.LINEAR_LEAVES if l[5]] == [(19, 19, 0, 12, 0, True)]
     # the constants leaf_of uses
-    assert re.search(r"constexpr int SK = (\d+);", text).group(1) == str(T.SK)
-    assert re.search(r"constexpr int RR_ZERO_ROW = (\d+);", text).group(1) == str(T.RR_ZERO_ROW)
+    common = _source("linear_common.h")
+    assert re.search(r"constexpr int SK = (\d+);", common).group(1) == str(T.SK)
+    assert re.search(r"constexpr int RR_ZERO_ROW = (\d+);", common).group(1) == str(T.RR_ZERO_ROW)
 
 
 def test_wgrad_split_instantiations_are_the_table_s():
-    text = _source()
-    fn = _block(text, "int rr_linear_wgrad_f32(")
-    macro = re.search(r"#define RR_WSPLIT_LAUNCH\(MASK, SUB, F16\)(.*?)while \(0\)", fn, re.S).group(1)
-    wtks = sorted(int(w) for w in re.findall(r"wgrad_split_kernel<MASK,\s*SUB,\s*(\d),\s*F16>", macro))
-    assert wtks == [3, 4, 5]
-    body = fn[fn.index("} else {", fn.index("if (a.split == 2)")):]
-    uses = re.findall(r"RR_WSPLIT_LAUNCH\((true|false),\s*(true|false),\s*false\)", body)
+    text = _source("wgrad.hip")
+    # the kernel launches: written once, for both kernel families and both arithmetic forms (FORM = rr_wgrad_args.split)
+    one = _block(text, "void wgrad_launch_one(")
+    assert re.search(r"if constexpr \(FORM == 0\) wgrad_fast_kernel<MASK,\s*SUB,\s*WTK><<<", one)
+    assert re.search(r"else wgrad_split_kernel<MASK,\s*SUB,\s*WTK,\s*FORM == 2><<<", one)
+    assert len(re.findall(r"wgrad_(?:fast|split)_kernel<[^>]*><<<", text)) == 2      # no launch beside these two
+    # the wtk ladder and the (mask, sub) ladder, each once
+    ladder = _block(text, "void wgrad_launch_wtk(")
+    wtks = [int(w) for w in re.findall(r"wgrad_launch_one<FORM,\s*MASK,\s*SUB,\s*(\d)>\(", ladder)]
+    assert wtks == [3, 4, 5] and re.findall(r"wtk == (\d)", ladder) == ["3", "4"]
+    pick = _block(text, "void wgrad_launch(")
+    uses = re.findall(r"wgrad_launch_wtk<FORM,\s*(true|false),\s*(true|false)>\(", pick)
+    assert uses == [("true", "true"), ("true", "false"), ("false", "true"), ("false", "false")]
+    assert re.findall(r"(?:else )?if \((.*?)\) wgrad_launch_wtk", pick) == ["P.a.mask && P.a.x1_sub", "P.a.mask", "P.a.x1_sub"]
+    assert len(re.findall(r"wgrad_launch_one<", text)) == 3 and len(re.findall(r"wgrad_launch_wtk<", text)) == 4
     got = sorted((m == "true", s == "true", w) for m, s in uses for w in wtks)
     assert got == T.WGRAD_SPLIT
+    fn = _block(text, "int rr_linear_wgrad_f32(")
+    forms = re.findall(r"(?:if \(a\.split == (\d)\) |else )wgrad_launch<(\d)>\(P, grid, s, wtk\);", fn)
+    assert forms == [("2", "2"), ("1", "1"), ("", "0")]                            # split = 1: the table's F16 = false form
+    assert "wgrad_split_kernel" not in fn and "wgrad_fast_kernel" not in fn      # no second ladder beside the helper
     # the k-block choice leaf_of's companion restates
     assert "const int wtk = per_blk <= 96 ? 3 : (per_blk <= 128 ? 4 : 5);" in fn
     assert "P->kext = P->k1p + k2 + 1;" in text and "P->k1p = (k1 + 3) & ~3;" in text

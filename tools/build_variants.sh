@@ -1,17 +1,20 @@
 #!/bin/bash
 # Build A/B variants of the library: tools/build_variants.sh name "-DFLAG ..." [name flags]...
-# Every .hip file is recompiled with the flags (objects under build/variants/<name>/).
+# Every source is recompiled with the flags added to the Makefile's own: the Makefile runs on a copy of csrc/ (under
+# build/variants/<name>/), so the source list and the link line are always the library's.  ARCH is passed through.
 set -e
-cd "$(dirname "$0")/../reactranker_amd/csrc"
+root=$(cd "$(dirname "$0")/.." && pwd)
+arch=${ARCH:-gfx950}
+base=$(sed -n 's/^CXXFLAGS := //p' "$root/reactranker_amd/csrc/Makefile" | sed "s/\$(ARCH)/$arch/")
 while [ $# -gt 0 ]; do
   name=$1; flags=$2; shift 2
-  d=../../build/variants/$name
-  mkdir -p $d
-  for f in gather elementwise loss linear ffn plan; do
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off $flags -c $f.hip -o $d/$f.o 2>/dev/null &
-  done
-  wait
-  /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 $d/gather.o $d/elementwise.o $d/loss.o pack.o $d/linear.o $d/ffn.o $d/plan.o collective.o -ldl -o ../../build/variants/lib_$name.so
-  rm -rf $d
-  echo built $name
+  v="$root/build/variants"
+  d="$v/$name/reactranker_amd/csrc"
+  rm -rf "$v/$name" && mkdir -p "$d" "$v/$name/include"
+  cp "$root"/reactranker_amd/csrc/*.hip "$root"/reactranker_amd/csrc/*.h "$root"/reactranker_amd/csrc/*.cpp "$root/reactranker_amd/csrc/Makefile" "$d/"
+  cp "$root"/include/*.h "$v/$name/include/"
+  make -C "$d" -j4 ARCH="$arch" CXXFLAGS="$base $flags" > "$v/$name.log" 2>&1 || { tail -20 "$v/$name.log"; exit 1; }
+  cp "$d/libreactranker_hip.so" "$v/lib_$name.so"
+  rm -rf "$v/$name"
+  echo "built $name"
 done

@@ -2,9 +2,9 @@
 """Per-workgroup start / end stamps of the persistent split GEMMs INSIDE a training step: how staggered do the 256 workgroups of a
 launch start when the chip is shared with the weight-gradient stream, and how much earlier would the launch end if every workgroup
 ended at the same time (max(end) - mean(end)) instead of carrying an equal static share from whenever it got its CU?
-Needs a library built with -DRR_TRACE from a copy of csrc/ with tools/experiments/r05_trace_insitu.patch applied to linear.hip (one
-trace slot per persistent launch, the k-loop count per workgroup):
-  cp -r reactranker_amd/csrc build/trace_src && patch build/trace_src/linear.hip tools/experiments/r05_trace_insitu.patch
+Needs a library built with -DRR_TRACE from a copy of csrc/ with tools/experiments/r05_trace_insitu.patch applied (it touches
+linear_common.h, linear.hip and linear_split.hip: one trace slot per persistent launch, the k-loop count per workgroup):
+  cp -r reactranker_amd/csrc build/trace_src && patch -p1 -d build/trace_src < tools/experiments/r05_trace_insitu.patch
   (cd build/trace_src && make CXXFLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -DRR_TRACE" && cp libreactranker_hip.so ../lib_trace.so)
 Usage: RR_LIB_PATH=build/lib_trace.so python tools/trace_insitu.py [--config mle64] [--noside]
 Round-5 output: profiles/r05_trace_insitu_persistent_gemm.txt."""
