@@ -24,6 +24,10 @@ struct LinearParams {
   uint32_t drop_thr;
   float keep_scale;
   int persist;          // linear_split_kernel: one workgroup per CU walks row blocks blockIdx.x, + gridDim.x, ... (see there)
+  // linear_split_kernel, balanced last round of a one-block-per-workgroup launch (see there): workgroups [0, bal_full) run
+  // full blocks of 3 x 64 rows, the ones behind them share the remaining 64-row units, bal_base or bal_base + 1 (the
+  // first bal_rem of them) each.  bal_base = bal_rem = 0: every workgroup runs a full block
+  int bal_full, bal_base, bal_rem;
 };
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -179,6 +183,7 @@ inline LinearParams linear_params(const rr_linear_args& a) {
   P.t2 = (a.k2 + BK - 1) / BK;
   P.flags = 0;
   P.persist = 0;
+  P.bal_full = P.bal_base = P.bal_rem = 0;
   if (a.k1 > 0 && vec_ok(a.a1, a.lda1)) P.flags |= F_A1_VEC;
   if (a.k2 > 0 && vec_ok(a.a2, a.lda2)) P.flags |= F_A2_VEC;
   if (a.a1_sub && vec_ok(a.a1_sub, a.lda1_sub)) P.flags |= F_SUB_VEC;

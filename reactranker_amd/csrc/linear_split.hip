@@ -32,6 +32,13 @@ __host__ __device__ constexpr bool split_can_persist(int NTP, int NT, int MODE, 
   return MODE == 0 && WAVES == 12 && NT == NTP && EPI == 0;
 }
 
+// Balanced last round (see the kernel): the other one-column-block instantiations of the 12-wave geometry that the model launches.
+// The generic-loader twins EPI 2 / 3 (K > 992: no configuration of the model) stay as they were: <19,19,1,12,3> has no register
+// to spare for it (waves without rows cost it spilled registers inside the k-loop).
+__host__ __device__ constexpr bool split_balanced(int NTP, int NT, int MODE, int WAVES, int EPI, bool F16) {
+  return WAVES == 12 && NT == NTP && EPI < 2 && !F16 && !split_can_persist(NTP, NT, MODE, WAVES, EPI);
+}
+
 // NTP: column tiles of the packed weight image; NT: column tiles of ONE workgroup (blockIdx.y picks tiles y * NT ...);
 // WAVES: 16-row groups per workgroup.  Instantiated: <19, 19, 12 waves> - one workgroup per CU (114 KB of LDS) covers all
 // columns of 192 rows - and <10, 10, 8> / <4, 4, 8> for narrow layers.  Cutting the 19 tiles into 10 + 9 (<19, 10, 8>:
@@ -63,7 +70,11 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
   // operand row left HBM twice).
   constexpr bool PAIR = NTP == 2 * NT;
   const unsigned int bx = PAIR ? (((blockIdx.x >> 4) << 3) + (blockIdx.x & 7u)) : blockIdx.x;
-  const unsigned int by = PAIR ? ((blockIdx.x >> 3) & 1u) : blockIdx.y;
+  // (BALANCED, SHORT: see "Balanced last round" below.  Those launches have one column block: by = 0 folds the column-block
+  // arithmetic away, scalar registers the epilogue needs)
+  constexpr bool BALANCED = split_balanced(NTP, NT, MODE, WAVES, EPI, F16);
+  constexpr bool SHORT = BALANCED || split_can_persist(NTP, NT, MODE, WAVES, EPI);
+  const unsigned int by = PAIR ? ((blockIdx.x >> 3) & 1u) : (BALANCED ? 0u : blockIdx.y);
   if (PAIR && static_cast<int64_t>(bx) * (16 * WAVES) >= P.a.M) return;   // (uniform: the grid is padded to whole groups of 16 ids)
   const int t0 = by * NT;                              // first column tile of this workgroup
   const int nth = NTP - t0 < NT ? NTP - t0 : NT;       // its column tiles (the last workgroup of a row block may have fewer)
@@ -113,6 +124,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
   // same order per element: bit-identical to the one-block form.  Rows are counted in groups of 16 (one wave's rows).
   constexpr bool CAN_PERSIST = split_can_persist(NTP, NT, MODE, WAVES, EPI);
   const bool persist = CAN_PERSIST && P.persist != 0;
+  // Balanced last round (the other instantiations of the one-workgroup-per-CU geometry, chosen by the host: P.bal_*): still one
+  // block per workgroup, but the row blocks behind the last whole round of full ones are cut so that every CU gets an equal
+  // share of their 64-row units - blocks of 4 or 8 active waves, where a grid of full blocks ends with a few CUs running
+  // twelve waves and the rest idle.  SHORT: the instantiations in which a wave may be without rows (uwave >= nw): it issues
+  // its loads - the weight image is dealt over ALL waves, and every wave keeps the same vmcnt sequence - and nothing else.
+  // The block's rows travel to the epilogue in ONE scalar register, blk = first 64-row unit << 2 | units (1 .. 3; the host
+  // keeps the unit count below 2^29), where the grid of full blocks needed none: these kernels have no scalar to spare.
   // the workgroup's running maxima of |C| / |dz_out| (rr_linear_args.c_amax_out / dz_amax_out): two words behind everything else
   unsigned int* const amx = reinterpret_cast<unsigned int*>(smem + PF_OFF + (CAN_PERSIST ? WAVES * 2048 : 0));
   if (F16 && tid == 0) { amx[0] = 0u; amx[1] = 0u; }    // (the prologue's barrier orders this before any use)
@@ -123,6 +141,18 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
     const int64_t base = units / G, rem = units % G, p = blockIdx.x;
     g_cur = 4 * (p * base + (p < rem ? p : rem));
     g_end = g_cur + 4 * (base + (p < rem ? 1 : 0));
+  }
+  int blk = 0;
+  if (BALANCED) {
+    int u0 = static_cast<int>(blockIdx.x) * (WAVES / 4), nu = WAVES / 4;
+    if ((P.bal_base | P.bal_rem) != 0 && static_cast<int>(blockIdx.x) >= P.bal_full) {
+      const int q = static_cast<int>(blockIdx.x) - P.bal_full;          // larger tail blocks first
+      u0 = P.bal_full * (WAVES / 4) + q * P.bal_base + (q < P.bal_rem ? q : P.bal_rem);
+      nu = P.bal_base + (q < P.bal_rem ? 1 : 0);
+    }
+    blk = (u0 << 2) | nu;
+    g_cur = 4 * static_cast<int64_t>(u0);
+    g_end = g_cur + 4 * nu;
   }
   int nw = g_end - g_cur < WAVES ? static_cast<int>(g_end - g_cur) : WAVES;   // active waves of the current block (uniform)
   int64_t m0 = g_cur * 16;
@@ -294,7 +324,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
     split_pair(v1.z, v1.w, t0, t1, t2); x0.w = t0; x1.w = t1; x2.w = t2;
   };
   auto fixup = [&](int s, int slot) {                  // first use of the loads: selects, mask / subtract, split
-    if (CAN_PERSIST && uwave >= nw) return;             // (its loads are still issued: every wave keeps the same vmcnt sequence)
+    if (SHORT && uwave >= nw) return;                   // (its loads are still issued: every wave keeps the same vmcnt sequence)
     if (FASTX && fastx_ok) {
       f32x4 v0 = ra[slot][0], v1 = ra[slot][1];
       f32x4 u0 = f32x4(0.f), u1 = f32x4(0.f);
@@ -365,7 +395,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
     }
   };
   auto mfma_block = [&](int s) {
-    if (CAN_PERSIST && uwave >= nw) return;             // (uniform) a wave without rows in a short last block: no MFMAs, no LDS reads
+    if (SHORT && uwave >= nw) return;                   // (uniform) a wave without rows in a short last block: no MFMAs, no LDS reads
     const u32x4* Ws = reinterpret_cast<const u32x4*>(smem + (s & 1) * PANEL) + lane;
     if constexpr (F16) {
       const f16x8 h0 = as_f16x8(x0), h1 = as_f16x8(x1);
@@ -510,9 +540,13 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
   const int tid = lane_o, lane = lane_o & 63, wave = lane_o >> 6;
   const int fr = lane & 15, fkq = lane >> 4;
   // this block's rows, from the (uniform) block index: nothing row-specific is carried through the k-loop in registers
-  const int64_t m0 = g_cur * 16;
+  int blk_o = blk;
+  if (BALANCED) asm volatile("" : "+s"(blk_o));        // (decoded HERE, not ahead of the k-loop)
+  const int64_t gb = BALANCED ? 4 * static_cast<int64_t>(blk_o >> 2) : g_cur;   // first 16-row group and active waves of this block
+  const int nwb = BALANCED ? 4 * (blk_o & 3) : nw;
+  const int64_t m0 = gb * 16;
   const int64_t m = m0 + wave * 16 + fr;
-  const bool row_ok = wave < nw && m < a.M;
+  const bool row_ok = wave < nwb && m < a.M;
   const int64_t mc = row_ok ? m : a.M - 1;
   const int nq = fkq * 4;
   float* crow = a.c + mc * a.ldc;
@@ -561,8 +595,11 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
   // column sums (dX GEMMs: no bias / residual / activation) are taken from the accumulators before the transposition;
   // the rare combination of column sums WITH epilogue arithmetic keeps the accumulator-layout code below.
   const bool plain_epi = !has_bias && a.residual == nullptr && !relu && P.drop_thr == 0u && prow == nullptr && !mb_on;
-  bool done = false;
-  if (RS_EPI && (EPI & 1) == 1 && (!cs_on || plain_epi)) {
+  // (a wave without rows of a balanced launch has nothing to finish, store or sum: it goes on to the barriers below.  The
+  // persistent form walks both epilogues with row_ok false, as it did)
+  const bool idle = BALANCED && uwave >= nwb;
+  bool done = idle;
+  if (!idle && RS_EPI && (EPI & 1) == 1 && (!cs_on || plain_epi)) {
     done = true;
     if (cs_on) {
 #pragma unroll
@@ -746,8 +783,8 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
       const float* base = cs_lds + h * 4 * BN + q * 4;
       const f32x4 s01 = ld4(base) + ld4(base + BN);
       const f32x4 s23 = ld4(base + 2 * BN) + ld4(base + 3 * BN);
-      if (n < a.N && h * 4 < nw && m0 + h * 64 < a.M)    // (one partial row per 64-row unit; a short last block owns fewer)
-        *reinterpret_cast<f32x4*>(a.colsum_partial + (g_cur / 4 + h) * a.ld_partial + n) = s01 + s23;
+      if (n < a.N && h * 4 < nwb && m0 + h * 64 < a.M)    // (one partial row per 64-row unit; a short last block owns fewer)
+        *reinterpret_cast<f32x4*>(a.colsum_partial + (gb / 4 + h) * a.ld_partial + n) = s01 + s23;
     }
   }
   if (!(CAN_PERSIST && has_next)) break;
@@ -784,6 +821,16 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
 #endif
 }
 
+// the device's compute units, asked for once per device (unknown: a count no launch exceeds, so nothing is shared out by it)
+inline int split_cus(int dev) {
+  static std::atomic<int> n_cu[64];
+  int cus = (dev >= 0 && dev < 64) ? n_cu[dev].load(std::memory_order_relaxed) : 0;
+  if (cus == 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1 << 30;
+    if (dev >= 0 && dev < 64) n_cu[dev].store(cus, std::memory_order_relaxed);
+  }
+  return cus;
+}
 // RR_EPI_MODE (A/B knob): 0 = accumulator-layout epilogue everywhere, 1 = row-contiguous where the epilogue READS (a
 // residual), 2 = row-contiguous everywhere it applies.  Measured (profiles/r03_experiments.txt): with a residual read
 // 223 -> 196 us per isolated 139k-row launch; store-only epilogues do not gain and pay the LDS round trip; inside a
@@ -808,22 +855,39 @@ int launch_split_epi(const LinearParams& P, hipStream_t s) {
     if (dev >= 0 && dev < 64) configured.fetch_or(uint64_t(1) << dev, std::memory_order_release);
   }
   const int64_t nblk = (P.a.M + 16 * WAVES - 1) / (16 * WAVES);
+  // (the balanced instantiations carry a block's first 64-row unit in 29 bits: 2^27 blocks of 3 units, 2.5e10 rows)
+  if (split_balanced(NTP, NT, MODE, WAVES, EPI, F16) && nblk >= (int64_t(1) << 27)) return RR_ERR_UNSUPPORTED;
   // Persistent form (see the kernel): plain-operand GEMMs of the one-workgroup-per-CU geometry with more row blocks than
   // CUs, an even number of k-steps (the pipeline's two slots / two image buffers keep their parity across the block
   // boundary) and interior steps on the lean loader.  RR_NO_PERSIST (A/B knob) keeps one workgroup per row block.
+  const int cus = split_cus(dev);
   if (can_persist) {
-    static int n_cu[64] = {0};
-    int cus = (dev >= 0 && dev < 64) ? n_cu[dev] : 0;
-    if (cus == 0) {
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1 << 30;
-      if (dev >= 0 && dev < 64) n_cu[dev] = cus;
-    }
     const int nk = P.t1 + P.t2;
     if (nblk > cus && nk >= 2 && nk % 2 == 0 && split_lean(P.a.k1, P.a.k2) && !getenv("RR_NO_PERSIST")) {
       LinearParams Q = P;
       Q.persist = 1;
       // every CU an equal share of the 64-row units (the granularity of the column-sum partials)
       const dim3 grid(static_cast<unsigned>(cus), 1);
+      linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16><<<grid, 64 * WAVES, smem, s>>>(Q);
+      return rr_launch_status();
+    }
+  }
+  // Balanced last round (see the kernel and split_balanced): with
+  // U 64-row units, the whole rounds of full blocks - F = floor(U / (3 cus)) * cus workgroups of 3 units, lowest ids, so they
+  // are dispatched first - are followed by tail workgroups that share the remaining T = U - 3 F units the way the
+  // persistent form shares all of them: T / cus each, the first T % cus one more, none without units.  Taken where it
+  // shortens the longest tail block (T <= 2 cus: blocks of 4 or 8 waves instead of 12); with T > 2 cus some tail block has 3
+  // units either way and the grid of full blocks stays.  RR_NO_BALANCED_TAIL (A/B knob) keeps that grid everywhere.
+  if (split_balanced(NTP, NT, MODE, WAVES, EPI, F16) && nblk > cus && !getenv("RR_NO_BALANCED_TAIL") &&
+      !(MODE >= 2 && getenv("RR_NO_BALANCED_TAIL_DX"))) {
+    const int64_t units = (P.a.M + 63) / 64;
+    const int64_t full = units / (3 * static_cast<int64_t>(cus)) * cus, tail = units - 3 * full;
+    if (tail > 0 && tail <= 2 * static_cast<int64_t>(cus)) {
+      LinearParams Q = P;
+      Q.bal_full = static_cast<int>(full);
+      Q.bal_base = static_cast<int>(tail / cus);
+      Q.bal_rem = static_cast<int>(tail % cus);
+      const dim3 grid(static_cast<unsigned>(full + (Q.bal_base > 0 ? cus : Q.bal_rem)), 1);
       linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16><<<grid, 64 * WAVES, smem, s>>>(Q);
       return rr_launch_status();
     }

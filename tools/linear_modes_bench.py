@@ -1,6 +1,8 @@
 """Isolated timings of the split GEMM launches a BASELINE configs[2] training step makes (M = 138,881 bond rows / 71,425
 atom rows, H = 300), for same-box A/B of kernel variants: RR_LIB_PATH=build/variants/lib_X.so python tools/linear_modes_bench.py
-Prints one line per launch form: microseconds per launch (median of 5 x 20 back-to-back launches)."""
+Prints one line per launch form: microseconds per launch (median of 5 x 20 back-to-back launches).
+RR_BENCH_AB=KNOB [RR_BENCH_ROUNDS=4]: every form timed with the environment knob KNOB (one the library reads per launch, e.g.
+RR_NO_BALANCED_TAIL) unset and set to 1 in alternation, in this process: "new" and "knob" columns, one value per round."""
 import os, sys, statistics, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import functions as Fn
@@ -26,6 +28,8 @@ def t(fn, n=20, reps=5):
     return statistics.median(out)
 
 
+AB = os.environ.get("RR_BENCH_AB")
+ROUNDS = int(os.environ.get("RR_BENCH_ROUNDS", "4"))
 res = {}
 for M in (138881, 71425):
     W = torch.randn(H, H, device=dev) / 17
@@ -51,6 +55,9 @@ for M in (138881, 71425):
         "fwd gathered - gathered, bias, residual, relu, dropout, bits (mode 1)": lambda: Fn.linear(
             M, H, wf, w_packed=True, a1=am, k1=H, a1_idx=b2a, a1_sub=y, a1_sub_idx=rev, bias=b, residual=res_, act=Fn.ACT_RELU,
             drop_p=0.1, seed=5, out=out, mask_bits_out=bits),
+        "fwd gathered - gathered, bias, relu, dropout, bits, no residual (mode 1)": lambda: Fn.linear(
+            M, H, wf, w_packed=True, a1=am, k1=H, a1_idx=b2a, a1_sub=y, a1_sub_idx=rev, bias=b, act=Fn.ACT_RELU,
+            drop_p=0.1, seed=5, out=out, mask_bits_out=bits),
         "fwd plain, bias, residual, relu, dropout, bits (mode 0)": lambda: Fn.linear(
             M, H, wf, w_packed=True, a1=x, k1=H, bias=b, residual=res_, act=Fn.ACT_RELU, drop_p=0.1, seed=5, out=out, mask_bits_out=bits),
     }
@@ -72,6 +79,19 @@ for M in (138881, 71425):
         forms["fwd W_o: K 61 | 300, bias, relu, dropout, bits (mode 0)"] = lambda: Fn.linear(
             M, H, Wo.pk(61, H), w_packed=True, a1=fa, k1=61, a2=x, k2=H, bias=b, act=Fn.ACT_RELU, drop_p=0.1, seed=7, out=out, mask_bits_out=bits)
     for name, fn in forms.items():
+        if AB:
+            new, knob = [], []
+            for _ in range(ROUNDS):
+                os.environ.pop(AB, None)
+                new.append(t(fn))
+                os.environ[AB] = "1"
+                knob.append(t(fn))
+            os.environ.pop(AB, None)
+            mn, mk = statistics.median(new), statistics.median(knob)
+            print(f"M {M:6d}  new {mn:7.1f} us  knob {mk:7.1f} us  {100 * (mn / mk - 1):+5.1f} %  new [{' '.join(f'{v:.1f}' for v in new)}]  "
+                  f"knob [{' '.join(f'{v:.1f}' for v in knob)}]  {name}", flush=True)
+            res[(M, name)] = mn
+            continue
         us = t(fn)
         res[(M, name)] = us
         print(f"M {M:6d}  {us:7.1f} us  {name}", flush=True)
