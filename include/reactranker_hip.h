@@ -523,6 +523,39 @@ int rr_ranknet_bwd_f32(const float* score, int64_t score_stride, const float* ta
                        const int32_t* seg_off, int Q, int max_len, float sigma, int mode,
                        const float* gloss, float* dscore, int64_t dscore_stride, rr_stream_t stream);
 
+/* LambdaRank (additive: three new symbols, the ABI revision stays 8): RankNet's pair cost with every pair weighted by the
+ * |delta NDCG| of swapping the two candidates in the current predicted order.  It is this library's own definition (the
+ * reference trainer has none).  Per query, with k = C for ndcg_k == 0 and min(ndcg_k, C) otherwise:
+ *   r_i     1-based rank of i by score, descending, ties by list position (rr_ranking_metrics_f32's `order`)
+ *   D_i     1 / log2(1 + r_i) for r_i <= k, else 0
+ *   g_i     exp(t_i - max_j t_j)                                  (compute_NDCG's gains; the shift cancels below)
+ *   maxDCG  sum_{p = 1..k} g_(p) / log2(1 + p), g_(p) the p-th largest gain
+ *   w_ij    |g_i - g_j| |D_i - D_j| / maxDCG                      (constants: no gradient flows through them)
+ *   C_ij    softplus(-sigma (s_i - s_j)) for t_i > t_j, softplus(sigma (s_i - s_j)) for t_i < t_j, 0 for t_i == t_j, with
+ *           the stable softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   loss_sum = sum over queries and ordered pairs i != j of w_ij C_ij;  pairs = sum over queries of 2 #{(i, j): t_i > t_j},
+ * RankNet's count.  A query without a pair (empty, one candidate, all targets equal) adds 0 to both, and every gradient
+ * entry it owns is WRITTEN as 0 (dscore may be uninitialised memory).  partial is [2 * Q] (loss as a float, pairs as an
+ * int32), finished in a fixed order: run-to-run identical bits, no float atomics.  LDS 20 * max_len bytes.
+ *   fwd   loss_sum and pairs.
+ *   bwd   dscore = gloss[0] * d loss_sum / d score.
+ *   step  one launch: loss = scale * loss_sum, pairs, and dscore = scale * d loss_sum / d score - the bits of fwd followed
+ *         by bwd with *gloss == scale.  `scale` is a host value (a trainer passes 1 / the window's pair count, so the losses
+ *         and gradients of the shards of a window add up).  `counter` as for rr_listmle_step_f32: ONE device word per
+ *         concurrent launch, zero (or a multiple of Q) when the launch starts, left at zero.
+ * Status: RR_ERR_ARG for a null pointer, a stride < 1, Q < 0, sigma <= 0 or ndcg_k < 0; max_len > 8192 ->
+ * RR_ERR_UNSUPPORTED, nothing is launched; Q == 0 writes a zero loss and zero pairs (fwd, step) or launches nothing (bwd). */
+int rr_lambdarank_fwd_f32(const float* score, int64_t score_stride, const float* targets,
+                          const int32_t* seg_off, int Q, int max_len, float sigma, int ndcg_k,
+                          float* loss_sum, int64_t* pairs, float* partial /* [2*Q] */, rr_stream_t stream);
+int rr_lambdarank_bwd_f32(const float* score, int64_t score_stride, const float* targets,
+                          const int32_t* seg_off, int Q, int max_len, float sigma, int ndcg_k,
+                          const float* gloss, float* dscore, int64_t dscore_stride, rr_stream_t stream);
+int rr_lambdarank_step_f32(const float* score, int64_t score_stride, const float* targets,
+                           const int32_t* seg_off, int Q, int max_len, float sigma, int ndcg_k, float scale,
+                           float* loss, int64_t* pairs, float* partial /* [2*Q] */, unsigned int* counter,
+                           float* dscore, int64_t dscore_stride, rr_stream_t stream);
+
 /* Pointwise: nn.MSELoss (train/train_listwise.py:166-167) and GaussDisLoss (train/loss.py:154-162).
  * partial: rr_pointwise_partial_count(n) floats. */
 int64_t rr_pointwise_partial_count(int64_t n);

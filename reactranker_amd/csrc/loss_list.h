@@ -431,13 +431,13 @@ __device__ inline PointRow point_row(float mean, float targ, float v, float g) {
 
 // ---------------------------------------------------------------- the last-arriver finish of the one-launch "step" kernels
 // fixed-order sum of n floats on one wave: reduce_scale_kernel's order (256 strided accumulators, then its halving tree),
-// lane l playing threads l, l + 64, l + 128, l + 192; the result is valid in lane 0
-__device__ inline float fixed_sum(const float* p, int n, int lane) {
+// lane l playing threads l, l + 64, l + 128, l + 192; the result is valid in lane 0.  step: the distance between two values.
+__device__ inline float fixed_sum(const float* p, int n, int lane, int step = 1) {
   float a[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     float acc = 0.f;
-    for (int i = lane + 64 * u; i < n; i += 256) acc += p[i];
+    for (int i = lane + 64 * u; i < n; i += 256) acc += p[i * step];
     a[u] = acc;
   }
   float r = (a[0] + a[2]) + (a[1] + a[3]);                           // tree steps o = 128 and o = 64
@@ -451,14 +451,20 @@ __device__ inline float fixed_sum(const float* p, int n, int lane) {
 // path (partials, then reduce_scale_kernel) and the same bits on every run - and re-arms the counter, one device word the
 // caller keeps.  The ticket is tested modulo n, so a word an earlier launch left at any multiple of n serves like a zero
 // one.  True in lane 0 of the finishing wave alone, where sum[] is valid.
-template <int ROWS>
-__device__ inline bool finish_last(const float* partial, int n, unsigned int* counter, int lane, float (&sum)[ROWS]) {
+// arrive_last is the ticket alone: true in every lane of the wave that arrives last, which then owes the counter its zero.
+__device__ inline bool arrive_last(int n, unsigned int* counter, int lane) {
   __threadfence();                                                   // release: this workgroup's partials
   unsigned int ticket = 0u;
   if (lane == 0) ticket = atomicAdd(counter, 1u);
   ticket = __shfl(ticket, 0, RR_WAVE);
   if (ticket % static_cast<unsigned int>(n) != static_cast<unsigned int>(n) - 1u) return false;
   __threadfence();                                                   // acquire: every other workgroup's partials
+  return true;
+}
+
+template <int ROWS>
+__device__ inline bool finish_last(const float* partial, int n, unsigned int* counter, int lane, float (&sum)[ROWS]) {
+  if (!arrive_last(n, counter, lane)) return false;
 #pragma unroll
   for (int r = 0; r < ROWS; ++r) sum[r] = fixed_sum(partial + r * n, n, lane);
   if (lane == 0) *counter = 0u;

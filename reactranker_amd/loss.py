@@ -325,6 +325,72 @@ def ranknet_lambda(y_pred, scope, targets, sigma: float = 1.0, gpu: int = None):
     return out
 
 
+class _LambdaRankFn(torch.autograd.Function):
+    """scale * loss_sum of LambdaRank (csrc/lambdarank.hip) and the window's ordered pairs.  When the score wants a gradient
+    and FusedStep is on, rr_lambdarank_step_f32 writes the loss and scale * d loss_sum / d score in one launch and
+    `backward(loss)` hands that gradient out; otherwise rr_lambdarank_fwd_f32, and rr_lambdarank_bwd_f32 with the upstream
+    gradient times `scale` - the same bits for an upstream gradient of one."""
+
+    @staticmethod
+    def forward(ctx, score, targets, seg, Q, max_len, sigma, ndcg_k, scale):
+        s = _vec(score.detach())
+        loss = _f1(s.device)
+        pairs = torch.empty(1, dtype=torch.int64, device=s.device)
+        part = torch.empty(max(2 * Q, 2), dtype=torch.float32, device=s.device)
+        args = [ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, float(sigma), int(ndcg_k)]
+        ctx.ds_unit = None
+        if FusedStep.enabled and ctx.needs_input_grad[0]:
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call("rr_lambdarank_step_f32", *args, scale, ptr(loss), ptr(pairs), ptr(part), ptr(_counter(s.device)), ptr(d), 1)
+            ctx.ds_unit = d
+        else:
+            _call("rr_lambdarank_fwd_f32", *args, ptr(loss), ptr(pairs), ptr(part))
+            if scale != 1.0:
+                loss = loss * scale                      # (a float32 product, as in the step kernel)
+        ctx.save_for_backward(s, targets, seg)
+        ctx.meta = (args, scale)
+        ctx.mark_non_differentiable(pairs)
+        return loss.reshape(()), pairs
+
+    @staticmethod
+    def backward(ctx, g, _gp):
+        if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
+            d, ctx.ds_unit = ctx.ds_unit, None
+            FusedStep.hits += 1
+        else:
+            s = ctx.saved_tensors[0]                     # (the saved tensors keep the pointers in `args` alive)
+            args, scale = ctx.meta
+            g = (g.reshape(-1).float() * scale).contiguous()
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call("rr_lambdarank_bwd_f32", *args, ptr(g), ptr(d), 1)
+        return (d,) + (None,) * 7
+
+
+def lambdarank_loss(y_pred, scope, targets, sigma: float = 1.0, ndcg_k: int = 0, gpu: int = None, pairs: int = None):
+    """LambdaRank over a window of queries: RankNet's pair cost, every pair weighted by the |delta NDCG| of swapping the two
+    candidates in the current predicted order - gains exp(target) as in `ranking_metrics`, NDCG truncated at `ndcg_k`
+    positions (0: the whole list).  The weights are constants; the definition is in DESIGN section 4b.  This library's own
+    loss: the reference trainer has none.
+
+    Returns (loss, pairs_tensor).  pairs=None: loss is loss_sum, as for ranknet_loss.  pairs: a host int, the ordered-pair
+    count to normalise by (the WINDOW's count for a shard of a data-parallel step) - loss is loss_sum * float32(1 / pairs) and
+    `backward(loss)` then takes the gradient the same launch wrote (FusedStep).  pairs_tensor is this call's own count, an
+    int64 device scalar.  `y_pred` may be [M] or [M, k] (first column, read in place)."""
+    if y_pred.dim() > 1:
+        y_pred = y_pred[:, 0]
+    if not sigma > 0:
+        raise ValueError("lambdarank_loss: sigma must be positive")
+    if int(ndcg_k) != ndcg_k or ndcg_k < 0:
+        raise ValueError("lambdarank_loss: ndcg_k must be a non-negative integer (0: the whole list)")
+    scale = 1.0
+    if pairs is not None:
+        if int(pairs) <= 0:
+            raise ValueError("lambdarank_loss: pairs must be a positive count (a window without pairs is skipped by the trainer)")
+        scale = float(np.float32(1.0 / int(pairs)))
+    scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
+    return _LambdaRankFn.apply(y_pred, t, seg, len(scope), max_len, sigma, int(ndcg_k), scale)
+
+
 # ---------------------------------------------------------------------------------------------- the remaining task types' losses
 def annealing_coef(max_coeff, epoch, epochs):
     """The annealing coefficient of Listnet_with_uq / Dirichlet_uq (reference train/loss.py:393, 468), computed on the host as
