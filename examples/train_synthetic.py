@@ -15,6 +15,10 @@ Under `python -m torch.distributed.run --nproc-per-node N examples/train_synthet
 parallel: every rank builds the same batches and keeps its block of whole queries of each (dp.shard_query_batch).  Backend:
 $RR_DIST_BACKEND (default nccl = RCCL); RR_SINGLE_DEVICE=1 puts every rank on --gpu.  The four NIG task types need every target
 of a step and are refused there (one process trains them).
+
+A task type whose head predicts a distribution per candidate (evidential_ranking, mledis_gaussian, listnetdis_gauss, the NIG
+ones) ends with the validation set's uncertainty from one forward per batch (uncertainty.evaluate_uncertainty,
+method='distribution').
 """
 import argparse
 import logging
@@ -27,7 +31,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import ranknet_baseline                          # noqa: E402
+from reactranker_amd import ranknet_baseline, uncertainty             # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -146,6 +150,13 @@ def main():
     load_checkpoint(args.checkpoint, model)
     if rank == 0:
         log.info("checkpoint %s restored", args.checkpoint)
+    if world == 1 and model.ffn.head() in uncertainty.MOMENT_KIND_OF_HEAD:
+        # the head predicts a distribution per candidate: its uncertainty on the validation set from ONE forward per batch
+        uq = uncertainty.evaluate_uncertainty(model, val_b, args.checkpoint, args.gpu, method="distribution", target_name=None)
+        log.info("uncertainty (method='distribution', kind %s): %s, worst |mass - 1| %.1e, Spearman(error, std) %.3f",
+                 uncertainty.MOMENT_KIND_OF_HEAD[model.ffn.head()],
+                 ", ".join(f"{k} {v:.3f}" for k, v in zip(uncertainty.QSTAT_NAMES, uq["qstats"])), uq["mass_worst"],
+                 uq["calibration"]["spearman"])
     if world > 1:
         dist.destroy_process_group()
 

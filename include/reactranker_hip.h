@@ -694,6 +694,45 @@ int rr_mc_sample_stats_f32(const float* samples, int64_t sample_stride, int T, c
                            int Q, int max_len, float* mean, float* std_dev, float* p_top1, float* mean_rank, double* qstats,
                            rr_stream_t stream);
 
+/* The same per-candidate and per-query statistics from ONE eval-mode forward of a distributional head: candidate i of a
+ * list of C scores N(mu_i, sigma_i^2), independently of the others, and everything follows analytically - no samples.  This
+ * is a definition of its own (the reference has no such code).  Row i of `out` (leading dimension ld, f32) is decoded by
+ * `kind` (rr_moment_kind), the variance in f64:
+ *   RR_MOMENT_GAUSSIAN      mu = col 0, var = col 1             (heads 3 and 4)
+ *   RR_MOMENT_LOG_VARIANCE  mu = col 0, var = exp(col 1)        (what mledis_gaussian's list term assumes)
+ *   RR_MOMENT_NIG           cols mu, v, alpha, beta (head 6): aleatoric = beta / (alpha - 1), epistemic = beta / (v (alpha - 1)),
+ *                           var = aleatoric + epistemic - the moment-matched Gaussian of the Student-t predictive
+ * Per candidate (length M = seg_off[Q], f32):
+ *   mean       the bits of column 0
+ *   std_dev    sigma = sqrt(var), rounded once
+ *   mean_rank  1 + sum_{j != i} Phi((mu_j - mu_i) / sqrt(sigma_i^2 + sigma_j^2)): the exact expected 1-based descending rank
+ *   p_top1     sum_n w_n prod_{j != i} Phi((mu_i + sigma_i x_n - mu_j) / sigma_j) over the n_nodes probabilists' Gauss-Hermite
+ *              nodes x_n with weights w_n normalised to sum 1 (numpy.polynomial.hermite_e.hermegauss), two f64 DEVICE arrays;
+ *              1 <= n_nodes <= RR_UQ_MAX_NODES
+ *   aleatoric_std, epistemic_std   sqrt of the two NIG variances; written for RR_MOMENT_NIG only, either may be NULL
+ * Arithmetic: per pair everything is f32 - the margin and ONE erfcf, Phi(z) = 0.5f * erfcf(-z * 0.70710678f); the product over
+ * j for one node, the sum over the nodes and the rank sum are f64, each rounded once.
+ * qstats[q*RR_UQ_NQSTATS + 0..3] (f64) has the meanings listed at rr_mc_sample_stats_f32, formed in f64 from the rounded f32
+ * outputs; mass[q] (f64) = sum_i p_top1_i.  mass is the quadrature's own diagnostic and is NOT normalised away: it is 1 when
+ * the rule resolves the integrand, and it drifts when one candidate's sigma is far larger than a rival's (the integrand
+ * then has a step much narrower than the node spacing).  Measured with the f64 restatement (tests/analytic_uq_ref.py):
+ * variances within a factor 11 of each other (0.05 .. 0.55), lists of 2 .. 300, 32 nodes: |mass - 1| <= 2.3e-4 and p within
+ * 1.5e-4 of the 128-node value; one candidate with 10x its rival's variance, 32 nodes: p error 1.7e-4; with 100x: 9e-3 at 32
+ * nodes, 1.1e-3 at 128.
+ * An empty list writes zeros to its qstats and mass; a list of one candidate gives p = 1 and rank 1.  A non-finite mean or
+ * a non-positive variance moves no store (nothing is scattered by rank); what is written for that list is unspecified and
+ * its std_dev is not a positive finite number, which is what a caller checks.
+ * Grid (query, block of 256 candidates), lane = candidate; every workgroup stages mu_j, 1/sigma_j, sigma_j^2 of its list in
+ * LDS, 12 * max_len bytes (96 KiB at 8192); a second launch, one wavefront per query, writes qstats and mass.  No atomics:
+ * the bits are run-to-run identical.  Status: RR_ERR_ARG for a null required pointer, n_nodes outside [1, 128], an unknown
+ * kind, ld below the kind's column count (2, 2, 4) or a negative size; RR_ERR_UNSUPPORTED for max_len > 8192. */
+typedef enum rr_moment_kind { RR_MOMENT_GAUSSIAN = 0, RR_MOMENT_LOG_VARIANCE = 1, RR_MOMENT_NIG = 2 } rr_moment_kind;
+#define RR_UQ_MAX_NODES 128
+int rr_analytic_rank_stats_f32(const float* out, int64_t ld, int kind, const float* targets, const int32_t* seg_off, int Q,
+                               int max_len, const double* nodes, const double* weights, int n_nodes, float* mean,
+                               float* std_dev, float* p_top1, float* mean_rank, float* aleatoric_std, float* epistemic_std,
+                               double* qstats, double* mass, rr_stream_t stream);
+
 /* Does the uncertainty track the error?  err[n], unc[n] (f32, n >= 1) with their stable ascending orders order_err /
  * order_unc (int64 row indices, ties in row order: torch.sort(stable=True) on the device - sorting stays torch plumbing).
  * fractions[n_frac] (f64, device), each in [0, 1).  out[1 + 3 * n_frac] (f64, device):

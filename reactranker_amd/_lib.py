@@ -270,6 +270,8 @@ _SIGS = {
                                c_stream]),
     "rr_mc_sample_stats_f32": (i32, [c_f32p, i64, i32, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                      c_stream]),
+    "rr_analytic_rank_stats_f32": (i32, [c_f32p, i64, i32, c_f32p, c_i32p, i32, i32, C.c_void_p, C.c_void_p, i32, c_f32p, c_f32p,
+                                         c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
     "rr_uq_calibration_f64": (i32, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.c_void_p, C.c_size_t,
                                     C.c_void_p, c_stream]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
