@@ -269,6 +269,9 @@ int rr_linear_f32(const rr_linear_args* args, rr_stream_t stream);
 int64_t rr_mask_bits_row_bytes(int N);
 /* Row blocks (= partial rows written through colsum_partial) of an M-row call. */
 int64_t rr_linear_colsum_rows(int64_t M);
+/* Launches of the split GEMM's fused-tail kernels (w_packed = 2, last k-step with at most 16 live columns) this process has
+ * made: which kernel a request took cannot be told from its result, so tests and tools read this counter around a call. */
+int64_t rr_linear_split_tail_launches(void);
 
 /* Packed weight layout for the straight-line fast path of rr_linear_f32:
  *   dst[r, 0:k1] = L[r, 0:k1];  dst[r, r16(k1) : r16(k1)+k2] = L[r, k1:k1+k2];  zeros elsewhere;

@@ -2,6 +2,7 @@
 // request and enters through rr_linear_split_launch.
 #include "linear_common.h"
 #include <atomic>
+#include <type_traits>
 
 namespace {
 
@@ -14,6 +15,13 @@ namespace {
 // products are exact in f32, and the sum of a k-step is rounded once instead of after every fmaf, so the error
 // against an f64 GEMM is at or BELOW that of the f32 MFMA chain (tests/test_gpu_split.py measures both).  Six bf16
 // MFMAs cost 6/16 of the f32 MFMA's cycles for the same k: the kernel moves from MFMA-bound to HBM-bound.
+// Fused tail: where the LAST k-step has at most 16 live columns (K = 300: 12; also 12 ... 16 past any multiple of 32, and the
+// second segment of 61 | 300) its six products are issued as three MFMAs, two products side by side in the 32 k-slots of one
+// instruction: 57 instead of 60 MFMAs per tile and row block at K = 300 (mfma_block).  It is a compile-time property of the
+// instantiation - the template flag TF, picked by the host in launch_split_tail, with the last step peeled out of the k-loop -
+// because any branch that joins in front of the epilogue with the 76 accumulators live makes hipcc spill hundreds of
+// registers.  Three-bf16-term form of <19,19,MODE 0 / 1 / 3,12,EPI 0 / 1> only.  On by default (launch_split_tail;
+// measured in profiles/tail_fuse_ab.txt): RR_NO_TAIL_FUSE=1 launches the unfused twins.
 //
 // Geometry: workgroup = 12 waves x 16 rows = 192 rows x up to 304 output columns; the activation operand goes
 // global -> registers (each lane loads the 8 consecutive k of ITS row that the MFMA layout hands it, fixes them up
@@ -39,6 +47,15 @@ __host__ __device__ constexpr bool split_balanced(int NTP, int NT, int MODE, int
   return WAVES == 12 && NT == NTP && EPI < 2 && !F16 && !split_can_persist(NTP, NT, MODE, WAVES, EPI);
 }
 
+// Fused tail (see mfma_block): the instantiations of the one-column-block 12-wave geometry that the model launches at H = 300
+// carry a twin (TF) whose LAST k-step issues three MFMAs per tile instead of six; the host picks it when that step has at most
+// 16 live columns (split_tail_live).
+__host__ __device__ constexpr bool split_tail_fusable(int NTP, int NT, int MODE, int WAVES, int EPI, bool F16) {
+  return WAVES == 12 && NT == NTP && MODE != 2 && EPI < 2 && !F16;
+}
+// live columns of the last k-step (it belongs to segment 2 when there is one)
+__host__ __device__ constexpr int split_tail_live(int k1, int k2) { return k2 > 0 ? k2 - (r32(k2) - SK) : k1 - (r32(k1) - SK); }
+
 // NTP: column tiles of the packed weight image; NT: column tiles of ONE workgroup (blockIdx.y picks tiles y * NT ...);
 // WAVES: 16-row groups per workgroup.  Instantiated: <19, 19, 12 waves> - one workgroup per CU (114 KB of LDS) covers all
 // columns of 192 rows - and <10, 10, 8> / <4, 4, 8> for narrow layers.  Cutting the 19 tiles into 10 + 9 (<19, 10, 8>:
@@ -46,8 +63,11 @@ __host__ __device__ constexpr bool split_balanced(int NTP, int NT, int MODE, int
 // both halves load and split the operand rows, 320 vs 236 us on the masked dX GEMM (profiles/r02_experiments.txt).
 // EPI: 0 = accumulator-layout epilogue, 1 = row-contiguous epilogue through LDS (12-wave geometry; chosen per launch,
 // see launch_split_one: separate instantiations keep each epilogue's registers out of the other's kernel)
-template <int NTP, int NT, int MODE, int WAVES, int EPI = 0, bool F16 = false>
+// TF: the last k-step is the fused tail (chosen per launch, launch_split_tail): 0 = no, 1 / 2 = yes, for an odd / even number
+// of k-steps (the peeled step's operand slot is a compile-time property as well: see the k-loop)
+template <int NTP, int NT, int MODE, int WAVES, int EPI = 0, bool F16 = false, int TF = 0>
 __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_kernel(const LinearParams P) {
+  static_assert(TF == 0 || split_tail_fusable(NTP, NT, MODE, WAVES, EPI, F16), "no fused tail for this instantiation");
   constexpr int BN = 16 * NT;
   constexpr int TERMS = F16 ? 2 : 3;                   // operand terms: three bf16 or two f16
   constexpr int PANEL = NT * TERMS * 1024;             // bytes of one k-step's weight image in LDS
@@ -301,7 +321,9 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
     }
   };
   auto issue_w = [&](int s) {                          // weight image of step s: NT * 3 LDS-DMA blocks of 1 KiB over the waves
-    const float* src = wlane + static_cast<int64_t>(s) * (SRC_PANEL / 4);
+    int so = s;                                        // (opaque in the TF twins: with the last step peeled, hipcc hoists the per-lane
+    if (TF != 0) asm volatile("" : "+s"(so));          // addresses of the constant steps out of the block loop and spills them, 34 registers)
+    const float* src = wlane + static_cast<int64_t>(so) * (SRC_PANEL / 4);
     const uint32_t dst = lds0 + (s & 1) * PANEL;
 #pragma unroll
     for (int b0 = 0; b0 < NT * TERMS; b0 += WAVES) {
@@ -394,8 +416,52 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
       }
     }
   };
-  auto mfma_block = [&](int s) {
+  // Fused tail.  K = 300 is 9.4 k-steps: the last one has 12 live columns, all of them in the k-slots of lanes 0-31 (a lane
+  // holds k = (lane >> 4) * 8 ...), and lanes 32-63 of all six operands hold zeros.  An MFMA sums over its 32 k-slots
+  // whatever they hold, so with the first operand [w_a (k 0..15) | w_b (k 0..15)] and the second [x_c (k 0..15) | x_d (k 0..15)]
+  // ONE instruction adds w_a x_c + w_b x_d, and a last step with at most 16 live columns needs three MFMAs per tile,
+  //     c += [w2|w1].[x0|x1]      c += [w0|w1].[x2|x0]      c += [w0|w0].[x1|x0]        (smallest terms first, as in every step)
+  // instead of six: 57 instead of 60 MFMAs per tile and row block at K = 300.  The two products of an instruction are summed
+  // unrounded where the six-MFMA step rounds after each: the last bits may differ from the unfused kernel's (the error
+  // against f64 cannot grow).  Neither operand has another layout for it: the weight operand is a ds_read_b128 of the same
+  // image with another per-lane address - lanes 0-31 their own slot of term a's block, lanes 32-63 slot lane - 32 of term
+  // b's - and the activation operand is one v_permlane32_swap per register, 12 per wave and step, reused over all tiles.
+  // FUSED is a compile-time argument of the peeled last step: a uniform branch here (live <= 16) makes every 12-wave
+  // instantiation spill 200-300 registers - the 76 accumulators cross the join.
+  auto mfma_block = [&](int s, auto fused) {
     if (SHORT && uwave >= nw) return;                   // (uniform) a wave without rows in a short last block: no MFMAs, no LDS reads
+    if constexpr (decltype(fused)::value) {
+      auto halves = [](const u32x4& lo, const u32x4& hi) {   // [lo lanes 0-31 | hi lanes 0-31]
+        u32x4 r;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = __builtin_amdgcn_permlane32_swap(lo[e], hi[e], false, false)[0];
+        return as_bf16x8(r);
+      };
+      const bf16x8 g1 = halves(x0, x1), g2 = halves(x2, x0), g3 = halves(x1, x0);
+      const u32x4* const Wc = reinterpret_cast<const u32x4*>(smem + (s & 1) * PANEL) + (lane & 31);   // [w0|w0]
+      const u32x4* const Wb = Wc + (lane & 32) * 2;                                                   // [w0|w1]
+      const u32x4* const Wa = Wc + 128 - (lane & 32) * 2;                                             // [w2|w1]
+      u32x4 wa = Wa[0], wb = Wb[0], wc = Wc[0];
+      __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const bf16x8 f1 = as_bf16x8(wa), f2 = as_bf16x8(wb), f3 = as_bf16x8(wc);
+        if (j + 1 < NT) {
+          wa = Wa[(j + 1) * 192];
+          wb = Wb[(j + 1) * 192];
+          wc = Wc[(j + 1) * 192];
+        }
+        f32x4 c = acc[j];
+        if (j + 1 == NT && NT != NTP && !full) continue;  // (uniform) the narrower last column block has no tile NT-1
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f1, g1, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f2, g2, c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f3, g3, c, 0, 0, 0);
+        acc[j] = c;
+        if (j + 1 < NT) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
+      }
+      return;
+    }
     const u32x4* Ws = reinterpret_cast<const u32x4*>(smem + (s & 1) * PANEL) + lane;
     if constexpr (F16) {
       const f16x8 h0 = as_f16x8(x0), h1 = as_f16x8(x1);
@@ -477,8 +543,10 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
       rr_glds16(kl + 4 < ks ? p + 4 : rr_zero_row, dst + 1024);
     }
   };
-  auto step = [&](int s, int slot) {
-    const bool more = s + 1 < nk, more2 = s + 2 < nk;
+  // (last: the peeled last step of a TF instantiation, s == nk - 1 - its MFMA block is the fused one)
+  auto step = [&](int s, int slot, auto last) {
+    constexpr bool LAST = decltype(last)::value;
+    const bool more = !LAST && s + 1 < nk, more2 = !LAST && s + 2 < nk;
     const bool wrap = CAN_PERSIST && has_next;         // (uniform) the pipeline runs on into the next row block; nk is even
     // (step 0 of a block entered through the wrap below finds its operand already split by EVERY wave: one register
     // set - x0..x2 - crosses the store epilogue instead of two)
@@ -491,7 +559,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
     } else {
       if (more) issue_x(s + 1, 0);
     }
-    mfma_block(s);
+    mfma_block(s, last);
     if (DEEP && (more2 || (wrap && more))) {           // (the two prefetch DMAs stand in for an issue_x: same count)
       if (NX == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       else if (NX == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
@@ -519,9 +587,23 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES == 8 ? 4 : 3) linear_split_k
   if (CAN_PERSIST) {
     has_next = persist && g_cur + nw < g_end;
   }
-  for (int s = 0; s < nk; s += 2) {
-    step(s, 0);
-    if (s + 1 < nk) step(s + 1, 1);
+  if constexpr (TF != 0) {                              // the last step peeled out of the pairs: its MFMA block is another.  Its
+    int s = 0;                                          // slot (nk odd / even) is the instantiation's too: a branch on nk here joins
+    for (; s + (TF == 1 ? 1 : 2) < nk; s += 2) {        // in front of the epilogue and costs 140 ... 280 spilled registers
+      step(s, 0, std::false_type{});
+      step(s + 1, 1, std::false_type{});
+    }
+    if constexpr (TF == 1) {
+      step(s, 0, std::true_type{});
+    } else {
+      step(s, 0, std::false_type{});
+      step(s + 1, 1, std::true_type{});
+    }
+  } else {
+    for (int s = 0; s < nk; s += 2) {
+      step(s, 0, std::false_type{});
+      if (s + 1 < nk) step(s + 1, 1, std::false_type{});
+    }
   }
   RR_STAMP(2);
 
@@ -835,7 +917,7 @@ inline int split_cus(int dev) {
 // residual), 2 = row-contiguous everywhere it applies.  Measured (profiles/r03_experiments.txt): with a residual read
 // 223 -> 196 us per isolated 139k-row launch; store-only epilogues do not gain and pay the LDS round trip; inside a
 // training step (kernels of three streams interleaved on the chip) the difference is within the noise.
-template <int NTP, int NT, int MODE, int WAVES, int EPI, bool F16>
+template <int NTP, int NT, int MODE, int WAVES, int EPI, bool F16, int TF = 0>
 int launch_split_epi(const LinearParams& P, hipStream_t s) {
   // k-loop: two weight images + the bias slice; the 12-wave geometry's epilogue needs 12 transposition regions of
   // 8 x 77 float4, the column-sum / sign-bit staging and the bias slice (linear_split_kernel, "LDS layout")
@@ -849,7 +931,7 @@ int launch_split_epi(const LinearParams& P, hipStream_t s) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return RR_ERR_LAUNCH;
   if (dev < 0 || dev >= 64 || !((configured.load(std::memory_order_acquire) >> dev) & 1u)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16>),
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16, TF>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
       return RR_ERR_LAUNCH;
     if (dev >= 0 && dev < 64) configured.fetch_or(uint64_t(1) << dev, std::memory_order_release);
@@ -868,7 +950,7 @@ int launch_split_epi(const LinearParams& P, hipStream_t s) {
       Q.persist = 1;
       // every CU an equal share of the 64-row units (the granularity of the column-sum partials)
       const dim3 grid(static_cast<unsigned>(cus), 1);
-      linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16><<<grid, 64 * WAVES, smem, s>>>(Q);
+      linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16, TF><<<grid, 64 * WAVES, smem, s>>>(Q);
       return rr_launch_status();
     }
   }
@@ -888,15 +970,30 @@ int launch_split_epi(const LinearParams& P, hipStream_t s) {
       Q.bal_base = static_cast<int>(tail / cus);
       Q.bal_rem = static_cast<int>(tail % cus);
       const dim3 grid(static_cast<unsigned>(full + (Q.bal_base > 0 ? cus : Q.bal_rem)), 1);
-      linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16><<<grid, 64 * WAVES, smem, s>>>(Q);
+      linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16, TF><<<grid, 64 * WAVES, smem, s>>>(Q);
       return rr_launch_status();
     }
   }
   // (two column blocks: ids i, i + 8 of a 1-D grid are one row block's pair - see the kernel)
   const dim3 grid = NTP == 2 * NT ? dim3(static_cast<unsigned>((nblk + 7) / 8 * 16), 1)
                                   : dim3(static_cast<unsigned>(nblk), static_cast<unsigned>((NTP + NT - 1) / NT));
-  linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16><<<grid, 64 * WAVES, smem, s>>>(P);
+  linear_split_kernel<NTP, NT, MODE, WAVES, EPI, F16, TF><<<grid, 64 * WAVES, smem, s>>>(P);
   return rr_launch_status();
+}
+// Fused tail (see the kernel's mfma_block): the TF twin where the instantiation has one and the last k-step has at most 16
+// live columns (K = 300: 12; not K = 83, 61 or 600).  Knobs, read per launch: RR_NO_TAIL_FUSE keeps the six-MFMA step
+// everywhere, RR_TAIL_FUSE asks for the twins where SPLIT_TAIL_FUSE_DEFAULT does not.
+constexpr bool SPLIT_TAIL_FUSE_DEFAULT = true;           // (every twin's per-launch gain is measured: profiles/tail_fuse_ab.txt section 3)
+std::atomic<int64_t> split_tail_launches{0};             // rr_linear_split_tail_launches
+template <int NTP, int NT, int MODE, int WAVES, int EPI, bool F16>
+int launch_split_tail(const LinearParams& P, hipStream_t s) {
+  if constexpr (split_tail_fusable(NTP, NT, MODE, WAVES, EPI, F16)) {
+    if (split_tail_live(P.a.k1, P.a.k2) <= 16 && !getenv("RR_NO_TAIL_FUSE") && (SPLIT_TAIL_FUSE_DEFAULT || getenv("RR_TAIL_FUSE"))) {
+      split_tail_launches.fetch_add(1, std::memory_order_relaxed);
+      return (P.t1 + P.t2) % 2 != 0 ? launch_split_epi<NTP, NT, MODE, WAVES, EPI, F16, 1>(P, s) : launch_split_epi<NTP, NT, MODE, WAVES, EPI, F16, 2>(P, s);
+    }
+  }
+  return launch_split_epi<NTP, NT, MODE, WAVES, EPI, F16>(P, s);
 }
 template <int NTP, int NT, int MODE, int WAVES, bool F16>
 int launch_split_one(const LinearParams& P, hipStream_t s) {
@@ -907,9 +1004,9 @@ int launch_split_one(const LinearParams& P, hipStream_t s) {
     const bool lean = split_lean(P.a.k1, P.a.k2);
     constexpr int E1 = (WAVES == 12 && (MODE == 0 || MODE == 1)) ? 1 : 0, G = (WAVES == 12 && (MODE == 0 || MODE == 1)) ? 2 : 0;
     if (!lean) return rs ? launch_split_epi<NTP, NT, MODE, WAVES, G + E1, F16>(P, s) : launch_split_epi<NTP, NT, MODE, WAVES, G, F16>(P, s);
-    if (rs) return launch_split_epi<NTP, NT, MODE, WAVES, E1, F16>(P, s);
+    if (rs) return launch_split_tail<NTP, NT, MODE, WAVES, E1, F16>(P, s);
   }
-  return launch_split_epi<NTP, NT, MODE, WAVES, 0, F16>(P, s);
+  return launch_split_tail<NTP, NT, MODE, WAVES, 0, F16>(P, s);
 }
 template <int NTP, int NT, int WAVES, bool F16>
 int launch_split(const LinearParams& P, hipStream_t s) {
@@ -937,6 +1034,8 @@ extern "C" {
 #ifdef RR_TRACE
 int rr_trace_set_linear_split(unsigned long long* buf) { return rr_trace_set_unit(buf); }
 #endif
+
+int64_t rr_linear_split_tail_launches(void) { return split_tail_launches.load(std::memory_order_relaxed); }
 
 // rr_linear_f32 (linear.hip) has checked the request; k-tiles are k-steps of SK here
 int rr_linear_split_launch(const rr_linear_args* args, int two_f16, rr_stream_t stream) {
