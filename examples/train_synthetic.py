@@ -5,11 +5,12 @@ build_model -> build_optimizer -> build_lr_scheduler -> train -> checkpoint, mai
     python examples/train_synthetic.py --task-type mle --epochs 5 --queries 256 --cands 32
 
 The pairwise trainer's selectors (run_train_pairwise.run_train) are reached with --task-type ranknet (--train-strategy
-sum_session | accelerate_grad | lambdarank, the last with --ndcg-k), betanet, betanet_evidential, or pair_baseline (the
-three-graph pair model):
+sum_session | accelerate_grad | lambdarank | approx_ndcg, the last two with --ndcg-k, the last with --temperature), betanet,
+betanet_evidential, or pair_baseline (the three-graph pair model):
 
     python examples/train_synthetic.py --task-type betanet --epochs 3 --queries 64 --cands 8
     python examples/train_synthetic.py --task-type ranknet --train-strategy lambdarank --ndcg-k 10 --epochs 3 --queries 64 --cands 32
+    python examples/train_synthetic.py --task-type ranknet --train-strategy approx_ndcg --temperature 0.5 --epochs 3 --queries 64 --cands 32
 
 Under `python -m torch.distributed.run --nproc-per-node N examples/train_synthetic.py ...` the listwise task types train data
 parallel: every rank builds the same batches and keeps its block of whole queries of each (dp.shard_query_batch).  Backend:
@@ -87,8 +88,9 @@ def head_for(task_type):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--task-type", default="mle")
-    ap.add_argument("--train-strategy", default="sum_session", help="with --task-type ranknet: sum_session | accelerate_grad | lambdarank")
-    ap.add_argument("--ndcg-k", type=int, default=0, help="with --train-strategy lambdarank: NDCG truncation (0: the whole list)")
+    ap.add_argument("--train-strategy", default="sum_session", help="with --task-type ranknet: sum_session | accelerate_grad | lambdarank | approx_ndcg")
+    ap.add_argument("--ndcg-k", type=int, default=0, help="with --train-strategy lambdarank | approx_ndcg: NDCG truncation (0: the whole list)")
+    ap.add_argument("--temperature", type=float, default=1.0, help="with --train-strategy approx_ndcg: soft-rank temperature, in score units")
     ap.add_argument("--pair-batch", type=int, default=256, help="with --task-type pair_baseline: pairs per optimizer step")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--queries", type=int, default=256)
@@ -131,7 +133,7 @@ def main():
         strategy, task = PAIRWISE[args.task_type]
         hist = run_train(model, sch, train_b, val_b, args.checkpoint, opt, args.epochs, seed=0, gpu=args.gpu,
                          train_strategy=strategy or args.train_strategy, task_type=task, logger=log, target_name=None,
-                         batch_size=args.pair_batch, val_batch_size=args.pair_batch, ndcg_k=args.ndcg_k)
+                         batch_size=args.pair_batch, val_batch_size=args.pair_batch, ndcg_k=args.ndcg_k, temperature=args.temperature)
         key = "acc" if args.task_type == "pair_baseline" else "top1"
         best = max(hist, key=lambda h: h[key])
         log.info("best epoch %d: %s %.4f", best["epoch"], key, best[key])

@@ -559,6 +559,64 @@ int rr_lambdarank_step_f32(const float* score, int64_t score_stride, const float
                            float* loss, int64_t* pairs, float* partial /* [2*Q] */, unsigned int* counter,
                            float* dscore, int64_t dscore_stride, rr_stream_t stream);
 
+/* Soft ranks and ApproxNDCG (additive: eight new symbols, the ABI revision stays 8).  This library's own definitions (the
+ * reference trainer has neither).  For one query of C candidates with float32 scores s and a temperature T > 0, in score units
+ * (a T that is large against the spread of the scores blurs every rank towards (C + 1) / 2):
+ *   u_ij    (s_j - s_i) / T
+ *   r_i     1 + sum_{j != i} sigmoid(u_ij)                         the soft rank; ties get equal ranks, sum_i r_i = C (C + 1) / 2
+ *   d L / d s_k = (1 / T) sum_{j != k} sigmoid'(u_kj) (a_j - a_k)   for an upstream gradient a_i = d L / d r_i (sigmoid' is even);
+ *                                                                  it sums to zero over the query
+ * ApproxNDCG writes NDCG on the soft ranks.  With targets t, k = C for ndcg_k == 0 and min(ndcg_k, C) otherwise:
+ *   g_i     exp(t_i - max_j t_j)                                   (rr_lambdarank_fwd_f32's gains and maxDCG)
+ *   maxDCG  sum_{p = 1..k} g_(p) / log2(1 + p), g_(p) the p-th largest gain
+ *   G_i     g_i / maxDCG
+ *   psi(r)  1 / log2(1 + r)                                        for ndcg_k == 0 or ndcg_k >= C
+ *           sigmoid(k + 1/2 - r) / log2(1 + r)                     for 0 < ndcg_k < C: a smooth gate, one rank wide and fixed
+ *   loss_q  1 - sum_i G_i psi(r_i),   a_i = -G_i psi'(r_i),   and d loss_q / d s follows from the soft-rank formula.
+ * A query is RANKED when some t_i > t_j (RankNet's pairs_q > 0).  An unranked query (empty, one candidate, all targets equal)
+ * adds 0 to the loss and to `ranked`, and every gradient entry it owns is WRITTEN as 0 (dscore may be uninitialised memory).
+ * Arithmetic: per pair, in float32, the margin, one expf, e = exp(-|u|), sigmoid = 1 / (1 + e) or e / (1 + e) by the sign of u
+ * and sigmoid' = e / (1 + e)^2; the sums over j, every O(C) quantity (gain, maxDCG, log2, gate, psi' - stored once as a
+ * float) and the loss sum in float64.  One workgroup per query: one wavefront for max_len <= 64, four above.  partial is
+ * [2 * Q] (loss_q as a float, ranked as an int32), finished in a fixed order: run-to-run identical bits, no float atomics.
+ * LDS 20 * max_len bytes (soft ranks: 4, their backward: 8).
+ *   soft_rank_fwd   rank[i * rank_stride] = r_i.
+ *   soft_rank_bwd   dscore = d L / d score for drank = d L / d rank.
+ *   fwd     loss_sum = sum_q loss_q, ranked = the number of ranked queries.
+ *   bwd     dscore = gloss[0] * d loss_sum / d score.
+ *   step    one launch: loss = scale * loss_sum, ranked, and dscore = scale * d loss_sum / d score - the bits of fwd followed by
+ *           bwd with *gloss == scale.  `scale` is a host value (a trainer passes 1 / the window's query count, so the losses
+ *           and gradients of the shards of a window add up).  `counter` as for rr_listmle_step_f32.
+ *   ranks   a[i * a_stride] = a_i, the gradient of loss_sum in the soft ranks (0 for an unranked query).
+ *   waves / set_waves   the wave count of the launches that follow: 0 = by max_len as above, 1 or 4 = that count whatever the
+ *           length.  One process-wide word that every launch reads, NOT thread-safe: set it from one thread with no launch
+ *           of this family in flight on another; it is there for the bench tool and the tests, to time and compare both
+ *           forms of one build.  set_waves returns RR_ERR_ARG for anything else.
+ * Status: RR_ERR_ARG for a null pointer, a stride < 1, Q < 0, a temperature that is not a positive finite number with a
+ * finite float32 reciprocal (the kernels multiply the margins by 1 / T: T >= 2.94e-39 = 1 / FLT_MAX, inside the subnormals) or
+ * ndcg_k < 0; max_len > 8192 -> RR_ERR_UNSUPPORTED, nothing is launched; Q == 0 writes a zero loss and count (fwd, step) or
+ * launches nothing. */
+int rr_soft_rank_fwd_f32(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len,
+                         float temperature, float* rank, int64_t rank_stride, rr_stream_t stream);
+int rr_soft_rank_bwd_f32(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len,
+                         float temperature, const float* drank, int64_t drank_stride, float* dscore, int64_t dscore_stride,
+                         rr_stream_t stream);
+int rr_approx_ndcg_fwd_f32(const float* score, int64_t score_stride, const float* targets,
+                           const int32_t* seg_off, int Q, int max_len, float temperature, int ndcg_k,
+                           float* loss_sum, int64_t* ranked, float* partial /* [2*Q] */, rr_stream_t stream);
+int rr_approx_ndcg_bwd_f32(const float* score, int64_t score_stride, const float* targets,
+                           const int32_t* seg_off, int Q, int max_len, float temperature, int ndcg_k,
+                           const float* gloss, float* dscore, int64_t dscore_stride, rr_stream_t stream);
+int rr_approx_ndcg_step_f32(const float* score, int64_t score_stride, const float* targets,
+                            const int32_t* seg_off, int Q, int max_len, float temperature, int ndcg_k, float scale,
+                            float* loss, int64_t* ranked, float* partial /* [2*Q] */, unsigned int* counter,
+                            float* dscore, int64_t dscore_stride, rr_stream_t stream);
+int rr_approx_ndcg_ranks_f32(const float* score, int64_t score_stride, const float* targets,
+                             const int32_t* seg_off, int Q, int max_len, float temperature, int ndcg_k,
+                             float* a, int64_t a_stride, rr_stream_t stream);
+int rr_approx_ndcg_waves(void);
+int rr_approx_ndcg_set_waves(int waves);
+
 /* Pointwise: nn.MSELoss (train/train_listwise.py:166-167) and GaussDisLoss (train/loss.py:154-162).
  * partial: rr_pointwise_partial_count(n) floats. */
 int64_t rr_pointwise_partial_count(int64_t n);

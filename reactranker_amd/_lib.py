@@ -227,6 +227,15 @@ _SIGS = {
     "rr_lambdarank_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, c_f32p, c_f32p, i64, c_stream]),
     "rr_lambdarank_step_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, f32, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
                                      c_f32p, i64, c_stream]),
+    "rr_soft_rank_fwd_f32": (i32, [c_f32p, i64, c_i32p, i32, i32, f32, c_f32p, i64, c_stream]),
+    "rr_soft_rank_bwd_f32": (i32, [c_f32p, i64, c_i32p, i32, i32, f32, c_f32p, i64, c_f32p, i64, c_stream]),
+    "rr_approx_ndcg_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, c_f32p, C.c_void_p, c_f32p, c_stream]),
+    "rr_approx_ndcg_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, c_f32p, c_f32p, i64, c_stream]),
+    "rr_approx_ndcg_step_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, f32, c_f32p, C.c_void_p, c_f32p, C.c_void_p,
+                                      c_f32p, i64, c_stream]),
+    "rr_approx_ndcg_ranks_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, i32, c_f32p, i64, c_stream]),
+    "rr_approx_ndcg_waves": (i32, []),
+    "rr_approx_ndcg_set_waves": (i32, [i32]),
     "rr_betanet_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
     "rr_betanet_bwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, c_f32p, i64, c_stream]),
     "rr_beta_evidential_fwd_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, f32, c_f32p, C.c_void_p, C.c_void_p, c_stream]),

@@ -391,6 +391,124 @@ def lambdarank_loss(y_pred, scope, targets, sigma: float = 1.0, ndcg_k: int = 0,
     return _LambdaRankFn.apply(y_pred, t, seg, len(scope), max_len, sigma, int(ndcg_k), scale)
 
 
+def _temperature(temperature, what) -> float:
+    # judged as the float32 the kernels get, by rr_soft_rank_fwd_f32's rule: they multiply by 1 / T, which has to be finite
+    with np.errstate(all="ignore"):
+        t = np.float32(temperature)
+        ok = t > 0 and np.isfinite(t) and np.isfinite(np.float32(1.0) / t)
+    if not ok:
+        raise ValueError(f"{what}: temperature must be a positive finite float32 with a finite reciprocal (score units)")
+    return float(temperature)
+
+
+class _SoftRankFn(torch.autograd.Function):
+    """rr_soft_rank_fwd_f32 / rr_soft_rank_bwd_f32 (csrc/approx_ndcg.hip)"""
+
+    @staticmethod
+    def forward(ctx, score, seg, Q, max_len, temperature):
+        s = _vec(score.detach())
+        rank = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+        args = [ptr(s), s.stride(0), ptr(seg), Q, max_len, temperature]
+        _call("rr_soft_rank_fwd_f32", *args, ptr(rank), 1)
+        ctx.save_for_backward(s, seg)
+        ctx.args = args
+        return rank
+
+    @staticmethod
+    def backward(ctx, g):
+        s = ctx.saved_tensors[0]                         # (the saved tensors keep the pointers in `args` alive)
+        g = g.float().contiguous()
+        d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+        _call("rr_soft_rank_bwd_f32", *ctx.args, ptr(g), 1, ptr(d), 1)
+        return (d,) + (None,) * 4
+
+
+def soft_rank(y_pred, scope, temperature: float = 1.0, gpu: int = None):
+    """Differentiable ranks of every candidate inside its query: r_i = 1 + sum_{j != i} sigmoid((s_j - s_i) / T), 1 for the
+    best score; float32 [M], differentiable in `y_pred`.  Tied scores get equal ranks and the ranks of a query of C candidates
+    sum to C (C + 1) / 2.  `temperature` is in SCORE units: against a spread of the scores much smaller than T every rank
+    blurs towards (C + 1) / 2, and as T -> 0 the ranks become the hard ones (and the gradient vanishes).  Soft Spearman, soft
+    top-k recall and the like are a few lines of torch on top.  `y_pred` may be [M] or [M, k] (first column, read in place).
+    DESIGN section 4b."""
+    if y_pred.dim() > 1:
+        y_pred = y_pred[:, 0]
+    temperature = _temperature(temperature, "soft_rank")
+    if gpu is not None:
+        torch.cuda.set_device(gpu)
+    _lib.require_cuda(y_pred, "y_pred")
+    scope = tuple(int(c) for c in (scope.tolist() if hasattr(scope, "tolist") else scope))
+    seg, total, max_len = _segments(scope, str(y_pred.device))
+    if total != y_pred.shape[0]:
+        raise RuntimeError(f"sum(scope) = {total} but y_pred has {y_pred.shape[0]} rows")
+    return _SoftRankFn.apply(y_pred, seg, len(scope), max_len, temperature)
+
+
+class _ApproxNdcgFn(torch.autograd.Function):
+    """scale * loss_sum of ApproxNDCG (csrc/approx_ndcg.hip) and the window's ranked queries; the launches of _LambdaRankFn:
+    rr_approx_ndcg_step_f32 when the score wants a gradient and FusedStep is on, else rr_approx_ndcg_fwd_f32, and
+    rr_approx_ndcg_bwd_f32 with the upstream gradient times `scale` - the same bits for an upstream gradient of one."""
+
+    @staticmethod
+    def forward(ctx, score, targets, seg, Q, max_len, temperature, ndcg_k, scale):
+        s = _vec(score.detach())
+        loss = _f1(s.device)
+        ranked = torch.empty(1, dtype=torch.int64, device=s.device)
+        part = torch.empty(max(2 * Q, 2), dtype=torch.float32, device=s.device)
+        args = [ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, temperature, int(ndcg_k)]
+        ctx.ds_unit = None
+        if FusedStep.enabled and ctx.needs_input_grad[0]:
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call("rr_approx_ndcg_step_f32", *args, scale, ptr(loss), ptr(ranked), ptr(part), ptr(_counter(s.device)), ptr(d), 1)
+            ctx.ds_unit = d
+        else:
+            _call("rr_approx_ndcg_fwd_f32", *args, ptr(loss), ptr(ranked), ptr(part))
+            if scale != 1.0:
+                loss = loss * scale                      # (a float32 product, as in the step kernel)
+        ctx.save_for_backward(s, targets, seg)
+        ctx.meta = (args, scale)
+        ctx.mark_non_differentiable(ranked)
+        return loss.reshape(()), ranked
+
+    @staticmethod
+    def backward(ctx, g, _gr):
+        if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
+            d, ctx.ds_unit = ctx.ds_unit, None
+            FusedStep.hits += 1
+        else:
+            s = ctx.saved_tensors[0]
+            args, scale = ctx.meta
+            g = (g.reshape(-1).float() * scale).contiguous()
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call("rr_approx_ndcg_bwd_f32", *args, ptr(g), ptr(d), 1)
+        return (d,) + (None,) * 7
+
+
+def approx_ndcg_loss(y_pred, scope, targets, temperature: float = 1.0, ndcg_k: int = 0, gpu: int = None, queries: int = None):
+    """ApproxNDCG over a window of queries: per ranked query 1 - sum_i G_i psi(r_i), the NDCG that `ranking_metrics` reports
+    (gains exp(target), truncated at `ndcg_k` positions, 0: the whole list) written on the soft ranks r_i of `soft_rank`, so
+    the gradient flows through the ranks; inside the list the truncation is a smooth gate sigmoid(k + 1/2 - r), one rank wide.
+    `temperature` is in SCORE units (see soft_rank): small against the score differences the loss approaches 1 - NDCG and its
+    gradient vanishes, large it blurs the ranks.  The definition is in DESIGN section 4b.  This library's own loss.
+
+    Returns (loss, ranked_tensor).  queries=None: loss is the plain sum over the queries.  queries: a host int, the query count
+    to normalise by (the WINDOW's count for a shard of a data-parallel step) - loss is the sum * float32(1 / queries) and
+    `backward(loss)` then takes the gradient the same launch wrote (FusedStep).  ranked_tensor is this call's number of ranked
+    queries (those with two different targets; the others add nothing and get a zero gradient), an int64 device scalar.
+    `y_pred` may be [M] or [M, k] (first column, read in place)."""
+    if y_pred.dim() > 1:
+        y_pred = y_pred[:, 0]
+    temperature = _temperature(temperature, "approx_ndcg_loss")
+    if int(ndcg_k) != ndcg_k or ndcg_k < 0:
+        raise ValueError("approx_ndcg_loss: ndcg_k must be a non-negative integer (0: the whole list)")
+    scale = 1.0
+    if queries is not None:
+        if int(queries) != queries or int(queries) <= 0:
+            raise ValueError("approx_ndcg_loss: queries must be a positive count")
+        scale = float(np.float32(1.0 / int(queries)))
+    scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
+    return _ApproxNdcgFn.apply(y_pred, t, seg, len(scope), max_len, temperature, int(ndcg_k), scale)
+
+
 # ---------------------------------------------------------------------------------------------- the remaining task types' losses
 def annealing_coef(max_coeff, epoch, epochs):
     """The annealing coefficient of Listnet_with_uq / Dirichlet_uq (reference train/loss.py:393, 468), computed on the host as

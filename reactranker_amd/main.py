@@ -36,8 +36,9 @@ class Config:
     batch_size: int = 64                        # queries per optimizer step (only enters the LR schedule here)
     task_type: str = "listnet"                  # loss: mle / listnet / evidential_ranking / regression / ... ; 'ranknet'
     train_strategy: str = "sum_session"         # RankNet only (main_ranknet.py:38): 'sum_session' | 'accelerate_grad' |
-                                                # 'lambdarank' (this library's NDCG-weighted pair loss)
-    ndcg_k: int = 0                             # train_strategy 'lambdarank': NDCG truncation, 0 = the whole list
+                                                # 'lambdarank' (this library's NDCG-weighted pair loss) | 'approx_ndcg' (its
+                                                # smooth NDCG on soft ranks)
+    ndcg_k: int = 0                             # train_strategy 'lambdarank' / 'approx_ndcg': NDCG truncation, 0 = the whole list
     pairwise_task_type: str = "baseline"        # task_type 'ranknet' only: run_train's task_type - 'baseline' | 'BetaNet' |
                                                 # 'BetaNet_envidential' (run_train_pairwise.py:66-90)
     target_name: Optional[str] = "lgk"          # None: targets are already standardised
@@ -52,6 +53,7 @@ class Config:
     model: dict = field(default_factory=lambda: dict(hidden_size=300, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3,
                                                      use_bias=True, dropout=0.1, task_num=1,
                                                      ffn_last_layer="with_softplus"))
+    temperature: float = 1.0                    # train_strategy 'approx_ndcg': the soft ranks' temperature, in score units
 
 
 def test(model, test_batches: Sequence, path_checkpoints: str, gpu: int, logger=None, target_name: Optional[str] = "ea",
@@ -134,7 +136,8 @@ def run(cfg: Config, folds: Callable[[int], Tuple[Sequence, Sequence, Sequence]]
         if cfg.task_type == "ranknet":
             run_train(model, scheduler, train_b, val_b, ck, optimizer, cfg.total_epochs, seed, cfg.gpu,
                       train_strategy=cfg.train_strategy, task_type=cfg.pairwise_task_type, logger=logger,
-                      target_name=cfg.target_name, save_metric=cfg.save_metric, group=group, ndcg_k=cfg.ndcg_k)
+                      target_name=cfg.target_name, save_metric=cfg.save_metric, group=group, ndcg_k=cfg.ndcg_k,
+                      temperature=cfg.temperature)
         else:
             train(model, scheduler, train_b, val_b, ck, optimizer, cfg.total_epochs, seed, cfg.gpu,
                   task_type=cfg.task_type, logger=logger, save_metric=cfg.save_metric, target_name=cfg.target_name,

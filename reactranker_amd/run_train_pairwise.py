@@ -31,13 +31,14 @@ def run_train(model: torch.nn.Module, scheduler, train_batches: Sequence, val_ba
               path_checkpoints: Union[str, List[str], None], optimizer, epochs: int, seed: int, gpu: int,
               train_strategy: str = "sum_session", task_type: str = "baseline", logger=None,
               target_name: Optional[str] = "ea", save_metric: Optional[str] = None, sigma: float = 1.0, epoch_hook=None,
-              group=None, batch_size: int = 1000, val_batch_size: int = 500, ndcg_k: int = 0):
+              group=None, batch_size: int = 1000, val_batch_size: int = 500, ndcg_k: int = 0, temperature: float = 1.0):
     """Selectors as in the reference (:66-90): task_type 'BetaNet' -> beta_dis_train_loop (alpha0 = 100), 'BetaNet_envidential' ->
     beta_evi_train_loop (max_coeff = 0.01; needs epochs >= 2 and a positive head), otherwise task_type 'baseline' with
     train_strategy 'sum_session' / 'accelerate_grad' -> factorized_training_loop or 'baseline' -> the pair model's
     baseline_pairwise_training_loop.  train_strategy 'lambdarank' (task_type 'baseline'; not in the reference) runs
-    factorized_training_loop on the NDCG-weighted pair loss, truncated at `ndcg_k` positions (0: the whole list).  Anything else
-    is a ValueError.
+    factorized_training_loop on the NDCG-weighted pair loss, truncated at `ndcg_k` positions (0: the whole list);
+    train_strategy 'approx_ndcg' (likewise) runs it on ApproxNDCG, one minus the NDCG at `ndcg_k` on soft ranks of
+    `temperature` (score units).  Anything else is a ValueError.
 
     train_strategy 'baseline': `model` is a reactranker_amd.ranknet_baseline model and every window also carries `mols_r` /
     `mols_p`, the reactant / product graph of each candidate; after the targets are standardised the pairs of all training
@@ -66,23 +67,23 @@ def run_train(model: torch.nn.Module, scheduler, train_batches: Sequence, val_ba
             return _run_train_pairs(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu,
                                     logger, target_name, epoch_hook, ex, batch_size, val_batch_size)
         return _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, selector,
-                          logger, target_name, save_metric, sigma, epoch_hook, ex, ndcg_k)
+                          logger, target_name, save_metric, sigma, epoch_hook, ex, ndcg_k, temperature)
     finally:
         ex.close()
 
 
 def select_loop(train_strategy: str, task_type: str) -> str:
     """The reference's if / elif chain (:66-90) as one name: 'pair_baseline', 'sum_session', 'accelerate_grad', 'BetaNet' or
-    'BetaNet_envidential' - and 'lambdarank', this library's addition; ValueError for anything the reference's chain would fall
-    through."""
+    'BetaNet_envidential' - and 'lambdarank' and 'approx_ndcg', this library's additions; ValueError for anything the
+    reference's chain would fall through."""
     if task_type == "baseline" and train_strategy == "baseline":
         return "pair_baseline"
-    if task_type == "baseline" and train_strategy in ("sum_session", "accelerate_grad", "lambdarank"):
+    if task_type == "baseline" and train_strategy in ("sum_session", "accelerate_grad", "lambdarank", "approx_ndcg"):
         return train_strategy
     if task_type in ("BetaNet", "BetaNet_envidential"):
         return task_type
     raise ValueError("reactranker_amd covers the reference's pairwise selectors: train_strategy 'baseline' / 'sum_session' / "
-                     "'accelerate_grad' (and its own 'lambdarank') with task_type 'baseline', or task_type 'BetaNet' / "
+                     "'accelerate_grad' (and its own 'lambdarank' / 'approx_ndcg') with task_type 'baseline', or task_type 'BetaNet' / "
                      "'BetaNet_envidential' "
                      f"(got train_strategy {train_strategy!r}, task_type {task_type!r})")
 
@@ -134,7 +135,7 @@ def _run_train_pairs(model, scheduler, train_batches, val_batches, path_checkpoi
 
 
 def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, optimizer, epochs, gpu, train_strategy, logger,
-               target_name, save_metric, sigma, epoch_hook, ex, ndcg_k=0):
+               target_name, save_metric, sigma, epoch_hook, ex, ndcg_k=0, temperature=1.0):
     mean, std = 0.0, 1.0
     if target_name is not None:
         # same statistics as the listwise trainer's default branch: z-score, sign flipped unless 'lgk' (:39-44)
@@ -156,7 +157,8 @@ def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, o
                                              gpu=gpu, exchange=ex)
         else:
             epoch_loss = factorized_training_loop(epoch, model, optimizer, scheduler, train_batches, sigma=sigma,
-                                                  training_algo=train_strategy, gpu=gpu, exchange=ex, ndcg_k=ndcg_k)
+                                                  training_algo=train_strategy, gpu=gpu, exchange=ex, ndcg_k=ndcg_k,
+                                                  temperature=temperature)
         model.eval()
         with torch.no_grad():
             # evaluate_top_scores, not ranking_metrics (:91-96): its third value is the TARGET's top-1 inside the

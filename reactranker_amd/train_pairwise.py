@@ -16,17 +16,20 @@ from typing import Iterable
 
 import torch
 
-from .loss import (annealing_coef, backward as loss_backward, beta_evidential_loss, betanet_loss, lambdarank_loss,
-                   pair_softmax_mse, ranknet_lambda, ranknet_loss, sq_pairs)
+from .loss import (annealing_coef, approx_ndcg_loss, backward as loss_backward, beta_evidential_loss, betanet_loss,
+                   lambdarank_loss, pair_softmax_mse, ranknet_lambda, ranknet_loss, sq_pairs)
 
 
 def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, sigma: float = 1.0,
-                             training_algo: str = "sum_session", gpu: int = 0, exchange=None, ndcg_k: int = 0) -> float:
+                             training_algo: str = "sum_session", gpu: int = 0, exchange=None, ndcg_k: int = 0,
+                             temperature: float = 1.0) -> float:
     """One epoch; returns the mean of the per-step losses like the reference (:173).
     training_algo: 'sum_session' (autograd through the pair losses, :117-122,147-148), 'accelerate_grad'
     (closed-form lambdas pushed through y_pred.backward, :123-137,149-151) or 'lambdarank' (not in the reference: the pair
     costs of 'sum_session' weighted by |delta NDCG| truncated at `ndcg_k` positions, 0 = the whole list -
-    reactranker_amd.loss.lambdarank_loss; loss and gradient come from one launch).
+    reactranker_amd.loss.lambdarank_loss; loss and gradient come from one launch) or 'approx_ndcg' (not in the reference
+    either: one minus the NDCG at `ndcg_k` written on soft ranks of `temperature`, in score units -
+    reactranker_amd.loss.approx_ndcg_loss; one launch as well, normalised by the window's QUERY count).
 
     The window's ordered-pair count - the loss's normaliser (:106,147) and the reason a window is skipped (:101-103) - is
     counted on the host from the targets the batch carries (dp.count_pairs, cached on the batch), and the per-step losses
@@ -34,7 +37,7 @@ def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: I
     exchange: a reactranker_amd.dp.Exchange; a batch is then this rank's shard of the window and the normaliser is the
     whole window's pair count."""
     from .dp import Exchange, step_counts
-    if training_algo not in ("sum_session", "accelerate_grad", "lambdarank"):
+    if training_algo not in ("sum_session", "accelerate_grad", "lambdarank", "approx_ndcg"):
         raise ValueError("training algo {} not implemented".format(training_algo))
     own_exchange = exchange is None
     ex = exchange if exchange is not None else Exchange(model)   # (under torch.distributed it owns the gradient bucket)
@@ -56,6 +59,9 @@ def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: I
             if training_algo == "lambdarank":
                 loss, _ = lambdarank_loss(y_pred, b["scope"], b["targets"], sigma, ndcg_k, gpu, pairs=pairs)
                 loss_backward(loss)
+            elif training_algo == "approx_ndcg":
+                loss, _ = approx_ndcg_loss(y_pred, b["scope"], b["targets"], temperature, ndcg_k, gpu, queries=glob["queries"])
+                loss_backward(loss)
             else:
                 loss_sum, _ = ranknet_loss(y_pred if training_algo == "sum_session" else y_pred.detach(), b["scope"],
                                            b["targets"], sigma, gpu)
@@ -68,7 +74,7 @@ def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: I
             minibatch_loss.append(loss.detach().sum().reshape(1))
         else:                                            # this rank's shard has no ordered pair: zero gradient, zero loss
             minibatch_loss.append(torch.zeros(1, device=dev))
-        ex.reduce_grads(1.0)                             # already normalised by the WINDOW's pair count: a plain sum
+        ex.reduce_grads(1.0)                             # already normalised by the WINDOW's count: a plain sum
         optimizer.step()
         scheduler.step()
     model.zero_grad()
