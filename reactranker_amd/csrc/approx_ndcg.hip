@@ -17,8 +17,9 @@
 // Arithmetic: a pair's margin, its one expf and the sigmoid or its derivative in the e = exp(-|u|) form are float32; the sums
 // over j, the O(C) quantities (gain, log2, gate, psi', maxDCG - each stored once as a float) and the loss sum are float64.
 // No float atomics and no store behind a comparison: ties, NaNs and unranked queries change values, never addresses.
-// The per-query partials [2 * Q] (loss as a float, ranked as an int32) are finished in fixed_sum's order by a second launch
-// (fwd) or by the workgroup that arrives last (step): the same bits on every run and in both forms.
+// The per-query partials [2 * Q] (loss as a float, ranked as an int32) are finished by finish_counted (loss_list.h, the finish
+// RankNet and LambdaRank share) in a second launch (fwd) or by the workgroup that arrives last (step): the same bits on every
+// run and in both forms.
 #include "loss_list.h"
 
 namespace {
@@ -146,25 +147,6 @@ __device__ inline void psi_of(double r, int k, bool gated, double* psi, double* 
   *dpsi = -dsg / l2 - sg * dl2 / (l2 * l2);                        // d gate / d r = -sigmoid'(z)
 }
 
-// loss = scale * sum of the float halves of partial[2 * n] in reduce_scale_kernel's order, ranked = sum of the int32 halves
-// (LambdaRank's finish, on this loss's count)
-__device__ inline void approx_finish(const float* partial, int n, float scale, float* loss, int64_t* ranked, int lane) {
-  const float sum = fixed_sum(partial, n, lane, 2);
-  long long nr = 0;
-  for (int i = lane; i < n; i += RR_WAVE) nr += reinterpret_cast<const int32_t*>(partial)[2 * i + 1];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) nr += __shfl_xor(nr, o, RR_WAVE);
-  if (lane == 0) {
-    loss[0] = n > 0 ? sum * scale : 0.f;
-    ranked[0] = nr;
-  }
-}
-
-__global__ void __launch_bounds__(RR_WAVE) approx_finish_kernel(const float* __restrict__ partial, int n, float scale,
-                                                                float* __restrict__ loss, int64_t* __restrict__ ranked) {
-  approx_finish(partial, n, scale, loss, ranked, threadIdx.x);
-}
-
 struct ApproxArgs {
   const float* score;      // [M] with stride sstride
   int64_t sstride;
@@ -277,7 +259,7 @@ __global__ void __launch_bounds__(NW * RR_WAVE) approx_ndcg_kernel(const ApproxA
     if (tid < RR_WAVE) {
       const int n = gridDim.x;
       if (arrive_last(n, p.counter, tid)) {
-        approx_finish(p.partial, n, p.scale, p.loss, p.ranked, tid);
+        finish_counted(p.partial, n, p.scale, p.loss, p.ranked, tid);
         if (tid == 0) *p.counter = 0u;
       }
     }
@@ -292,18 +274,12 @@ inline bool temperature_ok(float temperature) {
 
 inline int waves_for(int max_len) { return g_waves != 0 ? g_waves : (max_len <= RR_WAVE ? 1 : 4); }
 
-template <int MODE, int NW>
-int approx_launch_nw(ApproxArgs a, int Q, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(lds_arrays(MODE)) * a.L * sizeof(float);
-  if (set_lds(approx_ndcg_kernel<MODE, NW>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  approx_ndcg_kernel<MODE, NW><<<Q, NW * RR_WAVE, lds, s>>>(a);
-  return RR_OK;
-}
-
 template <int MODE>
 int approx_launch(ApproxArgs a, int Q, int max_len, hipStream_t s) {
   a.L = max_len > 8 ? (max_len + 3) & ~3 : 8;                      // float4 reads; 4 doubles of reduction scratch
-  return waves_for(max_len) == 1 ? approx_launch_nw<MODE, 1>(a, Q, s) : approx_launch_nw<MODE, 4>(a, Q, s);
+  constexpr size_t bytes = lds_arrays(MODE) * sizeof(float);
+  return waves_for(max_len) == 1 ? launch_per_query(approx_ndcg_kernel<MODE, 1>, Q, a.L, bytes, RR_WAVE, s, a)
+                                 : launch_per_query(approx_ndcg_kernel<MODE, 4>, Q, a.L, bytes, 4 * RR_WAVE, s, a);
 }
 
 inline bool rank_args_ok(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len, float temperature) {
@@ -344,12 +320,10 @@ int rr_soft_rank_fwd_f32(const float* score, int64_t score_stride, const int32_t
                          float* rank, int64_t rank_stride, rr_stream_t stream) {
   RR_CHECK_ARG(rank_args_ok(score, score_stride, seg_off, Q, max_len, temperature) && rank && rank_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
   ApproxArgs a = ndcg_args(score, score_stride, nullptr, seg_off, temperature, 0);
   a.out = rank;
   a.ostride = rank_stride;
-  const int st = approx_launch<RANK_FWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
-  return st != RR_OK ? st : rr_launch_status();
+  return approx_launch<RANK_FWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
 }
 
 int rr_soft_rank_bwd_f32(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len, float temperature,
@@ -357,14 +331,12 @@ int rr_soft_rank_bwd_f32(const float* score, int64_t score_stride, const int32_t
   RR_CHECK_ARG(rank_args_ok(score, score_stride, seg_off, Q, max_len, temperature) && drank && drank_stride >= 1 && dscore &&
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
   ApproxArgs a = ndcg_args(score, score_stride, nullptr, seg_off, temperature, 0);
   a.up = drank;
   a.ustride = drank_stride;
   a.out = dscore;
   a.ostride = dscore_stride;
-  const int st = approx_launch<RANK_BWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
-  return st != RR_OK ? st : rr_launch_status();
+  return approx_launch<RANK_BWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
 }
 
 int rr_approx_ndcg_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -373,13 +345,11 @@ int rr_approx_ndcg_fwd_f32(const float* score, int64_t score_stride, const float
   RR_CHECK_ARG(ndcg_args_ok(score, score_stride, targets, seg_off, Q, max_len, temperature, ndcg_k) && loss_sum && ranked && partial);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q > 0) {
-    ApproxArgs a = ndcg_args(score, score_stride, targets, seg_off, temperature, ndcg_k);
-    a.partial = partial;
-    const int st = approx_launch<NDCG_FWD>(a, Q, max_len, s);
-    if (st != RR_OK) return st;
-  }
-  approx_finish_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, ranked);
+  ApproxArgs a = ndcg_args(score, score_stride, targets, seg_off, temperature, ndcg_k);
+  a.partial = partial;
+  const int st = approx_launch<NDCG_FWD>(a, Q, max_len, s);
+  if (st != RR_OK) return st;
+  finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, ranked);
   return rr_launch_status();
 }
 
@@ -389,13 +359,11 @@ int rr_approx_ndcg_bwd_f32(const float* score, int64_t score_stride, const float
   RR_CHECK_ARG(ndcg_args_ok(score, score_stride, targets, seg_off, Q, max_len, temperature, ndcg_k) && gloss && dscore &&
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
   ApproxArgs a = ndcg_args(score, score_stride, targets, seg_off, temperature, ndcg_k);
   a.up = gloss;
   a.out = dscore;
   a.ostride = dscore_stride;
-  const int st = approx_launch<NDCG_BWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
-  return st != RR_OK ? st : rr_launch_status();
+  return approx_launch<NDCG_BWD>(a, Q, max_len, static_cast<hipStream_t>(stream));
 }
 
 int rr_approx_ndcg_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -406,7 +374,7 @@ int rr_approx_ndcg_step_f32(const float* score, int64_t score_stride, const floa
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (Q == 0) {                                          // nothing to rank: the zero loss and count of the forward entry
-    approx_finish_kernel<<<1, RR_WAVE, 0, s>>>(partial, 0, scale, loss, ranked);
+    finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, 0, scale, loss, ranked);
     return rr_launch_status();
   }
   ApproxArgs a = ndcg_args(score, score_stride, targets, seg_off, temperature, ndcg_k);
@@ -417,20 +385,17 @@ int rr_approx_ndcg_step_f32(const float* score, int64_t score_stride, const floa
   a.counter = counter;
   a.out = dscore;
   a.ostride = dscore_stride;
-  const int st = approx_launch<NDCG_STEP>(a, Q, max_len, s);
-  return st != RR_OK ? st : rr_launch_status();
+  return approx_launch<NDCG_STEP>(a, Q, max_len, s);
 }
 
 int rr_approx_ndcg_ranks_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                              int max_len, float temperature, int ndcg_k, float* a_out, int64_t a_stride, rr_stream_t stream) {
   RR_CHECK_ARG(ndcg_args_ok(score, score_stride, targets, seg_off, Q, max_len, temperature, ndcg_k) && a_out && a_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
   ApproxArgs a = ndcg_args(score, score_stride, targets, seg_off, temperature, ndcg_k);
   a.out = a_out;
   a.ostride = a_stride;
-  const int st = approx_launch<NDCG_A>(a, Q, max_len, static_cast<hipStream_t>(stream));
-  return st != RR_OK ? st : rr_launch_status();
+  return approx_launch<NDCG_A>(a, Q, max_len, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -12,8 +12,9 @@
 // stored as floats; a pair's weight, cost and lambda are float expressions; the sums over a candidate's pairs and over the
 // query are accumulated in double (a lane adds up to 2^20 terms of a list of 8192) and rounded once.  The weights are
 // constants: no gradient flows through them.  Only wave-level synchronisation, no float atomics; per-query partials
-// [2 * Q] (loss as a float, ordered pairs as an int32 - RankNet's layout) are finished in fixed_sum's order, by a second
-// launch (fwd) or by the workgroup that arrives last (step), so the bits are the same on every run and in both forms.
+// [2 * Q] (loss as a float, ordered pairs as an int32 - RankNet's layout) are finished by finish_counted (loss_list.h, the
+// finish RankNet and ApproxNDCG share), in a second launch (fwd) or by the workgroup that arrives last (step), so the bits
+// are the same on every run and in both forms.
 #include "loss_list.h"
 
 namespace {
@@ -78,24 +79,6 @@ __device__ inline double lambdarank_pairs(const float* s, const float* t, const 
   return LOSS ? wave_sum_f64(acc) : 0.0;
 }
 
-// loss = scale * sum of the float halves of partial[2 * n] in reduce_scale_kernel's order, pairs = sum of the int32 halves
-__device__ inline void lambdarank_finish(const float* partial, int n, float scale, float* loss, int64_t* pairs, int lane) {
-  const float sum = fixed_sum(partial, n, lane, 2);
-  long long np = 0;
-  for (int i = lane; i < n; i += RR_WAVE) np += reinterpret_cast<const int32_t*>(partial)[2 * i + 1];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) np += __shfl_xor(np, o, RR_WAVE);
-  if (lane == 0) {
-    loss[0] = n > 0 ? sum * scale : 0.f;
-    pairs[0] = np;
-  }
-}
-
-__global__ void __launch_bounds__(RR_WAVE) lambdarank_finish_kernel(const float* __restrict__ partial, int n, float scale,
-                                                                    float* __restrict__ loss, int64_t* __restrict__ pairs) {
-  lambdarank_finish(partial, n, scale, loss, pairs, threadIdx.x);
-}
-
 // MODE 0: forward (partial).  MODE 1: backward (dscore = gloss[0] * d loss_sum / d score).  MODE 2: step - both, for the
 // upstream gradient `scale`, and the last workgroup to arrive finishes loss = scale * loss_sum and the pair count.
 template <int MODE>
@@ -140,7 +123,7 @@ __global__ void __launch_bounds__(RR_WAVE) lambdarank_kernel(const float* __rest
   if constexpr (MODE == 2) {
     const int n = gridDim.x;
     if (arrive_last(n, counter, lane)) {
-      lambdarank_finish(partial, n, scale, loss, pairs, lane);
+      finish_counted(partial, n, scale, loss, pairs, lane);
       if (lane == 0) *counter = 0u;
     }
   }
@@ -155,12 +138,9 @@ template <int MODE>
 int lambdarank_launch(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
                       float sigma, int ndcg_k, float* partial, const float* gloss, float scale, float* dscore,
                       int64_t dscore_stride, float* loss, int64_t* pairs, unsigned int* counter, hipStream_t s) {
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 5u * L * sizeof(float);
-  if (set_lds(lambdarank_kernel<MODE>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  lambdarank_kernel<MODE><<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, sigma, ndcg_k, partial, gloss, scale,
-                                                  dscore, dscore_stride, loss, pairs, counter);
-  return RR_OK;
+  const int L = list_words(max_len);
+  return launch_per_query(lambdarank_kernel<MODE>, Q, L, 5 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L,
+                          sigma, ndcg_k, partial, gloss, scale, dscore, dscore_stride, loss, pairs, counter);
 }
 
 }  // namespace
@@ -173,12 +153,10 @@ int rr_lambdarank_fwd_f32(const float* score, int64_t score_stride, const float*
   RR_CHECK_ARG(lambdarank_args_ok(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k) && loss_sum && pairs && partial);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q > 0) {
-    const int st = lambdarank_launch<0>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, partial, nullptr, 0.f,
-                                        nullptr, 1, nullptr, nullptr, nullptr, s);
-    if (st != RR_OK) return st;
-  }
-  lambdarank_finish_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, pairs);
+  const int st = lambdarank_launch<0>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, partial, nullptr, 0.f,
+                                      nullptr, 1, nullptr, nullptr, nullptr, s);
+  if (st != RR_OK) return st;
+  finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, pairs);
   return rr_launch_status();
 }
 
@@ -188,10 +166,8 @@ int rr_lambdarank_bwd_f32(const float* score, int64_t score_stride, const float*
   RR_CHECK_ARG(lambdarank_args_ok(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k) && gloss && dscore &&
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  const int st = lambdarank_launch<1>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, nullptr, gloss, 0.f, dscore,
-                                      dscore_stride, nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream));
-  return st != RR_OK ? st : rr_launch_status();
+  return lambdarank_launch<1>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, nullptr, gloss, 0.f, dscore,
+                              dscore_stride, nullptr, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int rr_lambdarank_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -202,12 +178,11 @@ int rr_lambdarank_step_f32(const float* score, int64_t score_stride, const float
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (Q == 0) {                                          // nothing to rank: the zero loss and pair count of the forward entry
-    lambdarank_finish_kernel<<<1, RR_WAVE, 0, s>>>(partial, 0, scale, loss, pairs);
+    finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, 0, scale, loss, pairs);
     return rr_launch_status();
   }
-  const int st = lambdarank_launch<2>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, partial, nullptr, scale,
-                                      dscore, dscore_stride, loss, pairs, counter, s);
-  return st != RR_OK ? st : rr_launch_status();
+  return lambdarank_launch<2>(score, score_stride, targets, seg_off, Q, max_len, sigma, ndcg_k, partial, nullptr, scale, dscore,
+                              dscore_stride, loss, pairs, counter, s);
 }
 
 }  // extern "C"

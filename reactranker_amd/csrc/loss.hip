@@ -34,9 +34,9 @@ __global__ void __launch_bounds__(RR_WAVE) listmle_kernel(const float* __restric
                                                           const float* __restrict__ targets,
                                                           const int32_t* __restrict__ seg_off, int L, int Q, int bwd,
                                                           float* __restrict__ partial, const float* __restrict__ gloss,
-                                                          float* __restrict__ dscore, int64_t dstride, float scale = 0.f,
-                                                          float* __restrict__ loss = nullptr,
-                                                          unsigned int* __restrict__ counter = nullptr) {
+                                                          float* __restrict__ dscore, int64_t dstride, float scale,
+                                                          float* __restrict__ loss,
+                                                          unsigned int* __restrict__ counter) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
@@ -68,8 +68,8 @@ __global__ void __launch_bounds__(RR_WAVE) listnet_kernel(const float* __restric
                                                           const int32_t* __restrict__ seg_off, int L, int bwd,
                                                           float* __restrict__ partial, const float* __restrict__ gloss,
                                                           float inv_total, float* __restrict__ dscore,
-                                                          int64_t dstride, float* __restrict__ loss = nullptr,
-                                                          unsigned int* __restrict__ counter = nullptr) {
+                                                          int64_t dstride, float* __restrict__ loss,
+                                                          unsigned int* __restrict__ counter) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
@@ -103,8 +103,8 @@ __global__ void __launch_bounds__(RR_WAVE) evidential_kernel(const float* __rest
                                                              float* __restrict__ partial,
                                                              const float* __restrict__ gloss, float* __restrict__ dmu,
                                                              float* __restrict__ dvar, int64_t dstride,
-                                                             float* __restrict__ loss = nullptr,
-                                                             unsigned int* __restrict__ counter = nullptr) {
+                                                             float* __restrict__ loss,
+                                                             unsigned int* __restrict__ counter) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int q = blockIdx.x, lane = threadIdx.x;
   const int off = seg_off[q], C = seg_off[q + 1] - off;
@@ -238,20 +238,6 @@ __global__ void __launch_bounds__(256) reduce_scale_kernel(const float* __restri
     __syncthreads();
   }
   if (threadIdx.x == 0) out[0] = red[0] * scale;
-}
-
-__global__ void __launch_bounds__(256) reduce_pairs_kernel(const float* __restrict__ partial, int64_t n,
-                                                           int64_t* __restrict__ out) {
-  __shared__ long long red[256];
-  long long acc = 0;
-  for (int64_t i = threadIdx.x; i < n; i += 256) acc += reinterpret_cast<const int32_t*>(partial)[2 * i + 1];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0];
 }
 
 // ---------------------------------------------------------------- pointwise losses (rows: point_row, loss_list.h)
@@ -736,22 +722,27 @@ int pointwise_blocks(int64_t n) {
   return static_cast<int>(b);
 }
 
+// the second launch of a forward entry point, and all of a step entry point that has no query: loss = scale * the sum of
+// partial[n] in reduce_scale_kernel's fixed order.  st: the status of the launch before it, which a failure passes through
+int finish_mean(int st, const float* partial, int n, float scale, float* loss, hipStream_t s) {
+  if (st != RR_OK) return st;
+  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, n, 1, scale, loss);
+  return rr_launch_status();
+}
+
+inline float inv_count(int64_t n) { return n > 0 ? 1.0f / static_cast<float>(n) : 0.f; }
+
 // forward (gloss == nullptr: partials + the mean over queries into `loss`) or backward of one listwise variant
 template <int V>
 int variant_launch(const VarIn& in, const float* targets, const int32_t* seg_off, int Q, int max_len, float coef, float* loss,
                    float* partial, const float* gloss, const VarOut& out, rr_stream_t stream) {
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   const int bwd = gloss != nullptr;
-  if (bwd && Q == 0) return RR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(variant_lds(V)) * L * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(listwise_variant_kernel<V>, lds) != RR_OK) return RR_ERR_LAUNCH;
-    listwise_variant_kernel<V><<<Q, RR_WAVE, lds, s>>>(in, targets, seg_off, L, Q, coef, bwd, partial, gloss, out);
-  }
-  if (!bwd) reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, Q > 0 ? 1.0f / static_cast<float>(Q) : 0.f, loss);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(listwise_variant_kernel<V>, Q, L, variant_lds(V) * sizeof(float), RR_WAVE, s, in, targets,
+                                  seg_off, L, Q, coef, bwd, partial, gloss, out);
+  return bwd ? st : finish_mean(st, partial, Q, inv_count(Q), loss, s);
 }
 
 inline bool strides_ok(const VarIn& in, int nin) {
@@ -806,14 +797,10 @@ int rr_listmle_fwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && score_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 5u * L * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 0, partial, nullptr, nullptr, 1);
-  }
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, Q > 0 ? 1.0f / static_cast<float>(Q) : 0.f, loss);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, Q,
+                                  0, partial, nullptr, nullptr, 1, 0.f, nullptr, nullptr);
+  return finish_mean(st, partial, Q, inv_count(Q), loss, s);
 }
 
 int rr_listmle_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -821,13 +808,9 @@ int rr_listmle_bwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 5u * L * sizeof(float);
-  if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 1, nullptr, gloss, dscore, dscore_stride);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
+                          targets, seg_off, L, Q, 1, nullptr, gloss, dscore, dscore_stride, 0.f, nullptr, nullptr);
 }
 
 int rr_listmle_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
@@ -837,16 +820,10 @@ int rr_listmle_step_f32(const float* score, int64_t score_stride, const float* t
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0) {                                          // nothing to rank: the loss is the empty mean the forward entry point writes
-    reduce_scale_kernel<<<1, 256, 0, s>>>(partial, 0, 1, 0.f, loss);
-    return rr_launch_status();
-  }
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 5u * L * sizeof(float);
-  if (set_lds(listmle_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listmle_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, Q, 2, partial, nullptr, dscore, dscore_stride,
-                                         1.0f / static_cast<float>(Q), loss, counter);
-  return rr_launch_status();
+  if (Q == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);   // nothing to rank: the empty mean of the forward entry point
+  const int L = list_words(max_len);
+  return launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, Q, 2,
+                          partial, nullptr, dscore, dscore_stride, 1.0f / static_cast<float>(Q), loss, counter);
 }
 
 int rr_listnet_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -854,16 +831,10 @@ int rr_listnet_fwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && score_stride >= 1 && total >= 0);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * L * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(listnet_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    listnet_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, 0, partial, nullptr, 0.f, nullptr,
-                                           1);
-  }
-  // ONE global mean over all candidates (loss.py:347)
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, total > 0 ? 1.0f / static_cast<float>(total) : 0.f, loss);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, 0,
+                                  partial, nullptr, 0.f, nullptr, 1, nullptr, nullptr);
+  return finish_mean(st, partial, Q, inv_count(total), loss, s);    // ONE global mean over all candidates (loss.py:347)
 }
 
 int rr_listnet_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -872,14 +843,11 @@ int rr_listnet_bwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1 && total >= 0);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0 || total == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * L * sizeof(float);
-  if (set_lds(listnet_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listnet_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, 1, nullptr, gloss,
-                                         1.0f / static_cast<float>(total), dscore, dscore_stride);
-  return rr_launch_status();
+  if (total == 0) return RR_OK;
+  const int L = list_words(max_len);
+  return launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
+                          targets, seg_off, L, 1, nullptr, gloss, 1.0f / static_cast<float>(total), dscore, dscore_stride, nullptr,
+                          nullptr);
 }
 
 int rr_listnet_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
@@ -889,16 +857,10 @@ int rr_listnet_step_f32(const float* score, int64_t score_stride, const float* t
                dscore_stride >= 1 && total >= 0);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0 || total == 0) {
-    reduce_scale_kernel<<<1, 256, 0, s>>>(partial, 0, 1, 0.f, loss);
-    return rr_launch_status();
-  }
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * L * sizeof(float);
-  if (set_lds(listnet_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  listnet_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, 2, partial, nullptr,
-                                         1.0f / static_cast<float>(total), dscore, dscore_stride, loss, counter);
-  return rr_launch_status();
+  if (Q == 0 || total == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);
+  const int L = list_words(max_len);
+  return launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, 2, partial,
+                          nullptr, 1.0f / static_cast<float>(total), dscore, dscore_stride, loss, counter);
 }
 
 int rr_evidential_ranking_fwd_f32(const float* mu, const float* var, int64_t stride, const float* targets,
@@ -907,15 +869,10 @@ int rr_evidential_ranking_fwd_f32(const float* mu, const float* var, int64_t str
   RR_CHECK_ARG(list_args_ok(mu, targets, seg_off, Q, max_len) && var && loss && partial && stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 3u * L * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(evidential_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    evidential_kernel<<<Q, RR_WAVE, lds, s>>>(mu, var, stride, targets, seg_off, L, Q, 0, partial, nullptr, nullptr,
-                                              nullptr, 1);
-  }
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 1, Q > 0 ? 1.0f / static_cast<float>(Q) : 0.f, loss);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, s, mu, var, stride, targets, seg_off, L, Q, 0,
+                                  partial, nullptr, nullptr, nullptr, 1, nullptr, nullptr);
+  return finish_mean(st, partial, Q, inv_count(Q), loss, s);
 }
 
 int rr_evidential_ranking_bwd_f32(const float* mu, const float* var, int64_t stride, const float* targets,
@@ -924,14 +881,9 @@ int rr_evidential_ranking_bwd_f32(const float* mu, const float* var, int64_t str
   RR_CHECK_ARG(list_args_ok(mu, targets, seg_off, Q, max_len) && var && gloss && dmu && dvar && stride >= 1 &&
                dstride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 3u * L * sizeof(float);
-  if (set_lds(evidential_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  evidential_kernel<<<Q, RR_WAVE, lds, s>>>(mu, var, stride, targets, seg_off, L, Q, 1, nullptr, gloss, dmu, dvar,
-                                            dstride);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), mu, var, stride,
+                          targets, seg_off, L, Q, 1, nullptr, gloss, dmu, dvar, dstride, nullptr, nullptr);
 }
 
 int rr_evidential_ranking_step_f32(const float* mu, const float* var, int64_t stride, const float* targets, const int32_t* seg_off,
@@ -941,16 +893,10 @@ int rr_evidential_ranking_step_f32(const float* mu, const float* var, int64_t st
                dstride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0) {
-    reduce_scale_kernel<<<1, 256, 0, s>>>(partial, 0, 1, 0.f, loss);
-    return rr_launch_status();
-  }
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 3u * L * sizeof(float);
-  if (set_lds(evidential_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  evidential_kernel<<<Q, RR_WAVE, lds, s>>>(mu, var, stride, targets, seg_off, L, Q, 2, partial, nullptr, dmu, dvar, dstride, loss,
-                                            counter);
-  return rr_launch_status();
+  if (Q == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);
+  const int L = list_words(max_len);
+  return launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, s, mu, var, stride, targets, seg_off, L, Q, 2, partial,
+                          nullptr, dmu, dvar, dstride, loss, counter);
 }
 
 int rr_ranknet_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -959,14 +905,11 @@ int rr_ranknet_fwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss_sum && pairs && partial && score_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * L * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(ranknet_fwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    ranknet_fwd_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, sigma, partial);
-  }
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, Q, 2, 1.0f, loss_sum);
-  reduce_pairs_kernel<<<1, 256, 0, s>>>(partial, Q, pairs);
+  const int L = list_words(max_len);
+  const int st = launch_per_query(ranknet_fwd_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L,
+                                  sigma, partial);
+  if (st != RR_OK) return st;
+  finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, pairs);
   return rr_launch_status();
 }
 
@@ -976,14 +919,9 @@ int rr_ranknet_bwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1 && (mode == 0 || mode == 1));
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 3u * L * sizeof(float);
-  if (set_lds(ranknet_bwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  ranknet_bwd_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, sigma, mode, gloss, dscore,
-                                             dscore_stride);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(ranknet_bwd_kernel, Q, L, 3 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score,
+                          score_stride, targets, seg_off, L, sigma, mode, gloss, dscore, dscore_stride);
 }
 
 int64_t rr_pointwise_partial_count(int64_t n) { return pointwise_blocks(n); }
@@ -1032,13 +970,9 @@ int rr_ranking_metrics_f32(const float* score, int64_t score_stride, const float
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && order && stats && score_stride >= 1);
   RR_CHECK_ARG(ratio >= 0.0 && ratio <= 1.0 && ndcg_cut >= 0.0 && ndcg_cut <= 1.0);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * L * sizeof(float) + 4u * L * sizeof(uint16_t);
-  if (set_lds(ranking_metrics_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  ranking_metrics_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, ratio, ndcg_cut, order, stats);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(ranking_metrics_kernel, Q, L, 2 * sizeof(float) + 4 * sizeof(uint16_t), RR_WAVE,
+                          static_cast<hipStream_t>(stream), score, score_stride, targets, seg_off, L, ratio, ndcg_cut, order, stats);
 }
 
 int rr_logcumsumexp_fwd_f32(const float* x, int n, float* y, rr_stream_t stream) {

@@ -471,4 +471,25 @@ __device__ inline bool finish_last(const float* partial, int n, unsigned int* co
   return lane == 0;
 }
 
+// The finish of the losses that carry a count (RankNet, LambdaRank: ordered pairs; ApproxNDCG: ranked queries).  Their
+// per-query partials are [2 * n]: the query's loss as a float, its count as an int32.  loss = scale * the sum of the float
+// halves in fixed_sum's order, count = the exact sum of the int32 halves; n == 0 gives +0.0f and 0.  One wave: the second
+// launch of a forward entry point (finish_counted_kernel), or the wave that arrive_last picks in a step kernel.
+__device__ inline void finish_counted(const float* partial, int n, float scale, float* loss, int64_t* count, int lane) {
+  const float sum = fixed_sum(partial, n, lane, 2);
+  long long np = 0;
+  for (int i = lane; i < n; i += RR_WAVE) np += reinterpret_cast<const int32_t*>(partial)[2 * i + 1];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) np += __shfl_xor(np, o, RR_WAVE);
+  if (lane == 0) {
+    loss[0] = n > 0 ? sum * scale : 0.f;
+    count[0] = np;
+  }
+}
+
+__global__ void __launch_bounds__(RR_WAVE) finish_counted_kernel(const float* __restrict__ partial, int n, float scale,
+                                                                 float* __restrict__ loss, int64_t* __restrict__ count) {
+  finish_counted(partial, n, scale, loss, count, threadIdx.x);
+}
+
 }  // namespace

@@ -400,6 +400,16 @@ __global__ void __launch_bounds__(256) pair_combine_kernel(const float* __restri
   }
 }
 
+// the C x C kernels stage one double and one float per candidate (12 bytes)
+constexpr size_t kSqBytes = sizeof(double) + sizeof(float);
+
+// the second launch of their forward entry points; st: the status of the first, which a failure passes through
+int finish_sq(int st, const double* partial, const int32_t* seg_off, int Q, float* loss_sum, int64_t* pairs, hipStream_t s) {
+  if (st != RR_OK) return st;
+  finish_sq_kernel<<<1, 256, 0, s>>>(partial, seg_off, Q, loss_sum, pairs);
+  return rr_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -410,14 +420,10 @@ int rr_betanet_fwd_f32(const float* score, int64_t score_stride, const float* ta
                alpha0 > 0.f);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(L) * (sizeof(double) + sizeof(float));
-  if (Q > 0) {
-    if (set_lds(betanet_fwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    betanet_fwd_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, alpha0, partial);
-  }
-  finish_sq_kernel<<<1, 256, 0, s>>>(partial, seg_off, Q, loss_sum, pairs);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(betanet_fwd_kernel, Q, L, kSqBytes, RR_WAVE, s, score, score_stride, targets, seg_off, L, alpha0,
+                                  partial);
+  return finish_sq(st, partial, seg_off, Q, loss_sum, pairs, s);
 }
 
 int rr_betanet_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -426,13 +432,9 @@ int rr_betanet_bwd_f32(const float* score, int64_t score_stride, const float* ta
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1 && alpha0 > 0.f);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(L) * (sizeof(double) + sizeof(float));
-  if (set_lds(betanet_bwd_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  betanet_bwd_kernel<<<Q, RR_WAVE, lds, static_cast<hipStream_t>(stream)>>>(score, score_stride, targets, seg_off, L, alpha0,
-                                                                            gloss, dscore, dscore_stride);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(betanet_bwd_kernel, Q, L, kSqBytes, RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
+                          targets, seg_off, L, alpha0, gloss, dscore, dscore_stride);
 }
 
 int rr_beta_evidential_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
@@ -441,14 +443,10 @@ int rr_beta_evidential_fwd_f32(const float* score, int64_t score_stride, const f
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss_sum && pairs && partial && score_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(L) * (sizeof(double) + sizeof(float));
-  if (Q > 0) {
-    if (set_lds(beta_evi_kernel<false>, lds) != RR_OK) return RR_ERR_LAUNCH;
-    beta_evi_kernel<false><<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, coef, partial, nullptr, nullptr, 0);
-  }
-  finish_sq_kernel<<<1, 256, 0, s>>>(partial, seg_off, Q, loss_sum, pairs);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  const int st = launch_per_query(beta_evi_kernel<false>, Q, L, kSqBytes, RR_WAVE, s, score, score_stride, targets, seg_off, L, coef,
+                                  partial, nullptr, nullptr, 0);
+  return finish_sq(st, partial, seg_off, Q, loss_sum, pairs, s);
 }
 
 int rr_beta_evidential_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
@@ -457,13 +455,9 @@ int rr_beta_evidential_bwd_f32(const float* score, int64_t score_stride, const f
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(L) * (sizeof(double) + sizeof(float));
-  if (set_lds(beta_evi_kernel<true>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  beta_evi_kernel<true><<<Q, RR_WAVE, lds, static_cast<hipStream_t>(stream)>>>(score, score_stride, targets, seg_off, L, coef,
-                                                                               nullptr, gloss, dscore, dscore_stride);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(beta_evi_kernel<true>, Q, L, kSqBytes, RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
+                          targets, seg_off, L, coef, nullptr, gloss, dscore, dscore_stride);
 }
 
 int rr_pairwise_eval_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
@@ -471,12 +465,10 @@ int rr_pairwise_eval_f32(const float* score, int64_t score_stride, const float* 
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && qstats && out && score_stride >= 1);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = 2u * static_cast<size_t>(L) * sizeof(float);
-  if (Q > 0) {
-    if (set_lds(pairwise_eval_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-    pairwise_eval_kernel<<<Q, RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, sigma, qstats);
-  }
+  const int L = list_words(max_len);
+  const int st = launch_per_query(pairwise_eval_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L,
+                                  sigma, qstats);
+  if (st != RR_OK) return st;
   finish_eval_kernel<<<1, 256, 0, s>>>(qstats, Q, out);
   return rr_launch_status();
 }

@@ -138,10 +138,8 @@ __global__ void task_empty_kernel(float* loss, float* terms) {
 
 template <int LT, int PT>
 int task_launch(const TaskArgs& a, hipStream_t s) {
-  const size_t lds = static_cast<size_t>(task_lds(LT) > 0 ? task_lds(LT) : 1) * a.L * sizeof(float);
-  if (set_lds(task_step_kernel<LT, PT>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  task_step_kernel<LT, PT><<<a.Q, RR_WAVE, lds, s>>>(a);
-  return rr_launch_status();
+  constexpr size_t bytes = (task_lds(LT) > 0 ? task_lds(LT) : 1) * sizeof(float);
+  return launch_per_query(task_step_kernel<LT, PT>, a.Q, a.L, bytes, RR_WAVE, s, a);
 }
 
 template <int LT>
@@ -182,7 +180,7 @@ int rr_task_loss_step_f32(const rr_task_loss_args* p, rr_stream_t stream) {
   a.n_cols = p->n_cols;
   a.targets = p->targets;
   a.seg_off = p->seg_off;
-  a.L = p->max_len > 0 ? p->max_len : 1;
+  a.L = list_words(p->max_len);
   a.Q = p->Q;
   a.coef = p->coef;
   a.inv_queries = p->n_queries > 0 ? 1.0f / static_cast<float>(p->n_queries) : 0.f;

@@ -404,13 +404,9 @@ int rr_mc_sample_stats_f32(const float* samples, int64_t sample_stride, int T, c
   RR_CHECK_ARG(T >= 2 && Q >= 0 && max_len >= 0 && sample_stride >= 1 && sample_stride >= max_len);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   if (static_cast<int64_t>(T) * max_len > static_cast<int64_t>(UINT32_MAX)) return RR_ERR_UNSUPPORTED;   // u32 rank sums
-  if (Q == 0) return RR_OK;
-  const int L = max_len > 0 ? max_len : 1;
-  const size_t lds = static_cast<size_t>(L) * (sizeof(float) + 2 * sizeof(uint32_t));
-  if (set_lds(mc_stats_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
-  mc_stats_kernel<<<Q, RR_WAVE, lds, static_cast<hipStream_t>(stream)>>>(samples, sample_stride, T, targets, seg_off, L, mean,
-                                                                        std_dev, p_top1, mean_rank, qstats);
-  return rr_launch_status();
+  const int L = list_words(max_len);
+  return launch_per_query(mc_stats_kernel, Q, L, sizeof(float) + 2 * sizeof(uint32_t), RR_WAVE, static_cast<hipStream_t>(stream),
+                          samples, sample_stride, T, targets, seg_off, L, mean, std_dev, p_top1, mean_rank, qstats);
 }
 
 int rr_analytic_rank_stats_f32(const float* out, int64_t ld, int kind, const float* targets, const int32_t* seg_off, int Q,

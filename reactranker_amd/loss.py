@@ -44,16 +44,17 @@ def _call(name, *args):
     check(getattr(lib(), name)(*args, stream()), name)
 
 
-def _prep(score: torch.Tensor, scope, targets, gpu):
+def _prep(score: torch.Tensor, scope, targets, gpu, what: str = "score"):
+    """scope as a tuple, its device offsets, the candidate and longest-list counts, the targets (None stays None)"""
     if gpu is not None:
         torch.cuda.set_device(gpu)                      # reference loss.py:83
-    _lib.require_cuda(score, "score")
+    _lib.require_cuda(score, what)
     scope = tuple(int(c) for c in (scope.tolist() if hasattr(scope, "tolist") else scope))
     seg, total, max_len = _segments(scope, str(score.device))
     if total != score.shape[0]:
-        raise RuntimeError(f"sum(scope) = {total} but score has {score.shape[0]} rows")
-    t = _targets(targets, score.device)
-    if t.numel() != total:
+        raise RuntimeError(f"sum(scope) = {total} but {what} has {score.shape[0]} rows")
+    t = None if targets is None else _targets(targets, score.device)
+    if t is not None and t.numel() != total:
         raise RuntimeError("targets and score lengths differ")
     return scope, seg, total, max_len, t
 
@@ -69,6 +70,22 @@ def _vec(x: torch.Tensor) -> torch.Tensor:
 
 def _f1(dev):
     return torch.empty(1, dtype=torch.float32, device=dev)
+
+
+def _first_column(y: torch.Tensor) -> torch.Tensor:
+    """[M] as it is, the first column of [M, k] (read in place; reference train_pairwise.py:115-116)"""
+    return y[:, 0] if y.dim() > 1 else y
+
+
+def _ndcg_k(ndcg_k, what) -> int:
+    if int(ndcg_k) != ndcg_k or ndcg_k < 0:
+        raise ValueError(f"{what}: ndcg_k must be a non-negative integer (0: the whole list)")
+    return int(ndcg_k)
+
+
+def _inv_count(n) -> float:
+    """1 / n of a positive host count as the float32 the step kernels multiply by"""
+    return float(np.float32(1.0 / int(n)))
 
 
 class FusedStep:
@@ -173,31 +190,62 @@ class _FusedListFn(torch.autograd.Function):
         return (None, d) + (None,) * 5
 
 
-class _RankNetFn(torch.autograd.Function):
-    """loss_sum of 'sum_session' (train_pairwise.py:118-122); backward = its true gradient."""
+# The window losses: a sum over the queries of a window plus a count (ordered pairs, ranked queries), normalised by a HOST count.
+# kind (the entry points' stem: rr_{kind}_{fwd,bwd,step}_f32) -> (partial dtype, partial words per query, has a step entry,
+# what bwd passes after the hyper-parameters).  The hyper-parameters themselves come with the call, as the entry points
+# take them after max_len.
+_WINDOW = {
+    "ranknet": (torch.float32, 2, False, (0,)),           # (sigma); bwd mode 0: the true gradient of loss_sum
+    "lambdarank": (torch.float32, 2, True, ()),           # (sigma, ndcg_k)
+    "approx_ndcg": (torch.float32, 2, True, ()),          # (temperature, ndcg_k)
+    "betanet": (torch.float64, 1, False, ()),             # (alpha0)
+    "beta_evidential": (torch.float64, 1, False, ()),     # (the annealing coefficient)
+}
+
+
+class _WindowFn(torch.autograd.Function):
+    """scale * loss_sum of one of _WINDOW and the window's count (int64 device scalar, not differentiable).  A kind with a step
+    entry, when the score wants a gradient and FusedStep is on: rr_{kind}_step_f32 writes the loss and scale * d loss_sum /
+    d score in one launch and `backward(loss)` hands that gradient out.  Otherwise rr_{kind}_fwd_f32, and rr_{kind}_bwd_f32
+    with the upstream gradient times `scale` - the same bits for an upstream gradient of one."""
 
     @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len, sigma):
+    def forward(ctx, kind, score, targets, seg, Q, max_len, hyper, scale):
+        part_dtype, part_words, has_step, bwd_extra = _WINDOW[kind]
         s = _vec(score.detach())
         loss = _f1(s.device)
-        pairs = torch.empty(1, dtype=torch.int64, device=s.device)
-        part = torch.empty(max(2 * Q, 2), dtype=torch.float32, device=s.device)
-        check(lib().rr_ranknet_fwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, float(sigma), ptr(loss),
-                                       ptr(pairs), ptr(part), stream()), "rr_ranknet_fwd_f32")
+        count = torch.empty(1, dtype=torch.int64, device=s.device)
+        part = torch.empty(part_words * max(Q, 1), dtype=part_dtype, device=s.device)
+        args = [ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, *hyper]
+        ctx.ds_unit = None
+        if has_step and FusedStep.enabled and ctx.needs_input_grad[1]:
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call(f"rr_{kind}_step_f32", *args, scale, ptr(loss), ptr(count), ptr(part), ptr(_counter(s.device)), ptr(d), 1)
+            ctx.ds_unit = d
+        else:
+            _call(f"rr_{kind}_fwd_f32", *args, ptr(loss), ptr(count), ptr(part))
+            if scale != 1.0:
+                loss = loss * scale                      # (a float32 product, as in the step kernel)
         ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (Q, max_len, float(sigma))
-        ctx.mark_non_differentiable(pairs)
-        return loss.reshape(()), pairs
+        ctx.meta = (kind, args + list(bwd_extra), scale)
+        ctx.mark_non_differentiable(count)
+        return loss.reshape(()), count
 
     @staticmethod
-    def backward(ctx, g, _gp):
-        s, targets, seg = ctx.saved_tensors
-        Q, max_len, sigma = ctx.meta
-        g = g.reshape(-1).contiguous().float()
-        ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-        check(lib().rr_ranknet_bwd_f32(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, sigma, 0, ptr(g),
-                                       ptr(ds), 1, stream()), "rr_ranknet_bwd_f32")
-        return ds, None, None, None, None, None
+    def backward(ctx, g, _gc):
+        if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
+            d, ctx.ds_unit = ctx.ds_unit, None
+            FusedStep.hits += 1
+        else:
+            s = ctx.saved_tensors[0]                     # (the saved tensors keep the pointers in `args` alive)
+            kind, args, scale = ctx.meta
+            g = g.reshape(-1).float()
+            if scale != 1.0:
+                g = g * scale
+            g = g.contiguous()
+            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
+            _call(f"rr_{kind}_bwd_f32", *args, ptr(g), ptr(d), 1)
+        return (None, d) + (None,) * 6
 
 
 class _PointwiseFn(torch.autograd.Function):
@@ -305,65 +353,20 @@ def ranknet_loss(y_pred, scope, targets, sigma: float = 1.0, gpu: int = None):
     as the trainer does at :147-150); pairs is an int64 device scalar.  `y_pred` may be [M] or
     [M, k] (first column used, :115-116).
     """
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
-    loss, pairs = _RankNetFn.apply(y_pred, t, seg, len(scope), max_len, sigma)
-    return loss, pairs
+    return _WindowFn.apply("ranknet", y_pred, t, seg, len(scope), max_len, (float(sigma),), 1.0)
 
 
 def ranknet_lambda(y_pred, scope, targets, sigma: float = 1.0, gpu: int = None):
     """'accelerate_grad' closed-form lambdas `back` (reference train/train_pairwise.py:125-133)."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
     s = _vec(y_pred.detach())
     one = torch.ones(1, dtype=torch.float32, device=s.device)
     out = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-    check(lib().rr_ranknet_bwd_f32(ptr(s), s.stride(0), ptr(t), ptr(seg), len(scope), max_len, float(sigma), 1,
-                                   ptr(one), ptr(out), 1, stream()), "rr_ranknet_bwd_f32")
+    _call("rr_ranknet_bwd_f32", ptr(s), s.stride(0), ptr(t), ptr(seg), len(scope), max_len, float(sigma), 1, ptr(one), ptr(out), 1)
     return out
-
-
-class _LambdaRankFn(torch.autograd.Function):
-    """scale * loss_sum of LambdaRank (csrc/lambdarank.hip) and the window's ordered pairs.  When the score wants a gradient
-    and FusedStep is on, rr_lambdarank_step_f32 writes the loss and scale * d loss_sum / d score in one launch and
-    `backward(loss)` hands that gradient out; otherwise rr_lambdarank_fwd_f32, and rr_lambdarank_bwd_f32 with the upstream
-    gradient times `scale` - the same bits for an upstream gradient of one."""
-
-    @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len, sigma, ndcg_k, scale):
-        s = _vec(score.detach())
-        loss = _f1(s.device)
-        pairs = torch.empty(1, dtype=torch.int64, device=s.device)
-        part = torch.empty(max(2 * Q, 2), dtype=torch.float32, device=s.device)
-        args = [ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, float(sigma), int(ndcg_k)]
-        ctx.ds_unit = None
-        if FusedStep.enabled and ctx.needs_input_grad[0]:
-            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            _call("rr_lambdarank_step_f32", *args, scale, ptr(loss), ptr(pairs), ptr(part), ptr(_counter(s.device)), ptr(d), 1)
-            ctx.ds_unit = d
-        else:
-            _call("rr_lambdarank_fwd_f32", *args, ptr(loss), ptr(pairs), ptr(part))
-            if scale != 1.0:
-                loss = loss * scale                      # (a float32 product, as in the step kernel)
-        ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (args, scale)
-        ctx.mark_non_differentiable(pairs)
-        return loss.reshape(()), pairs
-
-    @staticmethod
-    def backward(ctx, g, _gp):
-        if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
-            d, ctx.ds_unit = ctx.ds_unit, None
-            FusedStep.hits += 1
-        else:
-            s = ctx.saved_tensors[0]                     # (the saved tensors keep the pointers in `args` alive)
-            args, scale = ctx.meta
-            g = (g.reshape(-1).float() * scale).contiguous()
-            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            _call("rr_lambdarank_bwd_f32", *args, ptr(g), ptr(d), 1)
-        return (d,) + (None,) * 7
 
 
 def lambdarank_loss(y_pred, scope, targets, sigma: float = 1.0, ndcg_k: int = 0, gpu: int = None, pairs: int = None):
@@ -376,19 +379,17 @@ def lambdarank_loss(y_pred, scope, targets, sigma: float = 1.0, ndcg_k: int = 0,
     count to normalise by (the WINDOW's count for a shard of a data-parallel step) - loss is loss_sum * float32(1 / pairs) and
     `backward(loss)` then takes the gradient the same launch wrote (FusedStep).  pairs_tensor is this call's own count, an
     int64 device scalar.  `y_pred` may be [M] or [M, k] (first column, read in place)."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     if not sigma > 0:
         raise ValueError("lambdarank_loss: sigma must be positive")
-    if int(ndcg_k) != ndcg_k or ndcg_k < 0:
-        raise ValueError("lambdarank_loss: ndcg_k must be a non-negative integer (0: the whole list)")
+    ndcg_k = _ndcg_k(ndcg_k, "lambdarank_loss")
     scale = 1.0
     if pairs is not None:
         if int(pairs) <= 0:
             raise ValueError("lambdarank_loss: pairs must be a positive count (a window without pairs is skipped by the trainer)")
-        scale = float(np.float32(1.0 / int(pairs)))
+        scale = _inv_count(pairs)
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
-    return _LambdaRankFn.apply(y_pred, t, seg, len(scope), max_len, sigma, int(ndcg_k), scale)
+    return _WindowFn.apply("lambdarank", y_pred, t, seg, len(scope), max_len, (float(sigma), ndcg_k), scale)
 
 
 def _temperature(temperature, what) -> float:
@@ -430,57 +431,10 @@ def soft_rank(y_pred, scope, temperature: float = 1.0, gpu: int = None):
     blurs towards (C + 1) / 2, and as T -> 0 the ranks become the hard ones (and the gradient vanishes).  Soft Spearman, soft
     top-k recall and the like are a few lines of torch on top.  `y_pred` may be [M] or [M, k] (first column, read in place).
     DESIGN section 4b."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     temperature = _temperature(temperature, "soft_rank")
-    if gpu is not None:
-        torch.cuda.set_device(gpu)
-    _lib.require_cuda(y_pred, "y_pred")
-    scope = tuple(int(c) for c in (scope.tolist() if hasattr(scope, "tolist") else scope))
-    seg, total, max_len = _segments(scope, str(y_pred.device))
-    if total != y_pred.shape[0]:
-        raise RuntimeError(f"sum(scope) = {total} but y_pred has {y_pred.shape[0]} rows")
+    scope, seg, total, max_len, _ = _prep(y_pred, scope, None, gpu, "y_pred")
     return _SoftRankFn.apply(y_pred, seg, len(scope), max_len, temperature)
-
-
-class _ApproxNdcgFn(torch.autograd.Function):
-    """scale * loss_sum of ApproxNDCG (csrc/approx_ndcg.hip) and the window's ranked queries; the launches of _LambdaRankFn:
-    rr_approx_ndcg_step_f32 when the score wants a gradient and FusedStep is on, else rr_approx_ndcg_fwd_f32, and
-    rr_approx_ndcg_bwd_f32 with the upstream gradient times `scale` - the same bits for an upstream gradient of one."""
-
-    @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len, temperature, ndcg_k, scale):
-        s = _vec(score.detach())
-        loss = _f1(s.device)
-        ranked = torch.empty(1, dtype=torch.int64, device=s.device)
-        part = torch.empty(max(2 * Q, 2), dtype=torch.float32, device=s.device)
-        args = [ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, temperature, int(ndcg_k)]
-        ctx.ds_unit = None
-        if FusedStep.enabled and ctx.needs_input_grad[0]:
-            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            _call("rr_approx_ndcg_step_f32", *args, scale, ptr(loss), ptr(ranked), ptr(part), ptr(_counter(s.device)), ptr(d), 1)
-            ctx.ds_unit = d
-        else:
-            _call("rr_approx_ndcg_fwd_f32", *args, ptr(loss), ptr(ranked), ptr(part))
-            if scale != 1.0:
-                loss = loss * scale                      # (a float32 product, as in the step kernel)
-        ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (args, scale)
-        ctx.mark_non_differentiable(ranked)
-        return loss.reshape(()), ranked
-
-    @staticmethod
-    def backward(ctx, g, _gr):
-        if ctx.ds_unit is not None and _is_unit(g):      # the gradient the forward launch already wrote (handed out once)
-            d, ctx.ds_unit = ctx.ds_unit, None
-            FusedStep.hits += 1
-        else:
-            s = ctx.saved_tensors[0]
-            args, scale = ctx.meta
-            g = (g.reshape(-1).float() * scale).contiguous()
-            d = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-            _call("rr_approx_ndcg_bwd_f32", *args, ptr(g), ptr(d), 1)
-        return (d,) + (None,) * 7
 
 
 def approx_ndcg_loss(y_pred, scope, targets, temperature: float = 1.0, ndcg_k: int = 0, gpu: int = None, queries: int = None):
@@ -495,18 +449,16 @@ def approx_ndcg_loss(y_pred, scope, targets, temperature: float = 1.0, ndcg_k: i
     `backward(loss)` then takes the gradient the same launch wrote (FusedStep).  ranked_tensor is this call's number of ranked
     queries (those with two different targets; the others add nothing and get a zero gradient), an int64 device scalar.
     `y_pred` may be [M] or [M, k] (first column, read in place)."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     temperature = _temperature(temperature, "approx_ndcg_loss")
-    if int(ndcg_k) != ndcg_k or ndcg_k < 0:
-        raise ValueError("approx_ndcg_loss: ndcg_k must be a non-negative integer (0: the whole list)")
+    ndcg_k = _ndcg_k(ndcg_k, "approx_ndcg_loss")
     scale = 1.0
     if queries is not None:
         if int(queries) != queries or int(queries) <= 0:
             raise ValueError("approx_ndcg_loss: queries must be a positive count")
-        scale = float(np.float32(1.0 / int(queries)))
+        scale = _inv_count(queries)
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
-    return _ApproxNdcgFn.apply(y_pred, t, seg, len(scope), max_len, temperature, int(ndcg_k), scale)
+    return _WindowFn.apply("approx_ndcg", y_pred, t, seg, len(scope), max_len, (temperature, ndcg_k), scale)
 
 
 # ---------------------------------------------------------------------------------------------- the remaining task types' losses
@@ -799,36 +751,7 @@ def task_step_loss(task_type, output, scope, targets, gpu, coef=0.0, norm=None):
 
 
 # ---------------------------------------------------------------------------------------------- the pairwise trainer's remaining losses
-class _SqPairFn(torch.autograd.Function):
-    """loss_sum over all C x C entries of every query (csrc/pairwise.hip); backward = its true gradient.
-    kind 'betanet' (param = alpha0) or 'beta_evidential' (param = the annealing coefficient)."""
-
-    @staticmethod
-    def forward(ctx, score, targets, seg, Q, max_len, kind, param):
-        s = _vec(score.detach())
-        loss = _f1(s.device)
-        pairs = torch.empty(1, dtype=torch.int64, device=s.device)
-        part = torch.empty(max(Q, 1), dtype=torch.float64, device=s.device)
-        fwd = getattr(lib(), f"rr_{kind}_fwd_f32")
-        check(fwd(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, float(param), ptr(loss), ptr(pairs), ptr(part),
-                  stream()), f"rr_{kind}_fwd_f32")
-        ctx.save_for_backward(s, targets, seg)
-        ctx.meta = (Q, max_len, kind, float(param))
-        ctx.mark_non_differentiable(pairs)
-        return loss.reshape(()), pairs
-
-    @staticmethod
-    def backward(ctx, g, _gp):
-        s, targets, seg = ctx.saved_tensors
-        Q, max_len, kind, param = ctx.meta
-        g = g.reshape(-1).contiguous().float()
-        ds = torch.empty(s.shape[0], dtype=torch.float32, device=s.device)
-        bwd = getattr(lib(), f"rr_{kind}_bwd_f32")
-        check(bwd(ptr(s), s.stride(0), ptr(targets), ptr(seg), Q, max_len, param, ptr(g), ptr(ds), 1, stream()),
-              f"rr_{kind}_bwd_f32")
-        return ds, None, None, None, None, None, None
-
-
+# (loss_sum over all C x C entries of every query, csrc/pairwise.hip, through _WindowFn)
 def betanet_loss(y_pred, scope, targets, alpha0: float = 100.0, gpu: int = None):
     """The Beta-density KL loss of `beta_dis_train_loop` over a window of queries (reference train/train_pairwise.py:189-226):
     tau = sigmoid(targets), pi = sigmoid(score); per query the sum over ALL C x C entries of exp(lt) * (lt - lp), where lt / lp
@@ -837,12 +760,11 @@ def betanet_loss(y_pred, scope, targets, alpha0: float = 100.0, gpu: int = None)
 
     Returns (loss_sum, pairs) like ranknet_loss: loss_sum is differentiable (the trainer divides by the window's pairs and calls
     backward); pairs = sum of C * C - C (:198), an int64 device scalar.  `y_pred` may be [M] or [M, k] (first column)."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     if not alpha0 > 0:
         raise ValueError("betanet_loss: alpha0 must be positive")
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
-    return _SqPairFn.apply(y_pred, t, seg, len(scope), max_len, "betanet", alpha0)
+    return _WindowFn.apply("betanet", y_pred, t, seg, len(scope), max_len, (float(alpha0),), 1.0)
 
 
 def beta_evidential_loss(y_pred, scope, targets, coef: float, gpu: int = None):
@@ -851,10 +773,9 @@ def beta_evidential_loss(y_pred, scope, targets, coef: float, gpu: int = None):
     (tau_i + tau_j), P = p_j / (p_i + p_j); per query the sum over all C x C entries of (T1-P1)^2 + (T2-P2)^2 + (P1 (1-P1) +
     P2 (1-P2)) / (p_i + p_j + 1) + coef * 2 |ln(T1 / P1) (p_j - 1)|.  coef: the annealing coefficient (`annealing_coef`).
     Returns (loss_sum, pairs) like betanet_loss."""
-    if y_pred.dim() > 1:
-        y_pred = y_pred[:, 0]
+    y_pred = _first_column(y_pred)
     scope, seg, total, max_len, t = _prep(y_pred, scope, targets, gpu)
-    return _SqPairFn.apply(y_pred, t, seg, len(scope), max_len, "beta_evidential", coef)
+    return _WindowFn.apply("beta_evidential", y_pred, t, seg, len(scope), max_len, (float(coef),), 1.0)
 
 
 def sq_pairs(scope) -> int:

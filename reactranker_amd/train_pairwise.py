@@ -20,6 +20,41 @@ from .loss import (annealing_coef, approx_ndcg_loss, backward as loss_backward, 
                    lambdarank_loss, pair_softmax_mse, ranknet_lambda, ranknet_loss, sq_pairs)
 
 
+def _run_epoch(model, optimizer, scheduler, batches, exchange, plan, step, rank_mean: bool = False) -> float:
+    """The epoch skeleton of the four loops; returns the mean of the per-step losses (NaN when no batch made a step, as
+    np.mean of an empty list).  A loop supplies its decision per batch in two parts, around the zero_grad:
+      plan(b, ex, dev)  None - the window is skipped - or whatever `step` needs (the window's normaliser);
+      step(b, planned)  forward and backward; returns the [1] loss, or None when this rank's shard holds nothing: zero
+                        gradient, and a zero loss is recorded.
+    rank_mean: the gradient and the reported loss are the MEAN over the ranks (each rank normalised by its own count),
+    otherwise the plain sum (every rank normalised by the WINDOW's count already).
+    The per-step losses stay on the device until the epoch ends: no host synchronisation per step."""
+    from .dp import Exchange
+    own_exchange = exchange is None
+    ex = exchange if exchange is not None else Exchange(model)   # (under torch.distributed it owns the gradient bucket)
+    dev = next(model.parameters()).device
+    minibatch_loss = []
+    for b in batches:
+        planned = plan(b, ex, dev)
+        if planned is None:
+            continue
+        model.zero_grad()
+        loss = step(b, planned)
+        minibatch_loss.append(torch.zeros(1, device=dev) if loss is None else loss)
+        ex.reduce_grads(1.0 / ex.world if rank_mean else 1.0)
+        optimizer.step()
+        scheduler.step()
+    model.zero_grad()
+    if own_exchange:
+        ex.close()
+    if not minibatch_loss:
+        return float("nan")
+    per_step = ex.sum(torch.cat(minibatch_loss).double())
+    if rank_mean:
+        per_step = per_step / ex.world
+    return float(per_step.mean())
+
+
 def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, sigma: float = 1.0,
                              training_algo: str = "sum_session", gpu: int = 0, exchange=None, ndcg_k: int = 0,
                              temperature: float = 1.0) -> float:
@@ -36,54 +71,44 @@ def factorized_training_loop(epoch: int, model, optimizer, scheduler, batches: I
     stay on the device until the epoch ends: no host synchronisation per step (the reference reads `.item()` per query).
     exchange: a reactranker_amd.dp.Exchange; a batch is then this rank's shard of the window and the normaliser is the
     whole window's pair count."""
-    from .dp import Exchange, step_counts
+    from .dp import step_counts
     if training_algo not in ("sum_session", "accelerate_grad", "lambdarank", "approx_ndcg"):
         raise ValueError("training algo {} not implemented".format(training_algo))
-    own_exchange = exchange is None
-    ex = exchange if exchange is not None else Exchange(model)   # (under torch.distributed it owns the gradient bucket)
-    dev = next(model.parameters()).device
-    minibatch_loss = []
-    for b in batches:
+
+    def plan(b, ex, dev):
         if "_counts" not in b:
             b["_counts"] = step_counts(b["scope"], b["targets"]) if len(b["scope"]) else dict(queries=0, cands=0, pairs=0)
         local = b["_counts"]
         glob = ex.counts(b, dev)[1] if ex.on else local
+        # windows without any ordered pair carry no information (:101-103)
+        return (local, glob) if glob["pairs"] > 0 else None
+
+    def step(b, planned):
+        local, glob = planned
         pairs = glob["pairs"]
-        if pairs == 0:                                   # windows without any ordered pair carry no information (:101-103)
-            continue
-        model.zero_grad()
-        if local["pairs"] > 0:
-            y_pred = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
-            if y_pred.dim() > 1:
-                y_pred = y_pred[:, 0]
-            if training_algo == "lambdarank":
-                loss, _ = lambdarank_loss(y_pred, b["scope"], b["targets"], sigma, ndcg_k, gpu, pairs=pairs)
-                loss_backward(loss)
-            elif training_algo == "approx_ndcg":
-                loss, _ = approx_ndcg_loss(y_pred, b["scope"], b["targets"], temperature, ndcg_k, gpu, queries=glob["queries"])
+        if local["pairs"] == 0:                          # this rank's shard has no ordered pair
+            return None
+        y_pred = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
+        if y_pred.dim() > 1:
+            y_pred = y_pred[:, 0]
+        if training_algo == "lambdarank":
+            loss, _ = lambdarank_loss(y_pred, b["scope"], b["targets"], sigma, ndcg_k, gpu, pairs=pairs)
+            loss_backward(loss)
+        elif training_algo == "approx_ndcg":
+            loss, _ = approx_ndcg_loss(y_pred, b["scope"], b["targets"], temperature, ndcg_k, gpu, queries=glob["queries"])
+            loss_backward(loss)
+        else:
+            loss_sum, _ = ranknet_loss(y_pred if training_algo == "sum_session" else y_pred.detach(), b["scope"],
+                                       b["targets"], sigma, gpu)
+            loss = loss_sum / pairs
+            if training_algo == "sum_session":
                 loss_backward(loss)
             else:
-                loss_sum, _ = ranknet_loss(y_pred if training_algo == "sum_session" else y_pred.detach(), b["scope"],
-                                           b["targets"], sigma, gpu)
-                loss = loss_sum / pairs
-                if training_algo == "sum_session":
-                    loss_backward(loss)
-                else:
-                    back = ranknet_lambda(y_pred, b["scope"], b["targets"], sigma, gpu)
-                    y_pred.backward(back / pairs)
-            minibatch_loss.append(loss.detach().sum().reshape(1))
-        else:                                            # this rank's shard has no ordered pair: zero gradient, zero loss
-            minibatch_loss.append(torch.zeros(1, device=dev))
-        ex.reduce_grads(1.0)                             # already normalised by the WINDOW's count: a plain sum
-        optimizer.step()
-        scheduler.step()
-    model.zero_grad()
-    if own_exchange:
-        ex.close()
-    if not minibatch_loss:
-        return float("nan")
-    per_step = ex.sum(torch.cat(minibatch_loss).double())
-    return float(per_step.mean())
+                back = ranknet_lambda(y_pred, b["scope"], b["targets"], sigma, gpu)
+                y_pred.backward(back / pairs)
+        return loss.detach().sum().reshape(1)
+
+    return _run_epoch(model, optimizer, scheduler, batches, exchange, plan, step)
 
 
 def window_sq_pairs(batch, exchange, device) -> tuple:
@@ -103,34 +128,20 @@ def window_sq_pairs(batch, exchange, device) -> tuple:
 
 
 def _sq_pair_loop(loss_of, model, optimizer, scheduler, batches, gpu, exchange) -> float:
-    from .dp import Exchange
-    own_exchange = exchange is None
-    ex = exchange if exchange is not None else Exchange(model)
-    dev = next(model.parameters()).device
-    minibatch_loss = []
-    for b in batches:
-        local, pairs = window_sq_pairs(b, ex, dev)
-        if pairs == 0:                                   # nothing to normalise by (the reference would divide by zero)
-            continue
-        model.zero_grad()
-        if len(b["scope"]) > 0:
-            y_pred = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
-            loss_sum, _ = loss_of(y_pred, b["scope"], b["targets"])
-            loss = loss_sum / pairs
-            loss_backward(loss)
-            minibatch_loss.append(loss.detach().sum().reshape(1))
-        else:                                            # an empty shard: zero gradient, zero loss
-            minibatch_loss.append(torch.zeros(1, device=dev))
-        ex.reduce_grads(1.0)                             # already normalised by the WINDOW's count: a plain sum
-        optimizer.step()
-        scheduler.step()
-    model.zero_grad()
-    if own_exchange:
-        ex.close()
-    if not minibatch_loss:
-        return float("nan")
-    per_step = ex.sum(torch.cat(minibatch_loss).double())
-    return float(per_step.mean())
+    def plan(b, ex, dev):
+        pairs = window_sq_pairs(b, ex, dev)[1]
+        return pairs if pairs > 0 else None              # nothing to normalise by (the reference would divide by zero)
+
+    def step(b, pairs):
+        if len(b["scope"]) == 0:                         # an empty shard
+            return None
+        y_pred = model(b["r"], b["p"], gpu=gpu, add_features=b.get("add"))
+        loss_sum, _ = loss_of(y_pred, b["scope"], b["targets"])
+        loss = loss_sum / pairs
+        loss_backward(loss)
+        return loss.detach().sum().reshape(1)
+
+    return _run_epoch(model, optimizer, scheduler, batches, exchange, plan, step)
 
 
 def beta_dis_train_loop(epoch: int, model, optimizer, scheduler, batches: Iterable, alpha0: float = 100, gpu: int = 0,
@@ -168,25 +179,11 @@ def baseline_pairwise_training_loop(epoch: int, epochs: int, model, optimizer, s
     `max_coeff` are accepted and unused).  Returns the mean of the per-step losses (NaN when no batch was whole, as np.mean of
     an empty list).  exchange: every rank holds its own pair batches of one global step and the same number of them; the
     gradient is the mean over the ranks."""
-    from .dp import Exchange
-    own_exchange = exchange is None
-    ex = exchange if exchange is not None else Exchange(model)
-    minibatch_loss = []
-    for b in pair_batches:
-        if len(b["targets"]) < batch_size:
-            continue
-        model.zero_grad()
+    def step(b, _):
         y_pred = model(b["r"], b["p1"], b["p2"], gpu=gpu)
         loss = pair_softmax_mse(y_pred, b["targets"])
         loss_backward(loss)
-        minibatch_loss.append(loss.detach().reshape(1))
-        ex.reduce_grads(1.0 / ex.world)
-        optimizer.step()
-        scheduler.step()
-    model.zero_grad()
-    if own_exchange:
-        ex.close()
-    if not minibatch_loss:
-        return float("nan")
-    per_step = ex.sum(torch.cat(minibatch_loss).double()) / ex.world
-    return float(per_step.mean())
+        return loss.detach().reshape(1)
+
+    return _run_epoch(model, optimizer, scheduler, pair_batches, exchange,
+                      lambda b, ex, dev: True if len(b["targets"]) >= batch_size else None, step, rank_mean=True)

@@ -1,5 +1,5 @@
 """Isolated timing of the LambdaRank step launch (rr_lambdarank_step_f32: loss and gradient in one launch) next to RankNet's
-two launches for the same window (rr_ranknet_fwd_f32, which ends in two reduction launches, + rr_ranknet_bwd_f32), at the
+two entry points for the same window (rr_ranknet_fwd_f32, which ends in the one-wave finish launch, + rr_ranknet_bwd_f32), at the
 workload's window (256 queries of 64 candidates) and at long lists (64 queries of 1000):
     python tools/lambdarank_bench.py
 Prints microseconds per call (median of 5 x 30 back-to-back calls) and pairs per second.  No threshold: LambdaRank does more
