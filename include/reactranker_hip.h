@@ -810,6 +810,12 @@ int rr_uq_calibration_f64(const float* err, const float* unc, const int64_t* ord
                           const double* fractions, int n_frac, void* workspace, size_t workspace_bytes, double* out,
                           rr_stream_t stream);
 
+/* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
+ * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
+ * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it
+ * too, so this count is where a missing one shows; the long-list tests read it. */
+long long rr_lds_opt_ins(void);
+
 /* LogCumsumExp along dim 0 of a 1-D tensor (train/loss.py:9-61); n <= 8192.
  * backward keeps the reference's un-shifted exp(x) (:59). */
 int rr_logcumsumexp_fwd_f32(const float* x, int n, float* y, rr_stream_t stream);

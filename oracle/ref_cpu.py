@@ -350,7 +350,7 @@ def ranknet_pairs(targets_q: torch.Tensor):
     rel = targets_q.reshape(-1, 1) - targets_q.reshape(1, -1)
     pos = (rel > 0).to(torch.float32)
     neg = (rel < 0).to(torch.float32)
-    return pos, neg, 2.0 * pos.sum()
+    return pos, neg, 2.0 * pos.sum(dtype=torch.float64)                     # (a float32 sum is inexact above 2^24 pairs)
 
 
 def ranknet_sum_session(score, scope, targets, sigma=1.0):

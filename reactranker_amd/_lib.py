@@ -167,6 +167,7 @@ class Grads(C.Structure):
 _SIGS = {
     "rr_strerror": (C.c_char_p, [i32]),
     "rr_version": (i32, []),
+    "rr_lds_opt_ins": (C.c_longlong, []),
     "rr_abi_struct_sizes": (None, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "rr_gather_sum_f32": (i32, [c_f32p, i64, i64, c_i32p, i64, i32, i32, c_f32p, i64, c_stream]),
     "rr_abi_gather_epi_size": (C.c_size_t, []),

@@ -16,6 +16,8 @@
 // (train/loss.py:86-97, 338-347, 504-554; train/train_pairwise.py:99-137).
 #include "loss_list.h"
 
+std::atomic<long long> rr_lds_opt_in_count{0};
+
 namespace {
 
 // ---------------------------------------------------------------- fused loss + gradient launches ("step" entry points)
@@ -158,7 +160,9 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_fwd_kernel(const float* __res
     t[i] = targets[off + i];
   }
   wave_sync();
-  float acc = 0.f;
+  // The pair costs are float32; their sum is kept in double: a lane adds C * C / 64 of them (a million at C = 8192), and a
+  // float32 running sum of ~1e6 rounds every further cost of ~1 to 1/16 - 6.5e-4 of the loss at 8192, 1e-4 at 5462.
+  double acc = 0.0;
   int npos = 0;
   for (int i = lane; i < C; i += RR_WAVE) {
     const float ti = t[i], si = s[i];
@@ -167,18 +171,18 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_fwd_kernel(const float* __res
       const float x = sigma * (si - s[j]);
       if (rel > 0.f) {
         ++npos;
-        acc += logf(1.0f + expf(-x));                              // C_pos, train_pairwise.py:119 (naive, may be inf)
+        acc += static_cast<double>(logf(1.0f + expf(-x)));         // C_pos, train_pairwise.py:119 (naive, may be inf)
       } else if (rel < 0.f) {
-        acc += logf(1.0f + expf(x));                               // C_neg, train_pairwise.py:120
+        acc += static_cast<double>(logf(1.0f + expf(x)));          // C_neg, train_pairwise.py:120
       }
     }
   }
   int tot = npos;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, RR_WAVE);
-  acc = rr_wave_sum(acc);
+  acc = wave_sum_f64(acc);
   if (lane == 0) {
-    partial[2 * q] = tot > 0 ? acc : 0.f;                          // pair-less queries are skipped, :103-104
+    partial[2 * q] = tot > 0 ? static_cast<float>(acc) : 0.f;      // pair-less queries are skipped, :103-104
     reinterpret_cast<int32_t*>(partial)[2 * q + 1] = 2 * tot;      // num_pairs, train_pairwise.py:106
   }
 }
@@ -204,18 +208,18 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_bwd_kernel(const float* __res
   int npos = 0;
   for (int i = lane; i < C; i += RR_WAVE) {
     const float ti = t[i], si = s[i];
-    float lam = 0.f;
-    for (int j = 0; j < C; ++j) {
+    double lam = 0.0;                                              // (float32 terms summed in double, as the forward does:
+    for (int j = 0; j < C; ++j) {                                  // a float32 row sum is 1.4e-5 of the largest lambda off at 8192)
       const float rel = ti - t[j];
       const float x = sigma * (si - s[j]);
       if (rel > 0.f) {
         ++npos;
-        lam += -sigma / (1.0f + expf(x));                          // train_pairwise.py:126,128
+        lam += static_cast<double>(-sigma / (1.0f + expf(x)));     // train_pairwise.py:126,128
       } else if (rel < 0.f) {
-        lam += sigma / (1.0f + expf(-x));                          // train_pairwise.py:127,128
+        lam += static_cast<double>(sigma / (1.0f + expf(-x)));     // train_pairwise.py:127,128
       }
     }
-    lamv[i] = lam;
+    lamv[i] = static_cast<float>(lam);
   }
   int tot = npos;
 #pragma unroll
@@ -791,6 +795,8 @@ int nig_launch(const NigIn& in, const float* targets, int64_t n, int cross, floa
 }  // namespace
 
 extern "C" {
+
+long long rr_lds_opt_ins(void) { return rr_lds_opt_in_count.load(std::memory_order_relaxed); }
 
 int rr_listmle_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, float* loss, float* partial, rr_stream_t stream) {

@@ -3,7 +3,14 @@
 // launch of a "one workgroup per query" kernel (launch_per_query).  Everything lives in an unnamed namespace: each
 // translation unit gets its own copy.
 #pragma once
+#include <atomic>
+
 #include "rr_common.h"
+
+// How many launches have opted in to more than 64 KiB of dynamic LDS (set_lds below); defined in loss.hip and read by
+// rr_lds_opt_ins().  The HIP runtime of today launches such a kernel without the opt-in as well, so a kernel or a template
+// instantiation that misses it computes the same numbers: this count is the one place where the tests can see it.
+extern __attribute__((visibility("hidden"))) std::atomic<long long> rr_lds_opt_in_count;   // not an export
 
 namespace {
 
@@ -27,6 +34,7 @@ int set_lds(Kern k, size_t bytes) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                             static_cast<int>(bytes)) != hipSuccess)
       return RR_ERR_LAUNCH;
+    rr_lds_opt_in_count.fetch_add(1, std::memory_order_relaxed);
   }
   return RR_OK;
 }

@@ -12,16 +12,23 @@ def _segments(scope):
     return [(int(off[i]), int(off[i + 1])) for i in range(len(scope))]
 
 
-def _betanet_query(t, s, alpha0):
+def _pair_grids(x, rows):
+    """(a, b) with a[i, j] = x[j] and b[i, j] = x[i] for the rows i of `rows` (None: all of them, b = a.t() as the reference
+    writes it)"""
+    if rows is None:
+        a = torch.ones_like(x).unsqueeze(1) * x
+        return a, a.t()
+    return torch.ones_like(x[rows]).unsqueeze(1) * x, x[rows].unsqueeze(1) * torch.ones_like(x)
+
+
+def _betanet_query(t, s, alpha0, rows=None):
     tau = torch.sigmoid(t)
-    alpha_ini = torch.ones_like(tau).unsqueeze(1) * tau                    # [i, j] = tau[j]
-    beta_ini = alpha_ini.t()
+    alpha_ini, beta_ini = _pair_grids(tau, rows)                           # [i, j] = tau[j], tau[i]
     x1 = alpha_ini / (alpha_ini + beta_ini)
     x2 = beta_ini / (alpha_ini + beta_ini)
     aT, bT = x1 * alpha0, x2 * alpha0
     pi = torch.sigmoid(s)
-    pa = torch.ones_like(pi).unsqueeze(1) * pi
-    pb = pa.t()
+    pa, pb = _pair_grids(pi, rows)
     aP, bP = pa / (pa + pb) * alpha0, pb / (pa + pb) * alpha0
     lnB_t = torch.lgamma(aT) + torch.lgamma(bT) - torch.lgamma(aT + bT)
     lt = (aT - 1) * torch.log(x1) + (bT - 1) * torch.log(x2) - lnB_t
@@ -30,13 +37,11 @@ def _betanet_query(t, s, alpha0):
     return torch.sum(torch.exp(lt) * (lt - lp))
 
 
-def _beta_evi_query(t, p, coef):
+def _beta_evi_query(t, p, coef, rows=None):
     tau = torch.sigmoid(t)
-    alpha_ini = torch.ones_like(tau).unsqueeze(1) * tau
-    beta_ini = alpha_ini.t()
+    alpha_ini, beta_ini = _pair_grids(tau, rows)
     T1, T2 = alpha_ini / (alpha_ini + beta_ini), beta_ini / (alpha_ini + beta_ini)
-    pa = torch.ones_like(p).unsqueeze(1) * p
-    pb = pa.t()
+    pa, pb = _pair_grids(p, rows)
     P1, P2 = pa / (pa + pb), pb / (pa + pb)
     err = (T1 - P1) ** 2 + (T2 - P2) ** 2
     var = P1 * (1 - P1) / (pa + pb + 1) + P2 * (1 - P2) / (pa + pb + 1)
@@ -45,14 +50,26 @@ def _beta_evi_query(t, p, coef):
     return torch.sum(err + var + coef * (pen1 + pen2))
 
 
-def sq_loss(kind, scores, scope, targets, param, dtype=torch.float64):
+def sq_loss(kind, scores, scope, targets, param, dtype=torch.float64, block=None):
     """(loss_sum, pairs, d loss_sum / d scores) of 'betanet' (param = alpha0) or 'beta_evidential' (param = coef) over a
-    window, evaluated in `dtype` from float32 inputs."""
+    window, evaluated in `dtype` from float32 inputs.  block: None builds every query's C x C tensors whole, as the reference
+    does; a row count evaluates them `block` rows at a time, each block's share back-propagated on its own (the same sums;
+    a query of 5462 candidates would otherwise hold several GB of float64 under autograd)."""
     s = torch.tensor(np.asarray(scores, np.float32)).to(dtype).requires_grad_(True)
     t = torch.tensor(np.asarray(targets, np.float32)).to(dtype)
     fn = _betanet_query if kind == "betanet" else _beta_evi_query
-    total = torch.zeros((), dtype=dtype)
     pairs = 0
+    if block is not None:
+        total = 0.0
+        for lo, hi in _segments(scope):
+            pairs += (hi - lo) ** 2 - (hi - lo)
+            for r0 in range(0, hi - lo, block):
+                part = fn(t[lo:hi], s[lo:hi], param, slice(r0, min(r0 + block, hi - lo)))
+                part.backward()
+                total += float(part.detach())
+        g = s.grad if s.grad is not None else torch.zeros_like(s)
+        return total, pairs, g.numpy().astype(np.float64)
+    total = torch.zeros((), dtype=dtype)
     for lo, hi in _segments(scope):
         if hi > lo:
             total = total + fn(t[lo:hi], s[lo:hi], param)
@@ -64,23 +81,27 @@ def sq_loss(kind, scores, scope, targets, param, dtype=torch.float64):
     return float(total.detach()), pairs, g.detach().numpy().astype(np.float64)
 
 
-def pairwise_stats(scores, scope, targets, sigma=1.0):
+def pairwise_stats(scores, scope, targets, sigma=1.0, block=None):
     """(pairwise_acc, eval_cross_entropy_loss, per-query [npos, mismatches, ce]) in float64; the score differences are formed
-    in float32 as the reference's tensors are."""
+    in float32 as the reference's tensors are.  block: rows of a query's C x C arrays evaluated at a time (None: all)."""
     s = np.asarray(scores, np.float32)
     t = np.asarray(targets, np.float32)
     accs, ce_sum, n_pairs, rows = [], 0.0, 0.0, []
     for lo, hi in _segments(scope):
         sq, tq = s[lo:hi], t[lo:hi]
-        tp = tq[:, None] > tq[None, :]
-        sp = sq[:, None] > sq[None, :]
-        npos = float(tp.sum())
-        mism = float((tp != sp).sum())
-        x = (np.float32(sigma) * (sq[:, None] - sq[None, :])).astype(np.float64)
-        softplus = np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
-        S = np.sign(tq[:, None].astype(np.float64) - tq[None, :])
-        C = 0.5 * (1.0 - S) * x + softplus                                # -logsigmoid(-x) = softplus(x)
-        ce = float((C * (S != 0)).sum())
+        npos, mism, ce = 0.0, 0.0, 0.0
+        step = block or max(hi - lo, 1)
+        for r0 in range(0, hi - lo, step):
+            sr, tr = sq[r0:r0 + step], tq[r0:r0 + step]
+            tp = tr[:, None] > tq[None, :]
+            sp = sr[:, None] > sq[None, :]
+            npos += float(tp.sum())
+            mism += float((tp != sp).sum())
+            x = (np.float32(sigma) * (sr[:, None] - sq[None, :])).astype(np.float64)
+            softplus = np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
+            S = np.sign(tr[:, None].astype(np.float64) - tq[None, :])
+            C = 0.5 * (1.0 - S) * x + softplus                            # -logsigmoid(-x) = softplus(x)
+            ce += float((C * (S != 0)).sum())
         rows.append([npos, mism, ce])
         if npos > 0:
             accs.append(1.0 - mism / (2.0 * npos))

@@ -1,6 +1,13 @@
 """GPU parity of the fused loss kernels: against vectors produced by the reference itself
 (tests/golden/losses.npz) and against the CPU oracle on fresh random lists (ragged, C in
-{1,2,3,32,64,65,129,300}).  Tolerance 1e-5 * (1 + |ref|)."""
+{1,2,3,32,64,65,129,300}).  Tolerance 1e-5 * (1 + |ref|).
+
+Every gradient of the two parity tests is ALSO held to max |g - ref| / max |ref| <= 1e-5 (close_scaled; the measure of
+tests/test_gpu_lambdarank.py and tests/test_gpu_long_lists.py): gradient entries shrink as 1 / (C * Q), where the first form
+is an absolute 1e-5 - a ListNet gradient 5 % wrong passes it on [64] * 64.  Headroom: the float32 CPU oracle measures
+<= 2.5e-7 against the float64 one on the four random windows, and the reference's own float32 vectors of
+tests/golden/losses.npz sit within 3.8e-7 of the float64 oracle (worst: evid_gv) - both below 1.25e-6, so the project's
+1e-5 leaves the device ~30x."""
 import numpy as np
 import pytest
 import torch
@@ -23,6 +30,16 @@ def close(got, ref, tol=1e-5, what=""):
     assert err <= tol, f"{what}: err {err:.3e}"
 
 
+def close_scaled(got, ref, what, tol=1e-5):
+    """max |got - ref| / max |ref| over the whole gradient (absolute where the reference is all zeros: a one-candidate list)"""
+    got = got.detach().cpu().double().numpy().reshape(-1)
+    ref = ref.detach().cpu().double().numpy().reshape(-1) if torch.is_tensor(ref) else np.asarray(ref, np.float64).reshape(-1)
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    err = float(np.max(np.abs(got - ref)) / (np.max(np.abs(ref)) or 1.0)) if got.size else 0.0
+    Hh.record(what + " scaled", err, tol)
+    assert err <= tol, f"{what}: scaled err {err:.3e}"
+
+
 @pytest.mark.parametrize("name", CASES)
 def test_losses_against_reference_vectors(name, golden_dir):
     L = np.load(golden_dir + "/losses.npz")
@@ -38,12 +55,14 @@ def test_losses_against_reference_vectors(name, golden_dir):
     assert l.shape == (1,)
     l.sum().backward()
     close(l, L[P + "mle"], what="mle"); close(s.grad, L[P + "mle_g"], what="mle_g")
+    close_scaled(s.grad, L[P + "mle_g"], "mle_g")
 
     s = fresh()
     l = RL.ListnetLoss()(s, scope, targets, 0)
     assert l.dim() == 0
     l.backward()
     close(l, L[P + "listnet"], what="listnet"); close(s.grad, L[P + "listnet_g"], what="listnet_g")
+    close_scaled(s.grad, L[P + "listnet_g"], "listnet_g")
 
     poss = torch.stack([torch.tensor(L[P + "score"]), torch.tensor(L[P + "var"])], 1).cuda().requires_grad_(True)
     l = RL.evidential_ranking()(poss, scope, targets, 0.01, 0, 10, 0)
@@ -52,17 +71,19 @@ def test_losses_against_reference_vectors(name, golden_dir):
     close(l, L[P + "evid"], what="evid")
     close(poss.grad[:, 0], L[P + "evid_gs"], tol=1e-5, what="evid_gs")
     close(poss.grad[:, 1], L[P + "evid_gv"], tol=1e-5, what="evid_gv")
+    close_scaled(poss.grad[:, 0], L[P + "evid_gs"], "evid_gs"); close_scaled(poss.grad[:, 1], L[P + "evid_gv"], "evid_gv")
 
     s = fresh()
     l = RL.MSELoss()(s, targets)
     l.backward()
-    close(l, L[P + "mse"]); close(s.grad, L[P + "mse_g"])
+    close(l, L[P + "mse"]); close(s.grad, L[P + "mse_g"]); close_scaled(s.grad, L[P + "mse_g"], "mse_g")
 
     s = fresh()
     v = torch.tensor(L[P + "var"]).cuda().requires_grad_(True)
     l = RL.GaussDisLoss()(s, v, targets, 0)
     l.backward()
     close(l, L[P + "gauss"]); close(s.grad, L[P + "gauss_gs"]); close(v.grad, L[P + "gauss_gv"], tol=1e-5)
+    close_scaled(s.grad, L[P + "gauss_gs"], "gauss_gs"); close_scaled(v.grad, L[P + "gauss_gv"], "gauss_gv")
 
     for sigma in (1.0, 0.5):
         s = fresh()
@@ -74,8 +95,10 @@ def test_losses_against_reference_vectors(name, golden_dir):
         (ls / pairs).backward()
         close(ls / pairs, L[P + f"rank_ss_{sigma}"], what="rank_ss")
         close(s.grad, L[P + f"rank_ss_g_{sigma}"], what="rank_ss_g")
+        close_scaled(s.grad, L[P + f"rank_ss_g_{sigma}"], "rank_ss_g")
         lam = RL.ranknet_lambda(s.detach(), scope, targets, sigma, 0) / pairs
         close(lam, L[P + f"rank_ag_g_{sigma}"], what="rank_ag_g")
+        close_scaled(lam, L[P + f"rank_ag_g_{sigma}"], "rank_ag_g")
 
 
 def test_logcumsumexp_op_and_ranknet_overflow(golden_dir):
@@ -107,12 +130,12 @@ def test_losses_against_oracle_random(seed, scope):
     ref = O.listmle_loss(ts, scope, tt); g_ref, = torch.autograd.grad(ref.sum(), ts)
     s = torch.tensor(score).cuda().requires_grad_(True)
     l = RL.MLEloss()(s, scope, tt, 0); l.sum().backward()
-    close(l, ref, what="mle"); close(s.grad, g_ref, what="mle_g")
+    close(l, ref, what="mle"); close(s.grad, g_ref, what="mle_g"); close_scaled(s.grad, g_ref, "mle_g")
 
     ref = O.listnet_loss(ts, scope, tt); g_ref, = torch.autograd.grad(ref, ts)
     s = torch.tensor(score).cuda().requires_grad_(True)
     l = RL.ListnetLoss()(s, scope, tt, 0); l.backward()
-    close(l, ref, what="listnet"); close(s.grad, g_ref, what="listnet_g")
+    close(l, ref, what="listnet"); close(s.grad, g_ref, what="listnet_g"); close_scaled(s.grad, g_ref, "listnet_g")
 
     ref = O.evidential_ranking_loss(torch.stack([ts, tv], 1), scope, tt)
     gs_ref, gv_ref = torch.autograd.grad(ref.sum(), [ts, tv])
@@ -121,6 +144,7 @@ def test_losses_against_oracle_random(seed, scope):
     close(l, ref, tol=1e-5, what="evid")
     sc = max(1.0, float(gv_ref.abs().max()))
     close(poss.grad[:, 0], gs_ref, tol=5e-5, what="evid_gs"); close(poss.grad[:, 1] / sc, gv_ref / sc, tol=5e-5, what="evid_gv")
+    close_scaled(poss.grad[:, 0], gs_ref, "evid_gs"); close_scaled(poss.grad[:, 1], gv_ref, "evid_gv")
 
     ref, pairs_ref = O.ranknet_sum_session(ts, scope, tt, 1.0)
     s = torch.tensor(score).cuda().requires_grad_(True)
@@ -130,6 +154,7 @@ def test_losses_against_oracle_random(seed, scope):
         g_ref, = torch.autograd.grad(ref / pairs_ref, ts)
         (ls / pairs).backward()
         close(ls / pairs, ref / pairs_ref, what="ranknet"); close(s.grad, g_ref, what="ranknet_g")
+        close_scaled(s.grad, g_ref, "ranknet_g")
 
 
 def test_strided_score_column_and_query_permutation_invariance():

@@ -84,3 +84,40 @@ def test_numpy_cross_form_agrees_with_torch_broadcasting():
     assert abs(got[0] - float(l.detach())) < 1e-12
     for x, g in zip(got[1:], gs):
         assert np.allclose(x, g.numpy().reshape(-1), rtol=1e-10, atol=1e-13)
+
+
+# the golden keys of every restatement of tests/listwise_variants_ref.py: (value key, input columns, gradient suffixes)
+VARIANT_KEYS = {
+    "mledis": ("mledis", ["score", "var"], ["_gs", "_gv"]),
+    "listnet_gauss": ("lgauss", ["score", "var"], ["_gs", "_gv"]),
+    "listnet_lognorm": ("llognorm", ["pos", "var"], ["_gs", "_gv"]),
+    "listnet_evidential": ("levid", ["score", "nu", "alpha"], ["_gs", "_gv", "_ga"]),
+    "listnet_uq": ("uq", ["pos"], ["_g"]),
+    "dirichlet_uq": ("dir", ["conc"], ["_g"]),
+}
+
+
+@pytest.mark.parametrize("case", ["single", "tiny", "c32", "c64", "ragged", "long"])
+@pytest.mark.parametrize("kind", list(VARIANT_KEYS))
+def test_listwise_restatements_reproduce_the_reference_vectors(kind, case, golden_dir):
+    """tests/listwise_variants_ref.py against the reference's own float32 run (tests/golden/loss_variants.npz), values and
+    every gradient: |loss - ref| / |ref| and max |g - ref| / max |ref| (absolute where the reference is exactly zero, as for
+    the score gradient of a one-candidate list).  Evaluated in float32 the restatement is the reference's operation, in
+    blocks of 50 rows so that the blocked sums are what is checked: 1e-6, a dozen float32 roundings of 6e-8.  Evaluated in
+    float64 it sits where float32 rounding puts the reference: 1e-5, the project's parity bound."""
+    import os
+    from tests import listwise_variants_ref as LV
+    V = np.load(os.path.join(golden_dir, "loss_variants.npz"))
+    mc, ep, eps = V["uq_args"].tolist()
+    coef = mc * (ep / (eps - 1)) ** 3
+    key, cols, sfx = VARIANT_KEYS[kind]
+    P = case + "."
+    for dtype, bound in ((torch.float32, 1e-6), (torch.float64, 1e-5)):
+        loss, grads = LV.variant_loss(kind, [V[P + c] for c in cols], V[P + "scope"].tolist(), V[P + "targets"], coef,
+                                      dtype=dtype, block=50)
+        ref = float(V[P + key].reshape(-1)[0])
+        assert abs(loss - ref) / (abs(ref) or 1.0) <= bound, (dtype, loss, ref)
+        for g, s in zip(grads, sfx):
+            r = V[P + key + s].astype(np.float64).reshape(-1)
+            assert g.shape == r.shape
+            assert np.max(np.abs(g - r)) / (np.max(np.abs(r)) or 1.0) <= bound, (dtype, s)

@@ -175,3 +175,25 @@ def test_pair_model_shares_the_state_dict_of_base_model():
     assert ranknet_baseline.build_model(task_num=2, ffn_last_layer="with_softplus", hidden_size=32).ffn.task_type == "gaussian_with_softplus"
     assert ranknet_baseline.build_model(task_num=4, ffn_last_layer="with_softplus", hidden_size=32).ffn.task_type == "evidential_with_softplus"
     assert ranknet_baseline.build_model(task_num=1, ffn_last_layer="no_softplus", hidden_size=32).ffn.task_type == "no_softplus"
+
+
+def test_row_blocked_restatements_equal_the_unblocked_ones(V):
+    """sq_loss(block=...) / pairwise_stats(block=...) evaluate a query's C x C arrays a few rows at a time (the long-list GPU
+    tests need that: 5462^2 float64 entries, twenty times over under autograd).  Same terms, summed block by block: float64
+    agreement to 1e-12 relative on the golden sq.c300 case, for a block that does not divide 300; the integer counts of
+    pairwise_stats exactly."""
+    a0 = float(V["alpha0"])
+    mc, ep, eps = V["evi_args"].tolist()
+    coef = mc * (ep / (eps - 1)) ** 3
+    P = "sq.c300."
+    scope, t = V[P + "scope"].tolist(), V[P + "targets"]
+    for key, x, param in (("betanet", V[P + "score"], a0), ("beta_evidential", V[P + "pos"], coef)):
+        l0, n0, g0 = R.sq_loss(key, x, scope, t, param)
+        l1, n1, g1 = R.sq_loss(key, x, scope, t, param, block=64)
+        assert n0 == n1
+        assert abs(l1 - l0) <= 1e-12 * abs(l0), key
+        assert np.max(np.abs(g1 - g0)) <= 1e-12 * np.max(np.abs(g0)), key
+    a, c, rows = R.pairwise_stats(V["eval.scores"], V["eval.scope"].tolist(), V["eval.targets"], float(V["eval.sigma"]))
+    ab, cb, rows_b = R.pairwise_stats(V["eval.scores"], V["eval.scope"].tolist(), V["eval.targets"], float(V["eval.sigma"]), block=3)
+    assert np.array_equal(rows[:, :2], rows_b[:, :2]) and a == ab
+    assert np.max(np.abs(rows[:, 2] - rows_b[:, 2])) <= 1e-12 * np.max(np.abs(rows[:, 2])) and abs(c - cb) <= 1e-12 * abs(c)
