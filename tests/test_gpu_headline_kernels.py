@@ -133,6 +133,12 @@ def _hip_gates(model, rb, masks):
 
 
 def _train_step_vs_fp64_oracle(cfg, Q, Cn, loss_kind, p, atoms_lo, atoms_hi, seed, log):
+    """train_step_vs_fp64_oracle on synth.make_queries(seed + 1, Q, Cn) packed with K = 4, above 8192 atom and bond rows."""
+    qb = synth.make_queries(seed + 1, Q, Cn, atoms_lo=atoms_lo, atoms_hi=atoms_hi)
+    train_step_vs_fp64_oracle(cfg, qb, 4, loss_kind, p, seed, log, rows_above=8192)
+
+
+def train_step_vs_fp64_oracle(cfg, qb, K, loss_kind, p, seed, log, rows_above=None):
     """One training step (train mode, dropout p, step plan, shared reactant prefix) against the fp64 oracle with
     identical dropout masks.  Two finite-precision evaluations of a ReLU network differ in KIND, not only in rounding,
     wherever a pre-activation lies within their error of zero: the gate opens in one and stays shut in the other, and each
@@ -144,15 +150,16 @@ def _train_step_vs_fp64_oracle(cfg, Q, Cn, loss_kind, p, atoms_lo, atoms_hi, see
          the tight bound - 5e-5 of the tensor's largest entry, or 3 x the fp32 oracle's own distance to fp64 under the
          same gates - with no outlier allowance;
       3. scores and loss within 1e-5 (1 + |ref|), or 3 x the fp32 oracle's distance where that is larger.
-    The measured numbers (flips per layer, errors with natural and with dictated gates) go to the parity log."""
+    The measured numbers (flips per layer, errors with natural and with dictated gates) go to the parity log.
+    qb: the query batch; K: the pad width both sides are packed with (None: each side's own); seed: the weights'."""
     H, d, dd = cfg["hidden_size"], cfg["mpnn_depth"], cfg["mpnn_diff_depth"]
     shapes = O.model_shapes(H, d, dd, cfg["ffn_depth"], cfg["task_num"], cfg["add_features_dim"], cfg["use_bias"])
     w = synth.seeded_weights(shapes, seed)
     model = make_model(cfg, w, dropout=p).train()
     model.dropout_seed = 0xABCDEF0123
-    qb = synth.make_queries(seed + 1, Q, Cn, atoms_lo=atoms_lo, atoms_hi=atoms_hi)
-    rb, pb = featurization.BatchMolGraph(qb.r_specs, K=4), featurization.BatchMolGraph(qb.p_specs, K=4)
-    assert rb.n_atoms > 8192 and rb.n_bonds > 8192, (rb.n_atoms, rb.n_bonds)   # the 12-wave geometry for every encoder GEMM
+    rb, pb = featurization.BatchMolGraph(qb.r_specs, K=K), featurization.BatchMolGraph(qb.p_specs, K=K)
+    if rows_above is not None:                           # 8192: the 12-wave geometry for every encoder GEMM
+        assert rb.n_atoms > rows_above and rb.n_bonds > rows_above, (rb.n_atoms, rb.n_bonds)
     M = len(qb.p_specs)
     masks = _masks_for(model, model.dropout_seed, rb, pb, M, cfg["add_features_dim"], p)
     scope, targets = qb.scope, torch.tensor(qb.targets)
@@ -171,7 +178,7 @@ def _train_step_vs_fp64_oracle(cfg, Q, Cn, loss_kind, p, atoms_lo, atoms_hi, see
         P = {k: v.detach().to(dt).requires_grad_(v.requires_grad) for k, v in O.params_from_numpy(w, requires_grad=True).items()}
 
         def gt(specs):
-            g = O.graph_tensors(O.pack_batch(specs, K=4))
+            g = O.graph_tensors(O.pack_batch(specs, K=K))
             g["f_atoms"], g["f_bonds"] = g["f_atoms"].to(dt), g["f_bonds"].to(dt)
             return g
         mk = {k: v.to(dt) for k, v in masks.items()}
