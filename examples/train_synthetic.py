@@ -92,6 +92,8 @@ def main():
     ap.add_argument("--ndcg-k", type=int, default=0, help="with --train-strategy lambdarank | approx_ndcg: NDCG truncation (0: the whole list)")
     ap.add_argument("--temperature", type=float, default=1.0, help="with --train-strategy approx_ndcg: soft-rank temperature, in score units")
     ap.add_argument("--pair-batch", type=int, default=256, help="with --task-type pair_baseline: pairs per optimizer step")
+    ap.add_argument("--save-metric", default="NDCG@all", help="listwise task types: the checkpoint criterion, e.g. NDCG@all | average_score | "
+                    "kendall_tau | spearman | mrr (the last three: mean per-query rank correlation, eval.rank_correlation)")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--queries", type=int, default=256)
     ap.add_argument("--cands", type=int, default=32)
@@ -142,8 +144,10 @@ def main():
         return
     rng = np.random.default_rng(0)
     hist = train(model, sch, lambda ep: [train_b[i] for i in rng.permutation(len(train_b))], val_b, args.checkpoint, opt,
-                 args.epochs, seed=0, gpu=args.gpu, task_type=args.task_type, logger=log, save_metric="NDCG@all")
+                 args.epochs, seed=0, gpu=args.gpu, task_type=args.task_type, logger=log, save_metric=args.save_metric)
     best = max(hist, key=lambda h: h["ndcg"][3])
+    if "rank_correlation" in hist[-1]:
+        log.info("last epoch's rank correlation: %s", hist[-1]["rank_correlation"])
     if world > 1:
         import torch.distributed as dist
         dist.barrier()                                    # rank 0 wrote the checkpoint

@@ -733,6 +733,39 @@ int rr_ranking_metrics_f32(const float* score, int64_t score_stride, const float
                            int Q, int max_len, double ratio, double ndcg_cut, int32_t* order, double* stats,
                            rr_stream_t stream);
 
+/* Per-query rank correlation on the device (additive: three new symbols, the ABI revision stays 8): the scale-free
+ * agreement of a whole predicted order with a continuous target.  This library's own definition (the reference has none).
+ * Same list description as rr_ranking_metrics_f32: seg_off[Q+1], max_len <= 8192.
+ *   stats[q*RR_RANK_CORR_NSTATS + 0..7], float64:
+ *     0  Kendall tau-b = (P - D) / sqrt((P + D + X) (P + D + Y))
+ *     1  Spearman rho on tie-averaged ranks
+ *     2  reciprocal rank: 1 / (1 + predicted rank of the target's first maximum); ranks are the stable descending order, ties
+ *        by list position (rr_ranking_metrics_f32's `order`)
+ *     3  top-1 regret: t[first maximum of t] - t[first maximum of s] (>= 0: targets are "higher is better" here)
+ *     4  P = concordant pairs        5  D = discordant pairs
+ *     6  X = pairs tied in score only        7  Y = pairs tied in target only
+ *   (pairs tied in both keys: C (C - 1) / 2 minus the sum of stats 4..7)
+ * A pair (i, j) is ordered in a key only where > or < holds; where neither holds it is tied in that key.  A NaN is therefore
+ * tied with everything: it changes values and never addresses.  The first maximum of a key is the lowest position that no
+ * candidate is greater than.  Spearman: a_i = 2 (1 + #{s_j > s_i}) + #{j != i : neither < nor >} - (C + 1), the centred,
+ * doubled tie-averaged rank - an integer, sum_i a_i = 0 - b_i the same on the targets, and
+ *   rho = sum a_i b_i / sqrt(sum a_i^2 sum b_i^2).
+ * Every count and each of the three Spearman sums is accumulated as an integer (at most C^3 = 5.5e11 at C = 8192: exact in
+ * int64 and in a double; a lane's 32-bit pair counter holds at most 2^20 per candidate pass); only the final quotients and
+ * square roots are float64, IEEE operations of one thread, so the values are run-to-run identical and the same in the
+ * one-wave and four-wave forms.  tau-b and rho are NaN where a key is constant (a zero denominator, as scipy), so for C < 2.  A
+ * list of one has reciprocal rank 1, regret 0 and counts 0; an empty list writes NaN to stats 0..3 and 0 to stats 4..7.
+ * One workgroup per query: one wavefront for max_len <= 64, four above.  LDS 8 * max_len + 320 bytes.  No atomics.
+ *   waves / set_waves   as rr_approx_ndcg_waves / rr_approx_ndcg_set_waves: 0 = by max_len, 1 or 4 = pinned; one
+ *           process-wide word, NOT thread-safe, for the bench tool and the tests; RR_ERR_ARG for anything else.
+ * Status: RR_ERR_ARG for a null pointer, score_stride < 1 or Q < 0; max_len > 8192 -> RR_ERR_UNSUPPORTED, nothing is launched;
+ * Q == 0 launches nothing and returns RR_OK. */
+#define RR_RANK_CORR_NSTATS 8
+int rr_rank_correlation_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
+                            int Q, int max_len, double* stats, rr_stream_t stream);
+int rr_rank_correlation_waves(void);
+int rr_rank_correlation_set_waves(int waves);
+
 /* Per-candidate and per-query statistics of T >= 2 score samples of ragged lists: MC-dropout passes or ensemble members
  * (the reference's deleted run_mc_model / run_ensemble_model, SURVEY.md:35-41; this is a definition of its own, not a port).
  * Same list description as rr_ranking_metrics_f32: seg_off[Q+1], max_len <= 8192.  Sample t of candidate i (0 <= i < M =

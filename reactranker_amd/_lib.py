@@ -279,6 +279,9 @@ _SIGS = {
     "rr_exp_mse_bwd_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, c_f32p, i64, c_stream]),
     "rr_ranking_metrics_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, C.c_double, C.c_double, c_i32p, C.c_void_p,
                                c_stream]),
+    "rr_rank_correlation_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, C.c_void_p, c_stream]),
+    "rr_rank_correlation_waves": (i32, []),
+    "rr_rank_correlation_set_waves": (i32, [i32]),
     "rr_mc_sample_stats_f32": (i32, [c_f32p, i64, i32, c_f32p, c_i32p, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                      c_stream]),
     "rr_analytic_rank_stats_f32": (i32, [c_f32p, i64, i32, c_f32p, c_i32p, i32, i32, C.c_void_p, C.c_void_p, i32, c_f32p, c_f32p,

@@ -19,6 +19,7 @@ from .loss import _prep, _vec
 
 
 NSTATS = 12          # RR_RANKING_NSTATS (include/reactranker_hip.h)
+RANK_CORR_NSTATS = 8  # RR_RANK_CORR_NSTATS
 
 
 def ranking_stats(scores: torch.Tensor, scope, targets, gpu: int = None, ratio: float = 0.25,
@@ -183,6 +184,77 @@ def calculate_mse(model, gpu, batches: Iterable, exchange=None) -> float:
         if exchange is not None and exchange.on:
             v = exchange.sum(v)
     return float(v[0] / v[1].clamp(min=1.0))
+
+
+# ------------------------------------------------------------------------------------------------ rank correlation
+def rank_correlation_stats(scores: torch.Tensor, scope, targets, gpu: int = None) -> torch.Tensor:
+    """rr_rank_correlation_f32 on one batch of scored lists: [Q, 8] float64 on the device = Kendall tau-b, Spearman rho (on
+    tie-averaged ranks), reciprocal rank of the target's first maximum, top-1 regret, then the pair counts P (concordant),
+    D (discordant), X (tied in score only), Y (tied in target only).  tau-b and rho are NaN where a key is constant; an empty
+    list has NaN in the first four columns.  Column 0 of a 2-D output is read in place, by its stride."""
+    if scores.dim() > 1:
+        scores = scores[:, 0]
+    scope, seg, total, max_len, t = _prep(scores, scope, targets, gpu)
+    s = _vec(scores.detach())
+    stats = torch.empty(len(scope), RANK_CORR_NSTATS, dtype=torch.float64, device=s.device)
+    check(lib().rr_rank_correlation_f32(ptr(s), s.stride(0), ptr(t), ptr(seg), len(scope), max_len, ptr(stats), stream()),
+          "rr_rank_correlation_f32")
+    return stats
+
+
+def _nanmean_stats(stats: torch.Tensor, exchange=None):
+    """Per column of the [Q, 8] rank-correlation statistics: (sums [8] of the entries that are not NaN, counts [8] of those
+    entries), float64 numpy arrays - summed over every rank when `exchange` (reactranker_amd.dp.Exchange) spans a process
+    group.  Columns 0..3 are means once divided (sums / counts, NaN where the count is 0); columns 4..7, the pair counts, are
+    used as plain sums."""
+    n = stats.shape[1]
+    ok = ~torch.isnan(stats)
+    v = torch.cat([torch.where(ok, stats, torch.zeros_like(stats)).sum(dim=0), ok.to(torch.float64).sum(dim=0)])
+    if exchange is not None and exchange.on:
+        v = exchange.sum(v)
+    v = v.cpu().numpy()
+    return v[:n].copy(), v[n:].copy()
+
+
+def _rank_correlation_dict(sums: np.ndarray, counts: np.ndarray) -> dict:
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(counts[:4] > 0, sums[:4] / np.maximum(counts[:4], 1.0), np.nan)
+        P, D, X, Y = (float(x) for x in sums[4:8])
+        den = (P + D + X) * (P + D + Y)
+        pooled = (P - D) / np.sqrt(den) if den > 0 else float("nan")
+    return dict(kendall_tau=float(mean[0]), spearman=float(mean[1]), mrr=float(mean[2]), regret=float(mean[3]),
+                n_defined=int(counts[0]), kendall_tau_pooled=float(pooled), pairs=[P, D, X, Y])
+
+
+def rank_correlation_from_scores(scores, scope, targets, gpu: int = None) -> dict:
+    """The rank agreement of one batch of scored lists with their targets: {kendall_tau, spearman, mrr, regret: means over
+    the queries where each is defined (NaN when there is none); n_defined: the number of queries behind kendall_tau;
+    kendall_tau_pooled: tau-b of the pair counts summed over all queries, (P - D) / sqrt((P + D + X) (P + D + Y));
+    pairs: those four sums [P, D, X, Y]}."""
+    return _rank_correlation_dict(*_nanmean_stats(rank_correlation_stats(scores, scope, targets, gpu)))
+
+
+def rank_correlation(model, gpu, batches: Iterable, exchange=None) -> dict:
+    """rank_correlation_from_scores over an iterable of (r_batch, p_batch, scope, targets, add_features) batches of whole
+    queries scored by `model`; switches the model to eval mode and restores the caller's mode, as ranking_metrics does.
+    exchange: a reactranker_amd.dp.Exchange when every rank evaluates its own shard of the queries (an empty shard is
+    skipped; the sums and counts are all-reduced).  The means are NaN when no query is defined anywhere."""
+    was_training = model.training
+    model.eval()
+    rows = []
+    with torch.no_grad():
+        for r_batch, p_batch, scope, targets, add_features in batches:
+            if len(scope) == 0:
+                continue
+            out = model(r_batch, p_batch, gpu=gpu, add_features=add_features)
+            rows.append(rank_correlation_stats(out, scope, targets, gpu))
+    model.train(was_training)
+    if rows:
+        stats = torch.cat(rows, 0)
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
+        stats = torch.zeros(0, RANK_CORR_NSTATS, dtype=torch.float64, device=dev)
+    return _rank_correlation_dict(*_nanmean_stats(stats, exchange))
 
 
 def ndcg_at_k(scores, scope, relevance, gpu: int = None) -> np.ndarray:

@@ -20,7 +20,7 @@ from typing import Callable, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .base_model import build_model
-from .eval import calculate_ndcg, evaluate_top_scores
+from .eval import calculate_ndcg, evaluate_top_scores, rank_correlation
 from .run_train_pairwise import run_train
 from .train_listwise import train
 from .train_utils import build_lr_scheduler, build_optimizer
@@ -58,7 +58,7 @@ class Config:
 
 def test(model, test_batches: Sequence, path_checkpoints: str, gpu: int, logger=None, target_name: Optional[str] = "ea",
          cal_ngcd: bool = False, is_order: bool = True, return_order: bool = True, task_type: Optional[str] = None,
-         exchange=None):
+         exchange=None, rank_corr: bool = False):
     """Reference train/test_listwise.py:10-86 (and test_ranknet.py:30-80, which reports the same triple): load the
     fold's checkpoint, flip the sign of raw targets unless 'lgk' (:30-35), evaluate with `evaluate_top_scores` at
     ratio 0.25 (:51-54) -> (average_score [top-1], average_pred_in_targ [predicted top-25 % inside the target top-25 %],
@@ -66,7 +66,9 @@ def test(model, test_batches: Sequence, path_checkpoints: str, gpu: int, logger=
     NDCG_cut = 0.25 on the de-standardised outputs (:58-63), logged, and - with return_order - its per-candidate
     listing appended to the return value (:83-84; the SMILES column stays with the DataFrame side: None).
     task_type 'MC_dropout' keeps the model in train mode (:42-45).  exchange: a reactranker_amd.dp.Exchange when every
-    rank evaluates its own shard of the test queries (the means are then over all ranks' queries)."""
+    rank evaluates its own shard of the test queries (the means are then over all ranks' queries).
+    rank_corr (not in the reference): also evaluate eval.rank_correlation - mean per-query Kendall tau-b, Spearman rho,
+    reciprocal rank and regret - log its dict and append it as the LAST element of the return value."""
     scaler = load_checkpoint(path_checkpoints, model, map_location="cpu")
     model = model.cuda(gpu)
     model.train() if task_type == "MC_dropout" else model.eval()
@@ -83,14 +85,19 @@ def test(model, test_batches: Sequence, path_checkpoints: str, gpu: int, logger=
         if cal_ngcd:
             ndcg, kl_div, order, smiles_and_index = calculate_ndcg(model, gpu, batches, NDCG_cut=0.25,
                                                                    is_order=is_order, means=means, stds=stds, exchange=exchange)
+        if rank_corr:
+            corr = rank_correlation(model, gpu, batches, exchange=exchange)
     if logger is not None:
         if cal_ngcd:
             logger.info("test: NDCG0.25 {}, KL divergence {}".format(ndcg, kl_div))
         logger.info("test: average score {:.4f}, pred top25% in targ top25% {:.4f}, targ top1 in pred top25% {:.4f}"
                     .format(top1, recall25, top25))
+        if rank_corr:
+            logger.info("test: rank correlation {}".format(corr))
+    res = (float(top1), float(recall25), float(top25))
     if cal_ngcd and return_order:
-        return float(top1), float(recall25), float(top25), order, smiles_and_index
-    return float(top1), float(recall25), float(top25)
+        res += (order, smiles_and_index)
+    return res + (corr,) if rank_corr else res
 
 
 def run(cfg: Config, folds: Callable[[int], Tuple[Sequence, Sequence, Sequence]], logger=None, group=None) -> List[List[float]]:

@@ -11,9 +11,9 @@ from typing import List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .eval import evaluate_top_scores, pairwise_baseline_acc
+from .eval import evaluate_top_scores, pairwise_baseline_acc, rank_correlation
 from .pairs import pair_windows
-from .train_listwise import standardize_batches
+from .train_listwise import RANK_CORR_METRICS, standardize_batches
 from .train_pairwise import (baseline_pairwise_training_loop, beta_dis_train_loop, beta_evi_train_loop,
                              factorized_training_loop)
 from .utils import save_checkpoint
@@ -49,6 +49,8 @@ def run_train(model: torch.nn.Module, scheduler, train_batches: Sequence, val_ba
     Otherwise returns the per-epoch history [{epoch, train_loss, top1, pred_top25_in_targ_top25, top1_in_pred_top25 (the TARGET's
     top-1 inside the predicted top-25 %), checkpoint, checkpoint_all (which of the three 'all' metrics improved)}].
     epoch_hook(epoch, model, record): optional observer called after every epoch's validation (not in the reference).
+    save_metric 'kendall_tau' / 'spearman' / 'mrr' (not in the reference) select on that mean of eval.rank_correlation, as in
+    reactranker_amd.train_listwise.train: the record then also holds its dict under `rank_correlation`.
     group: data-parallel training under torch.distributed exactly as in reactranker_amd.train_listwise.train - every rank
     passes its shard of every window (whole queries, each batch carrying the window's `global` counts) and of the
     validation queries; the loss is normalised by the WINDOW's ordered pairs, gradients are summed over the ranks,
@@ -143,7 +145,7 @@ def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, o
         train_batches, val_batches, mean, std = standardize_batches(list(train_batches), list(val_batches), tn, True, None, ex)
     ex.broadcast_model(model)
     ex.check_same_steps(len(train_batches), next(model.parameters()).device)
-    score_old = [0.0, 0.0, 0.0] if save_metric == "all" else 0.0
+    score_old = [0.0, 0.0, 0.0] if save_metric == "all" else (float("-inf") if save_metric in RANK_CORR_METRICS else 0.0)
     say = logger.info if (logger is not None and ex.is_writer) else (lambda *_: None)
     history = []
     for epoch in range(epochs):
@@ -185,11 +187,19 @@ def _run_train(model, scheduler, train_batches, val_batches, path_checkpoints, o
                 if v >= score_old[i]:
                     score_old[i] = v
                     keep(path_checkpoints[i] if path_checkpoints is not None else None, i)
+        elif save_metric in RANK_CORR_METRICS:
+            corr = rank_correlation(model, gpu, [(b["r"], b["p"], b["scope"], b["targets"], b.get("add")) for b in val_batches],
+                                    exchange=ex)
+            if corr[save_metric] >= score_old:                # False for a NaN: it never replaces the best and never saves
+                score_old = corr[save_metric]
+                keep(path_checkpoints)
         else:
             raise Exception("Unknown save metric")
         history.append(dict(epoch=epoch + 1, train_loss=float(epoch_loss), top1=float(top1),
                             pred_top25_in_targ_top25=float(recall25), top1_in_pred_top25=float(top25), checkpoint=saved,
                             checkpoint_all=list(saved_which)))
+        if save_metric in RANK_CORR_METRICS:
+            history[-1]["rank_correlation"] = corr
         if epoch_hook is not None:
             epoch_hook(epoch, model, history[-1])
         say("Epoch [{}/{}],train_loss,{:.4f}, average_score_top1,{:.4f}, average_pred_in_targ_top25%,{:.4f}"

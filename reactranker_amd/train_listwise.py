@@ -15,10 +15,11 @@ import numpy as np
 import torch
 
 from . import loss as RL
-from .eval import calculate_mse, ranking_metrics
+from .eval import calculate_mse, rank_correlation, ranking_metrics
 from .utils import save_checkpoint
 
 NDCG_METRICS = ["NDCG@1", "NDCG@2", "NDCG@25%", "NDCG@all"]
+RANK_CORR_METRICS = ("kendall_tau", "spearman", "mrr")     # not in the reference: eval.rank_correlation's scale-free means
 SUPPORTED_TASKS = ("mle", "listnet", "evidential_ranking", "gauss_regression", "mle_gaussian", "listnet_gauss",
                    "mle_regression", "listnet_regression", "regression",
                    "mledis_gaussian", "listnetdis_gauss", "listnetdis_lognorm", "listnet_uq", "evidential", "mle_evidential",
@@ -179,6 +180,10 @@ def train(model: torch.nn.Module, scheduler, train_batches: Union[Sequence, Call
     optimizer.step / scheduler.step (train_listwise.py:287-290), validation with ranking_metrics after every epoch,
     checkpoint whenever the selected metric does not get worse (:310-350).  `train_batches` is a sequence, or a
     callable epoch -> iterable (the reference reshuffles with seed=epoch, :178).  Returns the per-epoch history.
+    save_metric 'kendall_tau' / 'spearman' / 'mrr' (RANK_CORR_METRICS; not in the reference) select on the mean per-query
+    Kendall tau-b, Spearman rho or reciprocal rank of eval.rank_correlation: one more validation pass per epoch, whose dict
+    the history record then holds under `rank_correlation`; the best starts at -inf (tau and rho lie in [-1, 1]) and a NaN
+    epoch (no query with a defined value) never replaces it and never saves.
     epoch_hook(epoch, model, record): optional observer called after every epoch's validation (not in the reference; the
     trajectory tests read the validation scores through it).
 
@@ -221,6 +226,8 @@ def _train(model, scheduler, train_batches, val_batches, path_checkpoints, optim
     if getattr(model, "dropout_seed", None) is not None:
         model.dropout_seed = None
     score_old = [0.0, 0.0, 0.0] if save_metric == "all" else (float("inf") if save_metric == "mse" else 0.0)   # :54-59
+    if save_metric in RANK_CORR_METRICS:
+        score_old = float("-inf")
     history = []
     say = logger.info if (logger is not None and ex.is_writer) else (lambda *_: None)
     dev = next(model.parameters()).device
@@ -290,6 +297,12 @@ def _train(model, scheduler, train_batches, val_batches, path_checkpoints, optim
             if mse_val <= score_old:
                 score_old = mse_val
                 keep(path_checkpoints)
+        elif save_metric in RANK_CORR_METRICS:
+            corr = rank_correlation(model, gpu, [(b["r"], b["p"], b["scope"], b["targets"], b.get("add")) for b in val_batches],
+                                    exchange=ex)
+            if corr[save_metric] >= score_old:                  # False for a NaN
+                score_old = corr[save_metric]
+                keep(path_checkpoints)
         else:
             raise Exception("Unknown save metric")
         saved = saved and path_checkpoints is not None
@@ -298,6 +311,8 @@ def _train(model, scheduler, train_batches, val_batches, path_checkpoints, optim
                    pred_top25_in_targ_top25=float(recall25), ndcg=[float(x) for x in ndcg], checkpoint=saved)
         if save_metric == "mse":
             rec["mse"] = float(mse_val)
+        if save_metric in RANK_CORR_METRICS:
+            rec["rank_correlation"] = corr
         history.append(rec)
         if epoch_hook is not None:
             epoch_hook(epoch, model, rec)
