@@ -15,6 +15,7 @@
 // forward chain is linear_rowdot_kernel's 16-lane dot product with its shuffle tree.  tests/test_gpu_ffn.py holds it to
 // torch.equal against the per-layer path.
 #include "rr_common.h"
+#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -25,6 +26,10 @@ constexpr int FPF = 3;                          // k-tiles of weight fragments i
 __host__ __device__ constexpr int f_r16(int k) { return (k + 15) & ~15; }
 // LDS row pitch (floats): == 4 (mod 32), so the 8 lanes of a ds_read_b128 phase (8 rows, same k) hit 8 different 4-bank groups
 __host__ __device__ constexpr int f_pitch(int kmax) { return ((kmax + 31) & ~31) + 4; }
+constexpr int FFN_KMAX = 1024;                  // the widest stage input (or 16-padded output) the chain takes
+constexpr int FFN_TMAX = 40;                    // ... and the most column tiles of a stage: 8 waves x 5
+// dynamic LDS of a launch: two activation buffers of FROWS rows (FFN_KMAX: 131,584 bytes of the CU's 160 KiB)
+constexpr size_t f_lds_bytes(int kmax) { return static_cast<size_t>(2) * FROWS * f_pitch(f_r16(kmax)) * sizeof(float); }
 
 typedef const __attribute__((address_space(1))) f32x4* f_gptr4;
 __device__ __forceinline__ f32x4 f_ldg4(const float* p) { return *(f_gptr4)(p); }
@@ -226,14 +231,18 @@ __global__ void __launch_bounds__(64 * NW) ffn_chain_kernel(const FfnParams P) {
 
 template <int NW, int NTW>
 int launch_chain(const FfnParams& P, size_t lds, hipStream_t s) {
-  static bool configured[64] = {false};
+  // > 64 KiB of LDS has to be asked for once per instantiation AND per device.  Asked for once, at the LARGEST size the host
+  // check admits (FFN_KMAX), not at the size of the launch that happens to come first: a process that runs H = 512 and then
+  // H = 600 would otherwise launch the second chain above the size it opted in to.  Atomics because two host threads may
+  // launch the same instantiation at once (setting it twice is harmless).
+  static std::atomic<uint64_t> configured{0};          // bit d: done on device d (devices >= 64 set it every launch)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return RR_ERR_LAUNCH;
-  if (lds > 65536 && (dev < 0 || dev >= 64 || !configured[dev])) {
+  if (lds > 65536 && (dev < 0 || dev >= 64 || !((configured.load(std::memory_order_acquire) >> dev) & 1u))) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_chain_kernel<NW, NTW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds)) != hipSuccess)
+                            static_cast<int>(f_lds_bytes(FFN_KMAX))) != hipSuccess)
       return RR_ERR_LAUNCH;
-    if (dev >= 0 && dev < 64) configured[dev] = true;
+    if (dev >= 0 && dev < 64) configured.fetch_or(uint64_t(1) << dev, std::memory_order_release);
   }
   const unsigned grid = static_cast<unsigned>((P.a.M + FROWS - 1) / FROWS);
   ffn_chain_kernel<NW, NTW><<<grid, 64 * NW, lds, s>>>(P);
@@ -277,14 +286,14 @@ int rr_ffn_chain_f32(const rr_ffn_chain_args* args, rr_stream_t stream) {
     if (T > tmax) tmax = T;
     if (f_r16(S.n_out) > kmax) kmax = f_r16(S.n_out);
   }
-  if (kmax > 1024 || tmax > 40) return RR_ERR_UNSUPPORTED;
+  if (kmax > FFN_KMAX || tmax > FFN_TMAX) return RR_ERR_UNSUPPORTED;
   FfnParams P;
   P.a = a;
   P.pitch = f_pitch(f_r16(kmax));
   P.x_vec = f_vec_ok(a.x, a.ldx) ? 1 : 0;
   P.drop_thr = rr_drop_threshold(a.drop_p);
   P.keep_scale = 1.0f / (1.0f - a.drop_p);
-  const size_t lds = static_cast<size_t>(2) * FROWS * P.pitch * sizeof(float);
+  const size_t lds = f_lds_bytes(kmax);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (tmax <= 8) return launch_chain<8, 1>(P, lds, s);
   if (tmax <= 24) return launch_chain<8, 3>(P, lds, s);

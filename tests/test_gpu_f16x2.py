@@ -222,7 +222,8 @@ def test_gather_magnitude_outputs():
     assert float(slot2.max()) == float(out2.abs().max())
 
 
-# every plan shape of tests/test_gpu_plan.py (reactant modes, head layouts, depths 1..16, H = 32 .. 600) through the step plans
+# every plan shape of tests/test_gpu_plan.py (reactant modes, head layouts, depths 1..16, H = 32 .. 600, and every rung of
+# tests/hidden_sizes.py that a plan takes: H = 4 .. 1024, above 608 the same f32-layout GEMMs in both) through the step plans
 # in BOTH arithmetics: the two-term form must agree with the three-term form (which test_gpu_plan.py holds bit-identical to
 # the per-op mirror and the other modules hold against the oracle) within the parity tolerances, and be run-to-run identical
 from tests.test_gpu_plan import CASES as PLAN_CASES  # noqa: E402

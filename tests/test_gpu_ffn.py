@@ -75,6 +75,30 @@ def test_forward_chain_equals_the_layers_issued_one_by_one(M, widths, bias, p):
     assert torch.equal(hs[-1], ref_raw), float((hs[-1] - ref_raw).abs().max())
 
 
+def _chain_backward(d, layers, hs, p, dx_cols):
+    """the input-gradient chain of `layers` on d = d(raw output): (status, every stage's dx); hs: the forward's saved activations"""
+    M, nl = d.shape[0], len(layers)
+    ks = 1.0 / (1.0 - p)
+    a = _lib.FfnChainArgs()
+    a.M, a.n_stages, a.x, a.ldx, a.drop_p, a.mask_scale = M, nl, ptr(d), d.stride(0), 0.0, ks
+    outs, keep = [], []
+    for j in range(nl):
+        li = nl - 1 - j
+        L = layers[li]
+        nin = L.w.shape[1] if (li > 0 or dx_cols is None) else dx_cols
+        wt = L.pk_t(0, nin)
+        keep.append(wt)
+        g = a.stage[j]
+        g.w, g.ldw, g.n_out, g.n_in = ptr(wt), wt.stride(0), nin, L.w.shape[0]
+        o = torch.full((M, (nin + 3) // 4 * 4), float("nan"), device=dev)
+        g.out, g.ld_out = ptr(o), o.stride(0)
+        if li > 0:
+            g.post_mask, g.ld_mask = ptr(hs[li]), hs[li].stride(0)
+        outs.append(o)
+    st = lib().rr_ffn_chain_f32(C.byref(a), stream())
+    return st, outs
+
+
 @pytest.mark.parametrize("M,widths,bias,p", [
     (4096, [301, 300, 300, 1], True, 0.1),
     (4096, [601, 600, 600, 2], True, 0.1),
@@ -98,24 +122,8 @@ def test_backward_chain_equals_the_layers_issued_one_by_one(M, widths, bias, p):
         ref_dx, _ = Fn.ffn_backward(layers, p, 0, saved, d, need_dx=True, dx_cols=dx_cols)
     finally:
         Fn.SideStream.enabled = old
-    ks = 1.0 / (1.0 - p)
-    a = _lib.FfnChainArgs()
-    a.M, a.n_stages, a.x, a.ldx, a.drop_p, a.mask_scale = M, nl, ptr(d), d.stride(0), 0.0, ks
-    outs, keep = [], []
-    for j in range(nl):
-        li = nl - 1 - j
-        L = layers[li]
-        nin = L.w.shape[1] if (li > 0 or dx_cols is None) else dx_cols
-        wt = L.pk_t(0, nin)
-        keep.append(wt)
-        g = a.stage[j]
-        g.w, g.ldw, g.n_out, g.n_in = ptr(wt), wt.stride(0), nin, L.w.shape[0]
-        o = torch.full((M, (nin + 3) // 4 * 4), float("nan"), device=dev)
-        g.out, g.ld_out = ptr(o), o.stride(0)
-        if li > 0:
-            g.post_mask, g.ld_mask = ptr(hs[li]), hs[li].stride(0)
-        outs.append(o)
-    check(lib().rr_ffn_chain_f32(C.byref(a), stream()), "rr_ffn_chain_f32")
+    st, outs = _chain_backward(d, layers, hs, p, dx_cols)
+    check(st, "rr_ffn_chain_f32")
     n0 = ref_dx.shape[1]
     assert torch.equal(outs[-1][:, :n0], ref_dx), float((outs[-1][:, :n0] - ref_dx).abs().max())
 

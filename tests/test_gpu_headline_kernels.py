@@ -151,7 +151,8 @@ def train_step_vs_fp64_oracle(cfg, qb, K, loss_kind, p, seed, log, rows_above=No
          same gates - with no outlier allowance;
       3. scores and loss within 1e-5 (1 + |ref|), or 3 x the fp32 oracle's distance where that is larger.
     The measured numbers (flips per layer, errors with natural and with dictated gates) go to the parity log.
-    qb: the query batch; K: the pad width both sides are packed with (None: each side's own); seed: the weights'."""
+    qb: the query batch (add_features None with add_features_dim 0); K: the pad width both sides are packed with (None: each
+    side's own); seed: the weights'.  Returns what it measured: flipped gates, score / loss errors, the worst gradient."""
     H, d, dd = cfg["hidden_size"], cfg["mpnn_depth"], cfg["mpnn_diff_depth"]
     shapes = O.model_shapes(H, d, dd, cfg["ffn_depth"], cfg["task_num"], cfg["add_features_dim"], cfg["use_bias"])
     w = synth.seeded_weights(shapes, seed)
@@ -182,8 +183,8 @@ def train_step_vs_fp64_oracle(cfg, qb, K, loss_kind, p, seed, log, rows_above=No
             g["f_atoms"], g["f_bonds"] = g["f_atoms"].to(dt), g["f_bonds"].to(dt)
             return g
         mk = {k: v.to(dt) for k, v in masks.items()}
-        ref = O.reaction_forward(P, mc, gt(qb.r_specs), gt(qb.p_specs), torch.tensor(qb.add_features).to(dt), masks=mk,
-                                 gates=gates, trace=trace)
+        add = None if qb.add_features is None else torch.tensor(qb.add_features).to(dt)
+        ref = O.reaction_forward(P, mc, gt(qb.r_specs), gt(qb.p_specs), add, masks=mk, gates=gates, trace=trace)
         t = targets.to(dt)
         l = O.listmle_loss(ref, scope, t) if loss_kind == "mle" else O.evidential_ranking_loss(ref, scope, t)
         names = [k for k in P if P[k].requires_grad]
@@ -223,6 +224,7 @@ def train_step_vs_fp64_oracle(cfg, qb, K, loss_kind, p, seed, log, rows_above=No
     # ---- 2. gradients: against the fp64 oracle evaluated with the gates the HIP step took
     l.sum().backward()
     got = dict(model.named_parameters())
+    worst_g, worst_name = 0.0, ""
     fg = {k: v.double() for k, v in hip_gates.items()}
     _, _, g64h = run_oracle(torch.float64, gates=fg)
     _, _, g32h = run_oracle(torch.float32, gates={k: v.float() for k, v in hip_gates.items()})
@@ -241,10 +243,13 @@ def train_step_vs_fp64_oracle(cfg, qb, K, loss_kind, p, seed, log, rows_above=No
             log(f"grad {k}: max|err| / max|g| = {err / scale:.2e} with the HIP gates dictated to the fp64 oracle "
                 f"({err_nat / scale:.2e} against its own gates; fp32 oracle under the same gates: {noise / scale:.2e})")
         assert err <= bound, f"grad {k}: |err vs fp64 (same gates)| {err:.3e} > {bound:.3e} (fp32 oracle noise {noise:.3e}, scale {scale:.3e})"
+        if scale >= 1e-12 and err / scale > worst_g:
+            worst_g, worst_name = err / scale, k
     # the step really went through the plan with the shared reactant prefix and dropout acted
     model.eval()
     out_eval = model(rb, pb, gpu=0, add_features=qb.add_features)
     assert float((out_eval.detach() - out.detach()).abs().max()) > 1e-4
+    return dict(flips=n_flip, gates=n_gates, scores=e_s, scores32=e_s32, loss=e_l, loss32=e_l32, grad=worst_g, grad_at=worst_name)
 
 
 def test_train_mode_plan_path_above_8192_rows_against_fp64_oracle_h300(parity_log):

@@ -10,6 +10,7 @@ from reactranker_amd import featurization, synth
 from reactranker_amd import functions as Fn
 from reactranker_amd import loss as RL
 from oracle import ref_cpu as O
+from tests.hidden_sizes import RUNGS_MULT4
 from tests.test_gpu_model import make_model
 
 pytestmark = pytest.mark.gpu
@@ -54,6 +55,10 @@ CASES = [
     (32, 11, 12, 2, True, 1, "no_softplus", None, 1, 0.1, True),        # depth >= 10: more than 8 per-iteration dZ buffers
     (32, 16, 16, 2, True, 1, "no_softplus", None, 0, 0.0, True),        # the deepest model a plan takes (MAXD)
 ]
+# every hidden size a dispatcher branches on that a plan takes (tests/hidden_sizes.py says what each rung crosses): split
+# geometries, the f32 layout above 608, every FFN-chain instantiation and tile count, the chain refused inside a plan (644, 1024)
+CASES += [(H, 2, 2, 3, True, 1, "with_softplus", None, 1, 0.1, True) for H in RUNGS_MULT4]
+CASES += [(H, 2, 2, 3, True, 1, "with_softplus", None, 1, 0.0, False) for H in (304, 612)]
 
 
 @pytest.mark.parametrize("H,d,dd,fd,bias,tn,last,tt,F,p,train", CASES)
