@@ -20,6 +20,11 @@ of a step and are refused there (one process trains them).
 A task type whose head predicts a distribution per candidate (evidential_ranking, mledis_gaussian, listnetdis_gauss, the NIG
 ones) ends with the validation set's uncertainty from one forward per batch (uncertainty.evaluate_uncertainty,
 method='distribution').
+
+--evaluate-calibration (listwise task types, one process) holds out the first half of every validation batch's queries as the
+calibration set and reports on the other half (uncertainty.evaluate_calibration): the fitted sigma scale with the pointwise
+calibration before and after it, the top-1 calibration of p_top1, and the conformal top-1 sets at --alpha.  A distributional
+head is read with method='distribution', any other with MC dropout.
 """
 import argparse
 import logging
@@ -57,6 +62,17 @@ def make_batches(seed, n_queries, cands, per_batch, rank=0, world=1):
                         p=featurization.BatchMolGraph(qb.p_specs, K=4) if some else None,
                         scope=qb.scope, targets=torch.tensor(qb.targets), add=qb.add_features,
                         mols_r=qb.r_specs, mols_p=qb.p_specs, **extra))
+    return out
+
+
+def halves(b):
+    """the first and the second half of a batch's queries as two batches of the same form"""
+    q = len(b["scope"]) // 2
+    m = int(sum(b["scope"][:q]))
+    out = []
+    for qs, ms in ((slice(0, q), slice(0, m)), (slice(q, None), slice(m, None))):
+        out.append(dict(r=featurization.BatchMolGraph(b["mols_r"][ms], K=4), p=featurization.BatchMolGraph(b["mols_p"][ms], K=4),
+                        scope=list(b["scope"][qs]), targets=b["targets"][ms], add=b["add"][ms]))
     return out
 
 
@@ -100,6 +116,10 @@ def main():
     ap.add_argument("--batch-queries", type=int, default=32)
     ap.add_argument("--hidden", type=int, default=300)
     ap.add_argument("--gpu", type=int, default=0)
+    ap.add_argument("--evaluate-calibration", action="store_true", help="listwise task types: calibrate sigma and the top-1 sets on half "
+                    "of the validation queries and report on the other half")
+    ap.add_argument("--alpha", type=float, default=0.1, help="with --evaluate-calibration: the top-1 sets miss the best candidate with "
+                    "probability at most alpha")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -163,6 +183,21 @@ def main():
                  uncertainty.MOMENT_KIND_OF_HEAD[model.ffn.head()],
                  ", ".join(f"{k} {v:.3f}" for k, v in zip(uncertainty.QSTAT_NAMES, uq["qstats"])), uq["mass_worst"],
                  uq["calibration"]["spearman"])
+    if world == 1 and args.evaluate_calibration:
+        method = "distribution" if model.ffn.head() in uncertainty.MOMENT_KIND_OF_HEAD else "MC_dropout"
+        cal_b, test_b = zip(*[halves(b) for b in val_b if len(b["scope"]) >= 2])
+        res = uncertainty.evaluate_calibration(model, cal_b, test_b, args.checkpoint, args.gpu, method=method, alpha=args.alpha,
+                                               target_name=None)
+        for when in ("before", "after"):
+            pc = res["probabilistic"][when]
+            log.info("calibration (%s), sigma scale %.3f: nll %.4f crps %.4f mean z^2 %.3f sharpness %.4f rmse %.4f "
+                     "miscalibration area %.4f", method, pc["sigma_scale"], pc["nll"], pc["crps"], pc["z2_mean"], pc["sharpness"],
+                     pc["rmse"], pc["miscalibration_area"])
+        t1 = res["top1"]
+        log.info("top-1 of p_top1 on %d test queries: accuracy %.3f, confidence %.3f, ECE %.3f, Brier %.3f", t1["n"], t1["accuracy"],
+                 t1["confidence"], t1["ece"], t1["brier"])
+        log.info("conformal top-1 sets at alpha %.2f: tau %.4f, coverage %.3f, mean set size %.2f of %.2f candidates", args.alpha,
+                 res["tau"], res["coverage"], res["mean_set_size"], float(np.mean(res["scope"])))
     if world > 1:
         dist.destroy_process_group()
 

@@ -843,6 +843,62 @@ int rr_uq_calibration_f64(const float* err, const float* unc, const int64_t* ord
                           const double* fractions, int n_frac, void* workspace, size_t workspace_bytes, double* out,
                           rr_stream_t stream);
 
+/* Does sigma have the right SIZE?  Pointwise calibration of a predicted (mean, std) against targets (additive: four new
+ * symbols with rr_top1_sets_f32 below, the ABI revision stays 8).  This library's own definition (the reference has none).
+ * mean[n], std_dev[n], target[n] (f32, device, n >= 1), sigma_scale > 0, 1 <= n_bins <= RR_GAUSS_CAL_MAX_BINS.  A row is
+ * VALID when its mean and target are finite and its std_dev is finite and > 0; an invalid row is counted and adds nothing
+ * else.  For a valid row, all in f64 (IEEE operations and the device's erfc, exp and log; the build has -ffp-contract=off):
+ *   sigma = sigma_scale * std_dev      z = (target - mean) / sigma      pit = 0.5 * erfc(-z / sqrt 2)
+ *   phi = exp(-z^2 / 2) / sqrt(2 pi)   crps = sigma * (z * (2 * pit - 1) + 2 * phi - 1 / sqrt pi)   (Gneiting & Raftery 2007)
+ *   bin = min(n_bins - 1, (int)floor(pit * n_bins))
+ * out[RR_GAUSS_CAL_NSUMS + n_bins] (f64, device), RAW sums over the valid rows - the caller forms the means:
+ *   0  n_valid         1  n_invalid        2  sum z        3  sum z^2
+ *   4  sum ln sigma    5  sum sigma^2      6  sum (target - mean)^2      7  sum crps
+ *   8 ...  the n_bins counts of the PIT histogram, exact integers stored in doubles
+ * Two launches, as rr_uq_calibration_f64: per-block partials of RR_UQ_CAL_BLOCK rows into `workspace` (at least
+ * ceil(n / RR_UQ_CAL_BLOCK) * (RR_GAUSS_CAL_NSUMS + n_bins) doubles; RR_ERR_WORKSPACE otherwise) - a block's sums in a fixed
+ * order, its histogram by integer LDS adds - then one workgroup adds the blocks' partials in block order.  No floating-point
+ * atomics: run-to-run identical bits.  Status: RR_ERR_ARG for a null pointer, n < 1, n_bins outside [1, 64] or a sigma_scale
+ * that is not positive and finite. */
+#define RR_GAUSS_CAL_NSUMS 8
+#define RR_GAUSS_CAL_MAX_BINS 64
+int rr_gauss_calibration_f64(const float* mean, const float* std_dev, const float* target, int64_t n, double sigma_scale,
+                             int n_bins, void* workspace, size_t workspace_bytes, double* out, rr_stream_t stream);
+
+/* Per-list calibration and prediction sets of a top-1 probability.  Same list description as rr_rank_correlation_f32:
+ * seg_off[Q+1], max_len <= 8192.  p[M] (f32, element i at p[i * p_stride]: p_top1, non-negative, summing to about 1 per
+ * list), targets[M], tau >= 0 (+inf allowed).  For candidate i of a list of C:
+ *   AHEAD of i   the candidates j with p_j > p_i, or with p_j == p_i and j < i: the stable descending order, ties by list
+ *                position (the rule of rr_ranking_metrics_f32's `order`)
+ *   rank[M]      int32: 1 + the number of candidates ahead
+ *   before[M]    f64: the sum of p_j over the candidates ahead of i, taken in ASCENDING j - an ordered chain of IEEE
+ *                additions, so a definition and not an approximation
+ *   in_set[M]    uint8: before_i <= tau
+ * Every term is non-negative and rounding is monotone, so `before` is non-decreasing in rank: the set is a prefix of the
+ * predicted order, and it holds the candidate of rank 1 (before = 0) for every tau >= 0.
+ *   stats[q*RR_TOP1_NSTATS + 0..8], float64; the true top is the first maximum of the targets, the predicted top the
+ *   candidate of rank 1:
+ *     0  hit: 1 where the predicted top is the true top, else 0
+ *     1  confidence: p of the predicted top           2  p of the true top
+ *     3  rank of the true top                          4  Brier score sum_i (p_i - [i is the true top])^2, ascending i
+ *     5  conformity score E = before of the true top: the probability mass ranked STRICTLY ahead of it
+ *     6  set size #{i : in_set_i}                      7  covered: 1 where the true top is in the set, else 0
+ *     8  mass sum_i p_i, ascending i
+ * covered <=> E <= tau holds exactly: both come from the one stored `before`.  An empty list writes NaN to stats 0..5 and 0
+ * to stats 6..8, and so does a list longer than max_len (nothing of it is staged).  A NaN in p is ahead of nothing and has nothing ahead; it and a negative p change values and never an
+ * address (a caller checks its p; with several candidates of rank 1 the predicted top is the lowest position).
+ * One workgroup per query: one wavefront for max_len <= 64, four above; thread = candidate, strided, and a candidate's chain
+ * lives in one thread, so both forms write the same bits.  LDS 4 * max_len + 96 bytes (p only).  No atomics.
+ *   waves / set_waves   as rr_rank_correlation_waves / rr_rank_correlation_set_waves: 0 = by max_len, 1 or 4 = pinned; one
+ *           process-wide word, NOT thread-safe, for the bench tool and the tests; RR_ERR_ARG for anything else.
+ * Status: RR_ERR_ARG for a null pointer, p_stride < 1, Q < 0, or a tau that is negative or a NaN; max_len > 8192 ->
+ * RR_ERR_UNSUPPORTED, nothing is launched; Q == 0 launches nothing and returns RR_OK. */
+#define RR_TOP1_NSTATS 9
+int rr_top1_sets_f32(const float* p, int64_t p_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
+                     double tau, int32_t* rank, double* before, uint8_t* in_set, double* stats, rr_stream_t stream);
+int rr_top1_sets_waves(void);
+int rr_top1_sets_set_waves(int waves);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

@@ -288,6 +288,12 @@ _SIGS = {
                                          c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
     "rr_uq_calibration_f64": (i32, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.c_void_p, C.c_size_t,
                                     C.c_void_p, c_stream]),
+    "rr_gauss_calibration_f64": (i32, [c_f32p, c_f32p, c_f32p, i64, C.c_double, i32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       c_stream]),
+    "rr_top1_sets_f32": (i32, [c_f32p, i64, c_f32p, c_i32p, i32, i32, C.c_double, c_i32p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               c_stream]),
+    "rr_top1_sets_waves": (i32, []),
+    "rr_top1_sets_set_waves": (i32, [i32]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),

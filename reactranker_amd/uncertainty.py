@@ -16,6 +16,11 @@ A model whose head emits a distribution per candidate (heads 3, 4, 6: evidential
 NIG ones) needs no samples: rr_analytic_rank_stats_f32 turns one eval-mode forward into the same statistics analytically
 under independent Gaussians (analytic_stats / distribution_predict / method='distribution').
 
+Whether the uncertainty has the right SIZE, and whether p_top1 means what it says, is the calibration part:
+rr_gauss_calibration_f64 behind probabilistic_calibration / fit_sigma_scale (NLL, CRPS, PIT histogram, a fitted sigma scale),
+rr_top1_sets_f32 behind top1_sets (per-list rank, probability mass ahead, prediction set and top-1 statistics), and
+conformal_threshold / top1_calibration / evaluate_calibration on top of them.
+
 Batches have the tuple form of eval.evaluate_top_scores: (r_batch, p_batch, scope, targets, add_features).
 """
 from __future__ import annotations
@@ -390,3 +395,192 @@ def evaluate_uncertainty(model, test_batches: Sequence[dict], path_checkpoints, 
                 qstats=qstats.mean(dim=0).cpu().numpy(),
                 calibration=uncertainty_calibration(cat["mean"], targets, cat["std"], fractions),
                 targets=targets, scope=[int(c) for b in kept for c in b[2]], **cat)
+
+
+# ------------------------------------------------------------------------------------------------ calibration
+GAUSS_CAL_NSUMS = 8    # RR_GAUSS_CAL_NSUMS
+GAUSS_CAL_MAX_BINS = 64
+TOP1_NSTATS = 9        # RR_TOP1_NSTATS
+TOP1_STAT_NAMES = ("hit", "confidence", "p_of_true_top", "rank_of_true_top", "brier", "conformity_score", "set_size", "covered",
+                   "mass")
+
+
+def _gauss_sums(pred, target, std, n_bins: int, sigma_scale: float) -> np.ndarray:
+    """One rr_gauss_calibration_f64 call: the 8 raw sums and the n_bins PIT counts, float64 on the host."""
+    nb_ = int(n_bins)
+    if nb_ != n_bins or not (1 <= nb_ <= GAUSS_CAL_MAX_BINS):
+        raise ValueError(f"n_bins must be an integer in [1, {GAUSS_CAL_MAX_BINS}] (got {n_bins!r})")
+    s = float(sigma_scale)
+    if not (s > 0.0 and np.isfinite(s)):
+        raise ValueError(f"sigma_scale must be positive and finite (got {sigma_scale!r})")
+    p, y, u = (torch.as_tensor(v).reshape(-1) for v in (pred, target, std))
+    n = int(p.numel())
+    if y.numel() != n or u.numel() != n:
+        raise ValueError(f"pred, target and std differ in length ({n}, {y.numel()}, {u.numel()})")
+    if n == 0:
+        raise ValueError("calibration needs at least one row")
+    dev = next((v.device for v in (p, y, u) if v.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    p, y, u = (v.to(dev, torch.float32).contiguous() for v in (p, y, u))
+    nv = GAUSS_CAL_NSUMS + nb_
+    ws = torch.empty(((n + CAL_BLOCK - 1) // CAL_BLOCK) * nv, dtype=torch.float64, device=dev)
+    out = torch.empty(nv, dtype=torch.float64, device=dev)
+    check(lib().rr_gauss_calibration_f64(ptr(p), ptr(u), ptr(y), n, s, nb_, ptr(ws), C.c_size_t(ws.numel() * 8), ptr(out),
+                                         stream()), "rr_gauss_calibration_f64")
+    return out.cpu().numpy()
+
+
+def probabilistic_calibration(pred, target, std, n_bins: int = 20, sigma_scale: float = 1.0) -> dict:
+    """Does `std` have the right SIZE?  The predictive distribution of row i is N(pred_i, (sigma_scale * std_i)^2); one
+    rr_gauss_calibration_f64 call (two launches) gives the raw float64 sums and this forms the means over the VALID rows
+    (finite pred and target, finite positive std):
+
+      n_valid, n_invalid
+      nll          0.5 ln 2 pi + mean ln sigma + mean z^2 / 2,   z = (target - pred) / sigma
+      crps         mean of sigma (z (2 Phi(z) - 1) + 2 phi(z) - 1 / sqrt pi)
+      z_mean, z2_mean    0 and 1 for a calibrated Gaussian
+      sharpness    sqrt(mean sigma^2);   rmse = sqrt(mean (target - pred)^2): equal when calibrated
+      pit_hist     [n_bins] counts of the probability integral transform Phi(z): flat when calibrated
+      expected, observed   j / n_bins and the share of the rows with a PIT below it, j = 1..n_bins (the reliability curve)
+      miscalibration_area  mean_j |observed_j - expected_j|
+      interval_levels, interval_coverage   (even n_bins) the central intervals of level 2k / n_bins, k = 1..n_bins / 2, and
+                   the share of the rows inside (bins n_bins / 2 - k ... n_bins / 2 + k - 1)
+
+    Raises ValueError when no row is valid.  Inputs on the CPU are moved to the current GPU."""
+    o = _gauss_sums(pred, target, std, n_bins, sigma_scale)
+    nb_ = int(n_bins)
+    n = float(o[0])
+    if n < 1:
+        raise ValueError(f"no valid row: all {int(o[1])} have a non-finite mean or target or a std that is not positive and finite")
+    hist = o[GAUSS_CAL_NSUMS:].copy()
+    expected = np.arange(1, nb_ + 1, dtype=np.float64) / nb_
+    observed = np.cumsum(hist) / n
+    res = dict(n_valid=int(o[0]), n_invalid=int(o[1]), sigma_scale=float(sigma_scale),
+               nll=0.5 * float(np.log(2.0 * np.pi)) + o[4] / n + 0.5 * o[3] / n, crps=o[7] / n, z_mean=o[2] / n,
+               z2_mean=o[3] / n, sharpness=float(np.sqrt(o[5] / n)), rmse=float(np.sqrt(o[6] / n)),
+               pit_hist=hist.astype(np.int64), expected=expected, observed=observed,
+               miscalibration_area=float(np.mean(np.abs(observed - expected))))
+    if nb_ % 2 == 0:
+        h = nb_ // 2
+        ks = np.arange(1, h + 1)
+        res["interval_levels"] = 2.0 * ks / nb_
+        res["interval_coverage"] = np.array([hist[h - k:h + k].sum() / n for k in ks])
+    return {k: float(v) if isinstance(v, np.floating) else v for k, v in res.items()}
+
+
+def fit_sigma_scale(pred, target, std) -> float:
+    """The scalar s that minimises the Gaussian negative log-likelihood of N(pred, (s std)^2) over the valid rows, in closed
+    form: sqrt(mean z^2) at sigma_scale = 1.  One rr_gauss_calibration_f64 call."""
+    o = _gauss_sums(pred, target, std, 1, 1.0)
+    if o[0] < 1:
+        raise ValueError("no valid row to fit a sigma scale on")
+    return float(np.sqrt(o[3] / o[0]))
+
+
+def top1_sets(p_top1: torch.Tensor, scope, targets, tau: float, gpu: int = None) -> dict:
+    """Per-list calibration and prediction sets of a top-1 probability - one rr_top1_sets_f32 launch.  `p_top1` [M] (device;
+    a strided column is read in place) are non-negative and sum to about 1 per list of `scope`; `tau` >= 0 (inf allowed).
+
+    Returns a dict of device tensors: rank [M] int32 (1-based, stable descending p, ties by list position), before [M] float64
+    (the probability mass ranked strictly ahead of the candidate, summed in ascending position), in_set [M] bool
+    (before <= tau: the smallest prefix of the predicted order whose mass ahead of its last member is still <= tau) and
+    stats [Q, 9] float64 (TOP1_STAT_NAMES; the true top is the first maximum of the targets).  covered == (E <= tau)
+    exactly.  A NaN or negative probability or a NaN target raises ValueError."""
+    tau = float(tau)
+    if not tau >= 0.0:
+        raise ValueError(f"tau must be >= 0 (got {tau!r})")
+    if p_top1.dim() != 1:
+        raise ValueError(f"p_top1 must be [M] (got shape {tuple(p_top1.shape)})")
+    scope, seg, total, max_len, t = _prep(p_top1, scope, targets, gpu, "p_top1")
+    p = p_top1.detach()
+    p = p if p.dtype == torch.float32 else p.float()
+    if total and (not bool((p >= 0).all()) or bool(torch.isnan(t).any())):
+        raise ValueError("top1_sets: p_top1 holds a NaN or a negative value, or the targets hold a NaN")
+    dev, Q, m = p.device, len(scope), max(total, 1)
+    rank = torch.empty(m, dtype=torch.int32, device=dev)
+    before = torch.empty(m, dtype=torch.float64, device=dev)
+    in_set = torch.empty(m, dtype=torch.uint8, device=dev)
+    stats = torch.empty(max(Q, 1), TOP1_NSTATS, dtype=torch.float64, device=dev)
+    check(lib().rr_top1_sets_f32(ptr(_nonempty(p)), max(p.stride(0), 1) if total else 1, ptr(_nonempty(t)), ptr(seg), Q, max_len,
+                                 tau, ptr(rank), ptr(before), ptr(in_set), ptr(stats), stream()), "rr_top1_sets_f32")
+    return dict(rank=rank[:total], before=before[:total], in_set=in_set[:total].bool(), stats=stats[:Q])
+
+
+def conformal_threshold(scores, alpha: float) -> float:
+    """Split-conformal threshold of the conformity scores E of n calibration queries (NaNs, the empty lists, dropped): the
+    k-th smallest with k = ceil((n + 1) (1 - alpha)), or inf when k > n.  A fresh exchangeable query then has E <= tau with
+    probability >= 1 - alpha (Vovk et al. 2005), and top1_sets' `covered` IS E <= tau."""
+    alpha = float(alpha)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"alpha must lie in (0, 1) (got {alpha!r})")
+    e = scores.detach().cpu().numpy() if torch.is_tensor(scores) else np.asarray(scores)
+    e = np.sort(np.asarray(e, np.float64).reshape(-1))
+    e = e[~np.isnan(e)]
+    n = int(e.size)
+    k = int(np.ceil((n + 1) * (1.0 - alpha)))
+    return float(e[k - 1]) if k <= n else float("inf")
+
+
+def top1_calibration(stats, n_bins: int = 10) -> dict:
+    """Is p_top1 = 0.8 right 80 % of the time?  From top1_sets' per-query `stats` [Q, 9] (rows of empty lists, NaN, dropped):
+    accuracy (mean hit), confidence (mean p of the predicted top), brier (mean), and ece = sum_b (n_b / Q) |acc_b - conf_b|
+    over `n_bins` equal-width confidence bins (bin = min(n_bins - 1, floor(confidence * n_bins))) with the per-bin arrays
+    bin_count, bin_accuracy, bin_confidence (NaN for an empty bin).  Torch operations on Q numbers; no kernel."""
+    nb_ = int(n_bins)
+    if nb_ != n_bins or nb_ < 1:
+        raise ValueError(f"n_bins must be a positive integer (got {n_bins!r})")
+    s = torch.as_tensor(stats, dtype=torch.float64)
+    s = s[~torch.isnan(s[:, 0])]
+    Q = int(s.shape[0])
+    if Q == 0:
+        raise ValueError("no query with candidates")
+    hit, conf = s[:, 0], s[:, 1]
+    b = torch.clamp(torch.floor(conf * nb_), 0, nb_ - 1).long()
+    zero = torch.zeros(nb_, dtype=torch.float64, device=s.device)
+    count = zero.index_add(0, b, torch.ones_like(conf))
+    acc = zero.index_add(0, b, hit) / count
+    cnf = zero.index_add(0, b, conf) / count
+    gap = torch.where(count > 0, (acc - cnf).abs(), zero)
+    return dict(n=Q, accuracy=float(hit.sum()) / Q, confidence=float(conf.sum()) / Q, brier=float(s[:, 4].sum()) / Q,
+                ece=float((count / Q * gap).sum()), bin_count=count.long().cpu().numpy(), bin_accuracy=acc.cpu().numpy(),
+                bin_confidence=cnf.cpu().numpy())
+
+
+def evaluate_calibration(model, calib_batches: Sequence[dict], test_batches: Sequence[dict], path_checkpoints, gpu: int,
+                         method: str = "MC_dropout", alpha: float = 0.1, n_bins: int = 20, **kw) -> dict:
+    """Calibrate on one set of queries, report on another.  evaluate_uncertainty(model, batches, path_checkpoints, gpu,
+    method=method, **kw) runs on `calib_batches` and on `test_batches`; on the calibration set this fits
+    sigma_scale = fit_sigma_scale(mean, targets, std) and tau = conformal_threshold(E, alpha), E being the probability mass
+    ranked strictly ahead of each query's true top (top1_sets); on the test set it reports
+
+      probabilistic   dict(before=probabilistic_calibration at scale 1, after=... at sigma_scale), `n_bins` PIT bins
+      top1            top1_calibration of the test queries
+      tau, coverage (share of the test queries whose true top is in its set), mean_set_size, and per candidate in_set, rank
+      stats [Q, 9], p_top1, targets, scope, mean, std of the test set
+
+    and calibration_set = dict(probabilistic=dict(before, after), coverage, mean_set_size, p_top1, targets, scope) of the
+    calibration set itself (its coverage is at least 1 - alpha by construction).
+    The sigma scale changes the POINTWISE numbers only: p_top1 is left as the method produced it (it is not recomputed under
+    the scaled sigma), and the conformal threshold is what calibrates the ranking side - with exchangeable calibration and
+    test queries the coverage is at least 1 - alpha in expectation whatever p_top1 is."""
+    alpha = float(alpha)
+    if not 0.0 < alpha < 1.0:
+        raise ValueError(f"alpha must lie in (0, 1) (got {alpha!r})")
+    cal = evaluate_uncertainty(model, calib_batches, path_checkpoints, gpu, method=method, **kw)
+    test = evaluate_uncertainty(model, test_batches, path_checkpoints, gpu, method=method, **kw)
+    scale = fit_sigma_scale(cal["mean"], cal["targets"], cal["std"])
+    tau = conformal_threshold(top1_sets(cal["p_top1"], cal["scope"], cal["targets"], 0.0, gpu)["stats"][:, 5], alpha)
+
+    def report(r):
+        sets = top1_sets(r["p_top1"], r["scope"], r["targets"], tau, gpu)
+        st = sets["stats"]
+        live = st[~torch.isnan(st[:, 0])]
+        prob = {k: probabilistic_calibration(r["mean"], r["targets"], r["std"], n_bins, s)
+                for k, s in (("before", 1.0), ("after", scale))}
+        n = max(int(live.shape[0]), 1)                       # (integer sums divided on the host: correctly rounded quotients)
+        return sets, dict(probabilistic=prob, coverage=float(live[:, 7].sum()) / n, mean_set_size=float(live[:, 6].sum()) / n)
+
+    on_cal = dict(report(cal)[1], p_top1=cal["p_top1"], targets=cal["targets"], scope=cal["scope"])
+    sets, on_test = report(test)
+    return dict(method=method, alpha=alpha, sigma_scale=scale, tau=tau, **on_test, top1=top1_calibration(sets["stats"]),
+                in_set=sets["in_set"], rank=sets["rank"], stats=sets["stats"], p_top1=test["p_top1"], targets=test["targets"],
+                scope=test["scope"], mean=test["mean"], std=test["std"], calibration_set=on_cal)
