@@ -251,7 +251,10 @@ typedef struct rr_linear_args {
   uint8_t* mask_bits_out;                           /* optional fourth output (w_packed = 2, N % 4 == 0): the sign of every
                                                        stored element, 1 bit each, rr_mask_bits_row_bytes(N) bytes per row:
                                                        per block of up to 304 columns 2 x 20 bytes - byte 20*h + t holds
-                                                       columns 16*t + 8*h .. + 7 (bit e = column + e).  What a later
+                                                       columns 16*t + 8*h .. + 7 (bit e = column + e).  Bytes 19 and 39
+                                                       of a 40-byte block and the bytes of the 16-column tiles past N stand
+                                                       for no column: they are unspecified (not necessarily written) and
+                                                       never read.  What a later
                                                        dX GEMM needs of this activation (a_mask > 0), at 1/32 of the bytes */
   const uint8_t* a_mask_bits;                       /* alternative to a_mask (w_packed >= 2, k2 = 0, k1 % 4 == 0): such a bit
                                                        image over the k1 columns of A; a_mask is then not read */
@@ -295,7 +298,9 @@ typedef struct rr_pack_desc {
                         [k-step][16-column tile][term][lane 0..63][8 bf16], lane = (k-group of 8) * 16 + column.
                         2: the same buffer receives TWO f16 terms of S * L[r, c] per element (same layout with two terms
                         per tile), S = the power of two with 2^14 <= S * max |L| < 2^15, stored as one float right after
-                        the last k-step's image (rr_linear_f32, w_packed = 3, reads it there) */
+                        the last k-step's image (rr_linear_f32, w_packed = 3, reads it there).  The bytes of dst behind
+                        that float (the buffer is sized for three terms) are unspecified: scratch of the packing
+                        launch, never read by rr_linear_f32 */
 } rr_pack_desc;
 int rr_pack_weights_f32(const rr_pack_desc* descs, int n, rr_stream_t stream);
 size_t rr_split_weight_bytes(int rows, int k1, int k2);
@@ -398,6 +403,8 @@ int rr_head_bwd_f32(const float* dout, const float* raw, int64_t M, int N, int h
  * then inverted dropout (stream seed, index m*(H+F)+c) if drop_p > 0.
  * a_scope is [M,2] = (start, size) as BatchMolGraph.a_scope (featurization.py:276);
  * size == 0 gives a zero row (cached_zero_vector, models/mpn.py:226-227).
+ * Columns H+F .. ld_out-1 of a row of out (the pad of a pitched output) are unspecified: not written here, and no result of
+ * a kernel that reads the rows with k = H+F depends on them.
  * Replaces the per-molecule narrow/sum/div/stack loop + cat (models/mpn.py:224-238). */
 int rr_segment_mean_fwd_f32(const float* x, int64_t ldx, const int32_t* a_scope, int64_t M, int H,
                             const float* feat, int F, float drop_p, uint64_t drop_seed,
