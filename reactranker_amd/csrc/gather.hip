@@ -6,6 +6,7 @@
 // in memory, so the K neighbour rows of a destination are L2-resident and each source row
 // leaves HBM once (algorithmic bytes: DESIGN.md section 4).
 #include "rr_common.h"
+#include <initializer_list>
 
 namespace {
 
@@ -24,6 +25,62 @@ __device__ inline void st(float* p, typename Vec<VEC>::T v) {
 
 // out[r] = sum_k src[idx[r,k]]   (idx < 0 skipped)
 __device__ __attribute__((aligned(16))) const float gather_zero[4] = {0.f, 0.f, 0.f, 0.f};
+
+// Chunk c of source row j.  Pad entries (index < 0) read a zero chunk: the pointer is selected, the load is unconditional - a
+// load under a per-lane branch makes the compiler drain outstanding loads at the join.
+template <int VEC>
+__device__ __forceinline__ typename Vec<VEC>::T ld_row(const float* src, int64_t ld_src, int32_t j, int c) {
+  return ld<VEC>(j >= 0 ? src + j * ld_src + c : gather_zero);
+}
+
+// The sum over a destination's K table entries ir[0 .. K), in table order from +0.0 like sum(dim=1): (((acc + t0) + t1) + t2) + t3
+// per group of four with the four entries' loads in flight together, then the K % 4 remainder one by one.  load(j) issues
+// everything entry j needs (it is called for all four before any term), term(j, loaded) makes the addend of it.
+template <typename V, typename LOAD, typename TERM>
+__device__ __forceinline__ V gather_row_sum(const int32_t* __restrict__ ir, int K, LOAD&& load, TERM&& term) {
+  V acc = V(0.0f);
+  int k = 0;
+  for (; k + 4 <= K; k += 4) {
+    const int32_t j0 = ir[k], j1 = ir[k + 1], j2 = ir[k + 2], j3 = ir[k + 3];
+    const auto x0 = load(j0), x1 = load(j1), x2 = load(j2), x3 = load(j3);
+    acc = (((acc + term(j0, x0)) + term(j1, x1)) + term(j2, x2)) + term(j3, x3);
+  }
+  for (; k < K; ++k) {
+    const int32_t j = ir[k];
+    acc = acc + term(j, load(j));
+  }
+  return acc;
+}
+template <int VEC>                                      // the plain sum: every addend is the source row's chunk itself
+__device__ __forceinline__ typename Vec<VEC>::T gather_plain_sum(const float* __restrict__ src, int64_t ld_src,
+                                                                 const int32_t* __restrict__ ir, int K, int c) {
+  using V = typename Vec<VEC>::T;
+  return gather_row_sum<V>(ir, K, [&](int32_t j) { return ld_row<VEC>(src, ld_src, j, c); }, [](int32_t, V v) { return v; });
+}
+
+// The ReLU / dropout backward select, mask > 0 ? g * scale : 0 per element, with the mask as the four sign bits of the chunk
+// (epi_nibble) or as the f32 activations themselves.
+template <typename V4>
+__device__ __forceinline__ V4 mask_select(V4 g, uint32_t nib, float scale) {
+  g.x = (nib & 1u) ? g.x * scale : 0.f; g.y = (nib & 2u) ? g.y * scale : 0.f;
+  g.z = (nib & 4u) ? g.z * scale : 0.f; g.w = (nib & 8u) ? g.w * scale : 0.f;
+  return g;
+}
+template <typename V4, typename M4>
+__device__ __forceinline__ V4 mask_select(V4 g, M4 m, float scale) {
+  g.x = m.x > 0.f ? g.x * scale : 0.f; g.y = m.y > 0.f ? g.y * scale : 0.f;
+  g.z = m.z > 0.f ? g.z * scale : 0.f; g.w = m.w > 0.f ? g.w * scale : 0.f;
+  return g;
+}
+__device__ __forceinline__ float mask_select(float g, float m, float scale) { return m > 0.f ? g * scale : 0.f; }
+
+// Dropout of the four elements base .. base + 3 of the mask stream, base % 4 == 0 (one aligned group: one first-level hash)
+__device__ __forceinline__ f32x4 keep_scale4(f32x4 v, uint64_t seed, uint64_t base, uint32_t thr, float keep_scale) {
+  const uint32_t w = rr_hash_group(seed, base >> 2);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v[q] = rr_hash_lane(w, q) >= thr ? v[q] * keep_scale : 0.f;
+  return v;
+}
 
 // Element range of a block for the gather kernels.  Blocks are dealt round-robin over the 8 XCDs (b and b + 8 share one, each
 // with its own L2): with a plain grid-stride loop the K destinations that read one source row run on different XCDs and
@@ -82,7 +139,7 @@ __device__ __forceinline__ void gather_walk(const float* __restrict__ src, int64
     for (int k = 0; k < KT; ++k) jn[k] = irn[k];
     const int c = q * 4;
     f32x4 v[KT];
-    for (int k = 0; k < KT; ++k) v[k] = ld<4>(j[k] >= 0 ? src + j[k] * ld_src + c : gather_zero);
+    for (int k = 0; k < KT; ++k) v[k] = ld_row<4>(src, ld_src, j[k], c);
     auto aux = pre(r, c);
     f32x4 acc = FROM_ZERO ? f32x4(0.0f) + v[0] : v[0];  // (0 + v0 turns a -0.0 into +0.0, as the sum loop always did)
     for (int k = 1; k < KT; ++k) acc = acc + v[k];
@@ -93,6 +150,15 @@ __device__ __forceinline__ void gather_walk(const float* __restrict__ src, int64
     q = qn;
     for (int k = 0; k < KT; ++k) j[k] = jn[k];
   }
+}
+// the walk at the pad widths it exists for, K in 1..4
+template <typename PRE, typename FIN>
+__device__ __forceinline__ void gather_walk_k(const float* __restrict__ src, int64_t ld_src, const int32_t* __restrict__ idx,
+                                              int K, int HV, int64_t wbeg, int64_t wend, PRE&& pre, FIN&& fin) {
+  if (K == 4) gather_walk<4>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
+  else if (K == 3) gather_walk<3>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
+  else if (K == 2) gather_walk<2>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
+  else gather_walk<1>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
 }
 #endif
 
@@ -119,6 +185,37 @@ __device__ inline void amax_commit(float m, float* out) {      // every thread o
   }
 }
 
+// The padding-row reduction of gather_sum_kernel / gather_sum_epi_kernel: with one, the LAST HV blocks of the grid do this
+// instead of gathering - block j sums column group j (columns c ..) of all partial rows (256 threads stride over the rows,
+// two loads in flight each, then a fixed-order LDS + shuffle tree) and its thread 0 writes out[0, group j]: the reduction
+// runs next to the gather instead of as a straggler thread or an extra launch.  Every thread of the block calls it;
+// thread 0 hands the sum to put(v), which stores it.
+template <int VEC, typename PUT>
+__device__ __forceinline__ void padrow_sum(const float* __restrict__ partial, int64_t n_partial, int64_t ld_partial, int c,
+                                           PUT&& put) {
+  using V = typename Vec<VEC>::T;
+  __shared__ float red[256 * VEC];
+  V a0 = V(0.f), a1 = V(0.f);
+  int64_t i = threadIdx.x;
+  for (; i + 256 < n_partial; i += 512) {
+    a0 = a0 + ld<VEC>(partial + i * ld_partial + c);
+    a1 = a1 + ld<VEC>(partial + (i + 256) * ld_partial + c);
+  }
+  if (i < n_partial) a0 = a0 + ld<VEC>(partial + i * ld_partial + c);
+  st<VEC>(&red[threadIdx.x * VEC], a0 + a1);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    V v = (ld<VEC>(&red[threadIdx.x * VEC]) + ld<VEC>(&red[(threadIdx.x + 64) * VEC])) +
+          (ld<VEC>(&red[(threadIdx.x + 128) * VEC]) + ld<VEC>(&red[(threadIdx.x + 192) * VEC]));
+    if constexpr (VEC == 4) {
+      v.x = rr_wave_sum(v.x); v.y = rr_wave_sum(v.y); v.z = rr_wave_sum(v.z); v.w = rr_wave_sum(v.w);
+    } else {
+      v = rr_wave_sum(v);
+    }
+    if (threadIdx.x == 0) put(v);
+  }
+}
+
 // out[r] = sum_k (mask[j_k] > 0 ? src[j_k] * scale : 0): a ReLU / dropout backward (rr_relu_bwd_f32) folded into the gather
 // that consumes it - the same products in the same order, so the result equals the two-kernel sequence bit for bit, without
 // writing and re-reading the masked tensor.  Used where the masked tensor has no other reader: the shared-prefix reactant
@@ -130,34 +227,16 @@ __global__ void __launch_bounds__(256) gather_sum_masked_kernel(const float* __r
                                                                 int64_t ld_out) {
   using V = typename Vec<VEC>::T;
   const int64_t total = n_out * HV;
-  auto masked = [&](V v, V m) -> V {
-    if constexpr (VEC == 4) {
-      V r;
-      r.x = m.x > 0.f ? v.x * scale : 0.f; r.y = m.y > 0.f ? v.y * scale : 0.f;
-      r.z = m.z > 0.f ? v.z * scale : 0.f; r.w = m.w > 0.f ? v.w * scale : 0.f;
-      return r;
-    } else {
-      return m > 0.f ? v * scale : 0.f;
-    }
-  };
+  struct Row { V v, m; };
   RR_GATHER_LOOP(e, static_cast<int>(gridDim.x), total) {
     const int64_t r = e / HV;
     const int c = static_cast<int>(e - r * HV) * VEC;
-    const int32_t* ir = idx + r * K;
-    V acc = V(0.0f);
-    int k = 0;
-    for (; k + 4 <= K; k += 4) {          // 8 independent row loads in flight; pad entries read the zero chunk
-      const int32_t j0 = ir[k], j1 = ir[k + 1], j2 = ir[k + 2], j3 = ir[k + 3];
-      const V v0 = ld<VEC>(j0 >= 0 ? src + j0 * ld_src + c : gather_zero), m0 = ld<VEC>(j0 >= 0 ? mask + j0 * ld_src + c : gather_zero);
-      const V v1 = ld<VEC>(j1 >= 0 ? src + j1 * ld_src + c : gather_zero), m1 = ld<VEC>(j1 >= 0 ? mask + j1 * ld_src + c : gather_zero);
-      const V v2 = ld<VEC>(j2 >= 0 ? src + j2 * ld_src + c : gather_zero), m2 = ld<VEC>(j2 >= 0 ? mask + j2 * ld_src + c : gather_zero);
-      const V v3 = ld<VEC>(j3 >= 0 ? src + j3 * ld_src + c : gather_zero), m3 = ld<VEC>(j3 >= 0 ? mask + j3 * ld_src + c : gather_zero);
-      acc = (((acc + masked(v0, m0)) + masked(v1, m1)) + masked(v2, m2)) + masked(v3, m3);
-    }
-    for (; k < K; ++k) {
-      const int32_t j = ir[k];
-      acc = acc + masked(ld<VEC>(j >= 0 ? src + j * ld_src + c : gather_zero), ld<VEC>(j >= 0 ? mask + j * ld_src + c : gather_zero));
-    }
+    const V acc = gather_row_sum<V>(                    // 8 independent row loads in flight
+        idx + r * K, K,
+        [&](int32_t j) {                                // (written out: through ld_row the scalar kernel takes 28 VGPRs for 30)
+          return Row{ld<VEC>(j >= 0 ? src + j * ld_src + c : gather_zero), ld<VEC>(j >= 0 ? mask + j * ld_src + c : gather_zero)};
+        },
+        [&](int32_t, const Row& x) { return mask_select(x.v, x.m, scale); });
     st<VEC>(out + r * ld_out + c, acc);
   }
 }
@@ -189,20 +268,7 @@ __global__ void __launch_bounds__(256) gather_sum_dropmask_kernel(const float* _
       }
       return t;
     };
-    f32x4 acc = f32x4(0.0f);
-    int k = 0;
-    for (; k + 4 <= K; k += 4) {          // four row loads in flight; pad entries read the zero chunk
-      const int32_t j0 = ir[k], j1 = ir[k + 1], j2 = ir[k + 2], j3 = ir[k + 3];
-      const f32x4 v0 = ld<4>(j0 >= 0 ? src + j0 * ld_src + c : gather_zero);
-      const f32x4 v1 = ld<4>(j1 >= 0 ? src + j1 * ld_src + c : gather_zero);
-      const f32x4 v2 = ld<4>(j2 >= 0 ? src + j2 * ld_src + c : gather_zero);
-      const f32x4 v3 = ld<4>(j3 >= 0 ? src + j3 * ld_src + c : gather_zero);
-      acc = (((acc + term(j0, v0)) + term(j1, v1)) + term(j2, v2)) + term(j3, v3);
-    }
-    for (; k < K; ++k) {
-      const int32_t j = ir[k];
-      acc = acc + term(j, ld<4>(j >= 0 ? src + j * ld_src + c : gather_zero));
-    }
+    const f32x4 acc = gather_row_sum<f32x4>(ir, K, [&](int32_t j) { return ld_row<4>(src, ld_src, j, c); }, term);
     st<4>(out + r * ld_out + c, acc);
   }
 }
@@ -216,43 +282,19 @@ __global__ void __launch_bounds__(256) gather_sum_kernel(const float* __restrict
   using V = typename Vec<VEC>::T;
   const int64_t total = n_out * HV;
   float am = 0.f;
-  // With a padding-row reduction the LAST HV blocks of the grid do that instead of gathering: block j sums column
-  // group j of all partial rows (256 threads stride over the rows, then a fixed-order LDS + shuffle tree) and writes
-  // out[0, group j] - the reduction runs next to the gather instead of as a straggler thread or an extra launch.
   const int gblocks = row0_partial ? static_cast<int>(gridDim.x) - HV : static_cast<int>(gridDim.x);
   if (row0_partial != nullptr && static_cast<int>(blockIdx.x) >= gblocks) {
-    __shared__ float red[256 * VEC];
     const int c = (static_cast<int>(blockIdx.x) - gblocks) * VEC;
-    V a0 = V(0.f), a1 = V(0.f);
-    int64_t i = threadIdx.x;
-    for (; i + 256 < n_partial; i += 512) {
-      a0 = a0 + ld<VEC>(row0_partial + i * ld_partial + c);
-      a1 = a1 + ld<VEC>(row0_partial + (i + 256) * ld_partial + c);
-    }
-    if (i < n_partial) a0 = a0 + ld<VEC>(row0_partial + i * ld_partial + c);
-    st<VEC>(&red[threadIdx.x * VEC], a0 + a1);
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      V v = (ld<VEC>(&red[threadIdx.x * VEC]) + ld<VEC>(&red[(threadIdx.x + 64) * VEC])) +
-            (ld<VEC>(&red[(threadIdx.x + 128) * VEC]) + ld<VEC>(&red[(threadIdx.x + 192) * VEC]));
-      if constexpr (VEC == 4) {
-        v.x = rr_wave_sum(v.x); v.y = rr_wave_sum(v.y); v.z = rr_wave_sum(v.z); v.w = rr_wave_sum(v.w);
-      } else {
-        v = rr_wave_sum(v);
-      }
-      if (threadIdx.x == 0) {
-        st<VEC>(out + c, v);
-        am = amax_fold(am, v);
-      }
-    }
+    padrow_sum<VEC>(row0_partial, n_partial, ld_partial, c, [&](V v) {
+      st<VEC>(out + c, v);
+      am = amax_fold(am, v);
+    });
     amax_commit(am, amax_out);
     return;
   }
 #ifdef RR_GATHER_WALK
   if constexpr (VEC == 4) {
     if (K >= 1 && K <= 4) {
-      int64_t wbeg, wend;
-      gather_block_range(gblocks, total, &wbeg, &wend);
       const bool skip0 = row0_partial != nullptr;
       auto pre = [](int64_t, int) { return 0; };
       auto fin = [&](int64_t r, int c, f32x4 acc, int) {
@@ -261,10 +303,9 @@ __global__ void __launch_bounds__(256) gather_sum_kernel(const float* __restrict
           am = amax_fold(am, acc);
         }
       };
-      if (K == 4) gather_walk<4>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else if (K == 3) gather_walk<3>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else if (K == 2) gather_walk<2>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else gather_walk<1>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
+      int64_t wbeg, wend;
+      gather_block_range(gblocks, total, &wbeg, &wend);
+      gather_walk_k(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
       amax_commit(am, amax_out);
       return;
     }
@@ -274,23 +315,7 @@ __global__ void __launch_bounds__(256) gather_sum_kernel(const float* __restrict
     const int64_t r = e / HV;
     const int c = static_cast<int>(e - r * HV) * VEC;
     if (r == 0 && row0_partial != nullptr) continue;          // written by the reduction blocks
-    const int32_t* ir = idx + r * K;
-    V acc = V(0.0f);
-    int k = 0;
-    // pad entries (index < 0) read a zero chunk: the pointer is selected, the load is unconditional - a load
-    // under a per-lane branch makes the compiler drain outstanding loads at the join
-    for (; k + 4 <= K; k += 4) {          // 4 independent row loads in flight
-      const int32_t j0 = ir[k], j1 = ir[k + 1], j2 = ir[k + 2], j3 = ir[k + 3];
-      const V v0 = ld<VEC>(j0 >= 0 ? src + j0 * ld_src + c : gather_zero);
-      const V v1 = ld<VEC>(j1 >= 0 ? src + j1 * ld_src + c : gather_zero);
-      const V v2 = ld<VEC>(j2 >= 0 ? src + j2 * ld_src + c : gather_zero);
-      const V v3 = ld<VEC>(j3 >= 0 ? src + j3 * ld_src + c : gather_zero);
-      acc = (((acc + v0) + v1) + v2) + v3;   // k order, like sum(dim=1)
-    }
-    for (; k < K; ++k) {
-      const int32_t j = ir[k];
-      acc = acc + ld<VEC>(j >= 0 ? src + j * ld_src + c : gather_zero);
-    }
+    const V acc = gather_plain_sum<VEC>(src, ld_src, idx + r * K, K, c);
     st<VEC>(out + r * ld_out + c, acc);
     am = amax_fold(am, acc);
   }
@@ -387,37 +412,28 @@ __device__ __forceinline__ EpiAux<NADD> epi_load(const GatherEpi& E, int64_t r, 
   return x;
 }
 template <int NADD>
-__device__ __forceinline__ f32x4 epi_finish(const GatherEpi& E, f32x4 g, const EpiAux<NADD>& x) {   // = epi_apply on loaded values
+__device__ __forceinline__ f32x4 epi_finish(const GatherEpi& E, f32x4 g, const EpiAux<NADD>& x) {
   f32x4 v = g;
-  if (E.bits != nullptr) {
-    v.x = (x.nib & 1u) ? g.x * E.scale : 0.f; v.y = (x.nib & 2u) ? g.y * E.scale : 0.f;
-    v.z = (x.nib & 4u) ? g.z * E.scale : 0.f; v.w = (x.nib & 8u) ? g.w * E.scale : 0.f;
-  } else if (E.mask != nullptr) {
-    v.x = x.m.x > 0.f ? g.x * E.scale : 0.f; v.y = x.m.y > 0.f ? g.y * E.scale : 0.f;
-    v.z = x.m.z > 0.f ? g.z * E.scale : 0.f; v.w = x.m.w > 0.f ? g.w * E.scale : 0.f;
-  }
+  if (E.bits != nullptr) v = mask_select(g, x.nib, E.scale);
+  else if (E.mask != nullptr) v = mask_select(g, x.m, E.scale);
   if (NADD == 0) return v;
-  f32x4 s = f32x4(0.f);
+  f32x4 s = f32x4(0.f);                               // fixed order: ((0 + add_0) + add_1) + ... , then + v (rr_relu_bwd_sum_f32's)
 #pragma unroll
   for (int j = 0; j < NADD; ++j) s = s + x.a[j];
   return s + v;
 }
 
-// NADD >= 0: that many addends, unrolled (their loads fly with the gather's); NADD < 0: E.n_adds at run time
+// The epilogue of the generic loop and of the padding-row sum.  NADD >= 0: that many addends, unrolled; NADD < 0: E.n_adds at
+// run time.  (For NADD >= 0 this computes epi_finish<NADD>(E, g, epi_load<NADD>(E, r, c)), but written that way the addend
+// loads are issued ahead of the mask's select and every gather_sum_epi_kernel<0..5> allocates 4 SGPRs fewer than it did -
+// profiles/gather_single_source_ab.txt; the kernels are held to their allocation, so the body stays.)
 template <int NADD>
 __device__ inline f32x4 epi_apply(const GatherEpi& E, int64_t r, int c, f32x4 g) {
   f32x4 v = g;
-  if (E.bits != nullptr) {
-    const uint32_t nib = epi_nibble(E.bits, E.bits_row, r, c);
-    v.x = (nib & 1u) ? g.x * E.scale : 0.f; v.y = (nib & 2u) ? g.y * E.scale : 0.f;
-    v.z = (nib & 4u) ? g.z * E.scale : 0.f; v.w = (nib & 8u) ? g.w * E.scale : 0.f;
-  } else if (E.mask != nullptr) {
-    const f32x4 m = ld<4>(E.mask + r * E.ld_mask + c);
-    v.x = m.x > 0.f ? g.x * E.scale : 0.f; v.y = m.y > 0.f ? g.y * E.scale : 0.f;
-    v.z = m.z > 0.f ? g.z * E.scale : 0.f; v.w = m.w > 0.f ? g.w * E.scale : 0.f;
-  }
+  if (E.bits != nullptr) v = mask_select(g, epi_nibble(E.bits, E.bits_row, r, c), E.scale);
+  else if (E.mask != nullptr) v = mask_select(g, ld<4>(E.mask + r * E.ld_mask + c), E.scale);
   if (NADD == 0) return v;
-  f32x4 s = f32x4(0.f);                               // fixed order: ((0 + add_0) + add_1) + ... , then + v (rr_relu_bwd_sum_f32's)
+  f32x4 s = f32x4(0.f);
   if (NADD > 0) {
 #pragma unroll
     for (int j = 0; j < (NADD > 0 ? NADD : 1); ++j) s = s + ld<4>(E.adds[j] + r * E.ld_add + c);
@@ -433,40 +449,22 @@ __global__ void __launch_bounds__(256) gather_sum_epi_kernel(const float* __rest
                                                              float* __restrict__ out, int64_t ld_out,
                                                              const float* __restrict__ row0_partial, int64_t n_partial,
                                                              int64_t ld_partial, const GatherEpi E) {
-  using V = f32x4;
   const int64_t total = n_out * HV;
   float am = 0.f;
   const int gblocks = row0_partial ? static_cast<int>(gridDim.x) - HV : static_cast<int>(gridDim.x);
-  if (row0_partial != nullptr && static_cast<int>(blockIdx.x) >= gblocks) {      // padding-row reduction, see gather_sum_kernel
-    __shared__ float red[256 * 4];
+  if (row0_partial != nullptr && static_cast<int>(blockIdx.x) >= gblocks) {
     const int c = (static_cast<int>(blockIdx.x) - gblocks) * 4;
-    V a0 = V(0.f), a1 = V(0.f);
-    int64_t i = threadIdx.x;
-    for (; i + 256 < n_partial; i += 512) {
-      a0 = a0 + ld<4>(row0_partial + i * ld_partial + c);
-      a1 = a1 + ld<4>(row0_partial + (i + 256) * ld_partial + c);
-    }
-    if (i < n_partial) a0 = a0 + ld<4>(row0_partial + i * ld_partial + c);
-    st<4>(&red[threadIdx.x * 4], a0 + a1);
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      V v = (ld<4>(&red[threadIdx.x * 4]) + ld<4>(&red[(threadIdx.x + 64) * 4])) +
-            (ld<4>(&red[(threadIdx.x + 128) * 4]) + ld<4>(&red[(threadIdx.x + 192) * 4]));
-      v.x = rr_wave_sum(v.x); v.y = rr_wave_sum(v.y); v.z = rr_wave_sum(v.z); v.w = rr_wave_sum(v.w);
-      if (threadIdx.x == 0) {
-        const f32x4 o = epi_apply<NADD>(E, 0, c, v);
-        st<4>(out + c, o);
-        am = amax_fold(am, o);
-      }
-    }
+    padrow_sum<4>(row0_partial, n_partial, ld_partial, c, [&](f32x4 v) {
+      const f32x4 o = epi_apply<NADD>(E, 0, c, v);
+      st<4>(out + c, o);
+      am = amax_fold(am, o);
+    });
     amax_commit(am, E.amax_out);
     return;
   }
 #ifdef RR_GATHER_WALK
   if constexpr (NADD >= 0) {
     if (K >= 1 && K <= 4) {
-      int64_t wbeg, wend;
-      gather_block_range(gblocks, total, &wbeg, &wend);
       const bool skip0 = row0_partial != nullptr;
       auto pre = [&](int64_t r, int c) { return epi_load<NADD>(E, r, c); };
       auto fin = [&](int64_t r, int c, f32x4 acc, const EpiAux<NADD>& x) {
@@ -476,10 +474,9 @@ __global__ void __launch_bounds__(256) gather_sum_epi_kernel(const float* __rest
           am = amax_fold(am, o);
         }
       };
-      if (K == 4) gather_walk<4>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else if (K == 3) gather_walk<3>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else if (K == 2) gather_walk<2>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
-      else gather_walk<1>(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
+      int64_t wbeg, wend;
+      gather_block_range(gblocks, total, &wbeg, &wend);
+      gather_walk_k(src, ld_src, idx, K, HV, wbeg, wend, pre, fin);
       amax_commit(am, E.amax_out);
       return;
     }
@@ -489,22 +486,7 @@ __global__ void __launch_bounds__(256) gather_sum_epi_kernel(const float* __rest
     const int64_t r = e / HV;
     const int c = static_cast<int>(e - r * HV) * 4;
     if (r == 0 && row0_partial != nullptr) continue;
-    const int32_t* ir = idx + r * K;
-    V acc = V(0.0f);
-    int k = 0;
-    for (; k + 4 <= K; k += 4) {
-      const int32_t j0 = ir[k], j1 = ir[k + 1], j2 = ir[k + 2], j3 = ir[k + 3];
-      const V v0 = ld<4>(j0 >= 0 ? src + j0 * ld_src + c : gather_zero);
-      const V v1 = ld<4>(j1 >= 0 ? src + j1 * ld_src + c : gather_zero);
-      const V v2 = ld<4>(j2 >= 0 ? src + j2 * ld_src + c : gather_zero);
-      const V v3 = ld<4>(j3 >= 0 ? src + j3 * ld_src + c : gather_zero);
-      acc = (((acc + v0) + v1) + v2) + v3;
-    }
-    for (; k < K; ++k) {
-      const int32_t j = ir[k];
-      acc = acc + ld<4>(j >= 0 ? src + j * ld_src + c : gather_zero);
-    }
-    const f32x4 o = epi_apply<NADD>(E, r, c, acc);
+    const f32x4 o = epi_apply<NADD>(E, r, c, gather_plain_sum<4>(src, ld_src, idx + r * K, K, c));
     st<4>(out + r * ld_out + c, o);
     am = amax_fold(am, o);
   }
@@ -551,8 +533,8 @@ __global__ void __launch_bounds__(256) gather_diff_kernel(const float* __restric
     const int64_t r = e / HV;
     const int c = static_cast<int>(e - r * HV) * VEC;
     const int32_t ja = ia[r], jm = im[r];
-    const V va = ld<VEC>(ja >= 0 ? a + ja * ld_a + c : gather_zero);      // both row loads in flight together
-    const V vm = ld<VEC>(jm >= 0 ? m + jm * ld_m + c : gather_zero);
+    const V va = ld_row<VEC>(a, ld_a, ja, c);                             // both row loads in flight together
+    const V vm = ld_row<VEC>(m, ld_m, jm, c);
     st<VEC>(out + r * ld_out + c, va - vm);
   }
 }
@@ -572,12 +554,8 @@ __global__ void __launch_bounds__(256) gather_dropout_kernel(const float* __rest
     gather_block_range(static_cast<int>(gridDim.x), total, &wbeg, &wend);
     auto pre = [](int64_t, int) { return 0; };
     auto fin = [&](int64_t r, int c, f32x4 v, int) {
-      if (thr != 0u) {                                  // H % 4 == 0 and c % 4 == 0: one aligned group of the mask stream
-        const uint64_t base = static_cast<uint64_t>(r) * static_cast<uint64_t>(H) + static_cast<uint64_t>(c);
-        const uint32_t w = rr_hash_group(seed, base >> 2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = rr_hash_lane(w, q) >= thr ? v[q] * keep_scale : 0.f;
-      }
+      // (H % 4 == 0 and c % 4 == 0: one aligned group of the mask stream)
+      if (thr != 0u) v = keep_scale4(v, seed, static_cast<uint64_t>(r) * static_cast<uint64_t>(H) + static_cast<uint64_t>(c), thr, keep_scale);
       st<4>(out + r * ld_out + c, v);
       am = amax_fold(am, v);
     };
@@ -590,16 +568,11 @@ __global__ void __launch_bounds__(256) gather_dropout_kernel(const float* __rest
     const int64_t r = e / HV;
     const int c = static_cast<int>(e - r * HV) * VEC;
     const int32_t j = idx[r];
-    V v = ld<VEC>(j >= 0 ? src + j * ld_src + c : gather_zero);
+    V v = ld_row<VEC>(src, ld_src, j, c);
     if (thr != 0u) {
       const uint64_t base = static_cast<uint64_t>(r) * static_cast<uint64_t>(H) + static_cast<uint64_t>(c);
-      if constexpr (VEC == 4) {                       // H % 4 == 0 and c % 4 == 0: one aligned group of the mask stream
-        const uint32_t w = rr_hash_group(seed, base >> 2);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = rr_hash_lane(w, q) >= thr ? v[q] * keep_scale : 0.f;
-      } else {
-        v = rr_keep(seed, base, thr) ? v * keep_scale : 0.f;
-      }
+      if constexpr (VEC == 4) v = keep_scale4(v, seed, base, thr, keep_scale);
+      else v = rr_keep(seed, base, thr) ? v * keep_scale : 0.f;
     }
     st<VEC>(out + r * ld_out + c, v);
     am = amax_fold(am, v);
@@ -788,20 +761,35 @@ __global__ void __launch_bounds__(256) segment_mean_bwd_vec_kernel(const float* 
     }
     // optional: the ReLU / dropout backward of the layer that produced the readout's input (dZ = dx * (y > 0) * scale),
     // so the dX GEMMs downstream read a plain operand
-    if (mask_bits != nullptr) {
-      const uint32_t nib = epi_nibble(mask_bits, bits_row, a, c);
-      v.x = (nib & 1u) ? v.x * mask_scale : 0.f; v.y = (nib & 2u) ? v.y * mask_scale : 0.f;
-      v.z = (nib & 4u) ? v.z * mask_scale : 0.f; v.w = (nib & 8u) ? v.w * mask_scale : 0.f;
-    } else if (mask != nullptr) {
-      const float4 m = *reinterpret_cast<const float4*>(mask + a * ld_mask + c);
-      v.x = m.x > 0.f ? v.x * mask_scale : 0.f; v.y = m.y > 0.f ? v.y * mask_scale : 0.f;
-      v.z = m.z > 0.f ? v.z * mask_scale : 0.f; v.w = m.w > 0.f ? v.w * mask_scale : 0.f;
-    }
+    if (mask_bits != nullptr) v = mask_select(v, epi_nibble(mask_bits, bits_row, a, c), mask_scale);
+    else if (mask != nullptr) v = mask_select(v, ld<4>(mask + a * ld_mask + c), mask_scale);
     *reinterpret_cast<float4*>(dx + a * ldx + c) = v;
     am = fmaxf(fmaxf(am, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
   }
   amax_commit(am, amax_out);
 }
+
+// "Rows are whole 16-byte chunks" - what the <4> kernels need: the width and every leading dimension a multiple of four
+// floats, every pointer 16-byte aligned.
+bool rows_are_chunks(int H, std::initializer_list<int64_t> lds, std::initializer_list<const void*> ptrs) {
+  bool ok = H % 4 == 0;
+  for (const int64_t ld : lds) ok = ok && ld % 4 == 0;
+  for (const void* p : ptrs) ok = ok && rr_aligned16(p);
+  return ok;
+}
+
+// The <4> / <1> launch pair of a kernel templated on VEC, one thread per (row, chunk | float): W, usable in the arguments,
+// is the row width in the units of the form chosen; with pad_blocks, W more blocks follow the gather blocks (padrow_sum).
+#define RR_LAUNCH_ROWS(vec, kernel, n_out, H, pad_blocks, s, ...)                                       \
+  do {                                                                                                  \
+    if (vec) {                                                                                          \
+      const int W = (H) / 4;                                                                            \
+      kernel<4><<<rr_grid_for((n_out) * W, 256) + ((pad_blocks) ? W : 0), 256, 0, s>>>(__VA_ARGS__);    \
+    } else {                                                                                            \
+      const int W = (H);                                                                                \
+      kernel<1><<<rr_grid_for((n_out) * W, 256) + ((pad_blocks) ? W : 0), 256, 0, s>>>(__VA_ARGS__);    \
+    }                                                                                                   \
+  } while (0)
 
 }  // namespace
 
@@ -815,16 +803,10 @@ int rr_gather_sum_amax_f32(const float* src, int64_t n_src, int64_t ld_src, cons
   RR_CHECK_ARG(!row0_partial || (n_out >= 1 && n_partial >= 0 && ld_partial >= H));
   if (n_out == 0) return RR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(src) && rr_aligned16(out);
-  if (row0_partial) vec = vec && (ld_partial % 4 == 0) && rr_aligned16(row0_partial);
-  if (vec) {
-    const int HV = H / 4;
-    gather_sum_kernel<4><<<rr_grid_for(n_out * HV, 256) + (row0_partial ? HV : 0), 256, 0, s>>>(
-        src, ld_src, idx, n_out, K, HV, out, ld_out, row0_partial, n_partial, ld_partial, amax_out);
-  } else {
-    gather_sum_kernel<1><<<rr_grid_for(n_out * H, 256) + (row0_partial ? H : 0), 256, 0, s>>>(
-        src, ld_src, idx, n_out, K, H, out, ld_out, row0_partial, n_partial, ld_partial, amax_out);
-  }
+  bool vec = rows_are_chunks(H, {ld_src, ld_out}, {src, out});
+  if (row0_partial) vec = vec && rows_are_chunks(H, {ld_partial}, {row0_partial});
+  RR_LAUNCH_ROWS(vec, gather_sum_kernel, n_out, H, row0_partial != nullptr, s, src, ld_src, idx, n_out, K, W, out, ld_out,
+                 row0_partial, n_partial, ld_partial, amax_out);
   return rr_launch_status();
 }
 
@@ -838,7 +820,7 @@ int rr_gather_sum_multi_f32(const float* const* srcs, int n_srcs, int64_t n_src,
   RR_CHECK_ARG(srcs && idx && out && n_srcs >= 1 && n_srcs <= RR_MAX_GATHER_SRCS && n_src >= 0 && n_out >= 0 && K >= 1 && H >= 1 &&
                ld_src >= H && ld_out >= H);
   GatherSrcs S{};
-  bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(out);
+  bool vec = rows_are_chunks(H, {ld_src, ld_out}, {out});
   for (int q = 0; q < n_srcs; ++q) {
     RR_CHECK_ARG(srcs[q] != nullptr);
     S.s[q] = srcs[q];
@@ -873,9 +855,9 @@ int rr_gather_sum_epi_f32(const float* src, int64_t n_src, int64_t ld_src, const
   RR_CHECK_ARG(epi->n_adds >= 0 && epi->n_adds <= RR_MAX_GATHER_ADDS && (epi->n_adds == 0 || epi->ld_add >= H));
   RR_CHECK_ARG(!epi->mask || epi->ld_mask >= H);
   // the fused form exists for the straight-line geometry only (what the packer and the step plans produce)
-  bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(src) && rr_aligned16(out);
-  if (row0_partial) vec = vec && (ld_partial % 4 == 0) && rr_aligned16(row0_partial);
-  if (epi->mask && !epi->mask_bits) vec = vec && (epi->ld_mask % 4 == 0) && rr_aligned16(epi->mask);
+  bool vec = rows_are_chunks(H, {ld_src, ld_out}, {src, out});
+  if (row0_partial) vec = vec && rows_are_chunks(H, {ld_partial}, {row0_partial});
+  if (epi->mask && !epi->mask_bits) vec = vec && rows_are_chunks(H, {epi->ld_mask}, {epi->mask});
   GatherEpi E;
   E.mask = epi->mask_bits ? nullptr : epi->mask;
   E.ld_mask = epi->ld_mask;
@@ -889,7 +871,7 @@ int rr_gather_sum_epi_f32(const float* src, int64_t n_src, int64_t ld_src, const
     E.adds[j] = j < epi->n_adds ? epi->adds[j] : nullptr;
     if (j < epi->n_adds) {
       RR_CHECK_ARG(epi->adds[j]);
-      vec = vec && (epi->ld_add % 4 == 0) && rr_aligned16(epi->adds[j]);
+      vec = vec && rows_are_chunks(H, {epi->ld_add}, {epi->adds[j]});
     }
   }
   if (!vec) return RR_ERR_ALIGN;
@@ -919,16 +901,8 @@ int rr_gather_sum_masked_f32(const float* src, const float* mask, int64_t n_src,
                              int64_t n_out, int K, int H, float scale, float* out, int64_t ld_out, rr_stream_t stream) {
   RR_CHECK_ARG(src && mask && idx && out && n_src >= 0 && n_out >= 1 && K >= 1 && H >= 1 && ld_src >= H && ld_out >= H);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(src) && rr_aligned16(mask) &&
-                   rr_aligned16(out);
-  if (vec) {
-    const int HV = H / 4;
-    gather_sum_masked_kernel<4><<<rr_grid_for(n_out * HV, 256), 256, 0, s>>>(src, mask, ld_src, idx, n_out, K, HV, scale, out,
-                                                                             ld_out);
-  } else {
-    gather_sum_masked_kernel<1><<<rr_grid_for(n_out * H, 256), 256, 0, s>>>(src, mask, ld_src, idx, n_out, K, H, scale, out,
-                                                                            ld_out);
-  }
+  const bool vec = rows_are_chunks(H, {ld_src, ld_out}, {src, mask, out});
+  RR_LAUNCH_ROWS(vec, gather_sum_masked_kernel, n_out, H, false, s, src, mask, ld_src, idx, n_out, K, W, scale, out, ld_out);
   return rr_launch_status();
 }
 
@@ -937,8 +911,8 @@ int rr_gather_sum_dropmask_f32(const float* src, int64_t n_src, int64_t ld_src, 
                                float* out, int64_t ld_out, rr_stream_t stream) {
   RR_CHECK_ARG(src && y && idx && out && n_src >= 0 && n_out >= 1 && K >= 1 && H >= 1 && ld_src >= H && ld_y >= H && ld_out >= H);
   RR_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
-  if (!(H % 4 == 0 && ld_src % 4 == 0 && ld_y % 4 == 0 && ld_out % 4 == 0 && rr_aligned16(src) && rr_aligned16(y) && rr_aligned16(out)))
-    return RR_ERR_ALIGN;                                // (the dropout stream is hashed per aligned group of four elements)
+  // (the dropout stream is hashed per aligned group of four elements)
+  if (!rows_are_chunks(H, {ld_src, ld_y, ld_out}, {src, y, out})) return RR_ERR_ALIGN;
   const int HV = H / 4;
   gather_sum_dropmask_kernel<<<rr_grid_for(n_out * HV, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
       src, ld_src, y, ld_y, idx, n_out, K, HV, H, rr_drop_threshold(drop_p), drop_seed, scale, out, ld_out);
@@ -950,15 +924,8 @@ int rr_gather_sum_csr_f32(const float* src, int64_t n_src, int64_t ld_src, const
   RR_CHECK_ARG(src && offsets && out && n_src >= 0 && n_out >= 0 && H >= 1 && ld_src >= H && ld_out >= H);
   if (n_out == 0) return RR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(src) && rr_aligned16(out);
-  if (vec) {
-    const int HV = H / 4;
-    gather_sum_csr_kernel<4><<<rr_grid_for(n_out * HV, 256), 256, 0, s>>>(src, ld_src, offsets, idx, n_out, HV, out,
-                                                                          ld_out);
-  } else {
-    gather_sum_csr_kernel<1><<<rr_grid_for(n_out * H, 256), 256, 0, s>>>(src, ld_src, offsets, idx, n_out, H, out,
-                                                                         ld_out);
-  }
+  const bool vec = rows_are_chunks(H, {ld_src, ld_out}, {src, out});
+  RR_LAUNCH_ROWS(vec, gather_sum_csr_kernel, n_out, H, false, s, src, ld_src, offsets, idx, n_out, W, out, ld_out);
   return rr_launch_status();
 }
 
@@ -969,16 +936,8 @@ int rr_gather_diff_f32(const float* a, int64_t n_a, int64_t ld_a, const int32_t*
                ld_m >= H && ld_out >= H);
   if (n_out == 0) return RR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool vec = (H % 4 == 0) && (ld_a % 4 == 0) && (ld_m % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(a) &&
-                   rr_aligned16(m) && rr_aligned16(out);
-  if (vec) {
-    const int HV = H / 4;
-    gather_diff_kernel<4><<<rr_grid_for(n_out * HV, 256), 256, 0, s>>>(a, ld_a, ia, m, ld_m, im, n_out, HV, out,
-                                                                       ld_out);
-  } else {
-    gather_diff_kernel<1><<<rr_grid_for(n_out * H, 256), 256, 0, s>>>(a, ld_a, ia, m, ld_m, im, n_out, H, out,
-                                                                      ld_out);
-  }
+  const bool vec = rows_are_chunks(H, {ld_a, ld_m, ld_out}, {a, m, out});
+  RR_LAUNCH_ROWS(vec, gather_diff_kernel, n_out, H, false, s, a, ld_a, ia, m, ld_m, im, n_out, W, out, ld_out);
   return rr_launch_status();
 }
 
@@ -996,14 +955,9 @@ int rr_gather_dropout_amax_f32(const float* src, int64_t n_src, int64_t ld_src, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t thr = rr_drop_threshold(drop_p);
   const float ks = 1.0f / (1.0f - drop_p);
-  const bool vec = (H % 4 == 0) && (ld_src % 4 == 0) && (ld_out % 4 == 0) && rr_aligned16(src) && rr_aligned16(out);
-  if (vec) {
-    gather_dropout_kernel<4><<<rr_grid_for(n_out * (H / 4), 256), 256, 0, s>>>(src, ld_src, idx, n_out, H / 4, H, thr, ks,
-                                                                             drop_seed, out, ld_out, amax_out);
-  } else {
-    gather_dropout_kernel<1><<<rr_grid_for(n_out * H, 256), 256, 0, s>>>(src, ld_src, idx, n_out, H, H, thr, ks,
-                                                                         drop_seed, out, ld_out, amax_out);
-  }
+  const bool vec = rows_are_chunks(H, {ld_src, ld_out}, {src, out});
+  RR_LAUNCH_ROWS(vec, gather_dropout_kernel, n_out, H, false, s, src, ld_src, idx, n_out, W, H, thr, ks, drop_seed, out, ld_out,
+                 amax_out);
   return rr_launch_status();
 }
 
@@ -1041,7 +995,7 @@ int rr_weighted_colsum_f32(const float* x, int64_t n, int64_t ld, const float* w
   int64_t rpb = (n + nb - 1) / nb;
   if (rpb < 1) rpb = 1;
   float* partial = static_cast<float*>(workspace);
-  const bool vec = (H % 4 == 0) && (ld % 4 == 0) && rr_aligned16(x) && rr_aligned16(workspace);
+  const bool vec = rows_are_chunks(H, {ld}, {x, workspace});
   const int Hp = (H + 3) / 4 * 4;
   if (vec) colsum_partial_kernel<4><<<nb, 256, 0, s>>>(x, n, ld, w, H, rpb, partial);
   else colsum_partial_kernel<1><<<nb, 256, 0, s>>>(x, n, ld, w, H, rpb, partial);
@@ -1080,8 +1034,8 @@ int rr_segment_mean_bwd_masked_amax_f32(const float* dout, int64_t ld_dout, cons
   RR_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
   RR_CHECK_ARG((mask || mask_bits) && (!mask || ld_mask >= H));
   if (n_atoms == 0) return RR_OK;
-  if (!(H % 4 == 0 && ldx % 4 == 0 && rr_aligned16(dx))) return RR_ERR_ALIGN;
-  if (!mask_bits && !(ld_mask % 4 == 0 && rr_aligned16(mask))) return RR_ERR_ALIGN;
+  if (!rows_are_chunks(H, {ldx}, {dx})) return RR_ERR_ALIGN;
+  if (!mask_bits && !rows_are_chunks(H, {ld_mask}, {mask})) return RR_ERR_ALIGN;
   // (A two-launch form - the per-molecule division and dropout once per molecule, then a K = 1 masked gather over
   // atom2mol - was measured in round 4: +0.2 % on the step.  This kernel writes 86 MB at 71k atoms in ~45 us, within
   // 1.6x of the write-only HBM rate, so its per-atom arithmetic is not what the step waits for.)
@@ -1099,7 +1053,7 @@ int rr_segment_mean_bwd_f32(const float* dout, int64_t ld_dout, const int32_t* a
   if (n_atoms == 0) return RR_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint32_t thr = rr_drop_threshold(drop_p);
-  if (H % 4 == 0 && ldx % 4 == 0 && rr_aligned16(dx)) {
+  if (rows_are_chunks(H, {ldx}, {dx})) {
     segment_mean_bwd_vec_kernel<<<rr_grid_for(n_atoms * (H / 4), 256), 256, 0, s>>>(
         dout, ld_dout, a_scope, atom2mol, n_atoms, H / 4, H + F, thr, 1.0f / (1.0f - drop_p), drop_seed, dx, ldx,
         nullptr, 0, nullptr, 0, 1.0f, nullptr);

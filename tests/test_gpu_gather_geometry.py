@@ -314,6 +314,46 @@ def test_gather_sum_dropmask_and_multi_over_the_geometry_classes(name):
               f"rr_gather_sum_multi_f32 {name} n_srcs={n_srcs} K={Km}")
 
 
+_EVERY_K = [1, 2, 3, 4, 5, 6, 7, 8, 9]                   # every K % 4, with and without a full group of four
+
+
+@pytest.mark.parametrize("name,K", [(n, K) for n in ("plain_h300", "one_wg_h300_n3") for K in _EVERY_K] +
+                         [("plain_h30_scalar", K) for K in (3, 4, 7)])
+def test_gather_sum_masked_at_every_pad_width_remainder(name, K):
+    """gather_row_sum's groups of four and its one-by-one remainder as gather_sum_masked_kernel<4> runs them (a source chunk and
+    a mask chunk per entry), and the scalar kernel at a remainder, a whole group and both."""
+    H, n_out, g = _geometry(name)
+    src_h, mask_h, idx_h = _src(H), np.maximum(_src(H, seed=1), 0), _idx(n_out, K, 13 * K + n_out % 83)
+    _bits(Fn.gather_sum_masked(dev(src_h), dev(mask_h), 1.0 / 0.9, dev(idx_h), H), R.gather_sum_masked(src_h, mask_h, 1.0 / 0.9, idx_h, H),
+          f"rr_gather_sum_masked_f32 {name} K={K}")
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1])
+@pytest.mark.parametrize("K", _EVERY_K)
+@pytest.mark.parametrize("name", ["plain_h300", "one_wg_h300_n3"])
+def test_gather_sum_dropmask_at_every_pad_width_remainder(name, K, p):
+    """The same loop with gather_sum_dropmask_kernel's derived mask: its term also sees the entry's index (pads are off, the keep
+    bits are those of source row j), with the dropout stream and without (threshold 0)."""
+    H, n_out, g = _geometry(name)
+    seed = 0x5EED5EED77
+    src_h, idx_h = _src(H), _idx(n_out, K, 17 * K + n_out % 79)
+    y_h = np.maximum(np.random.default_rng(n_out + K).standard_normal((n_out, H)), 0).astype(np.float32)
+    _bits(Fn.gather_sum_dropmask(dev(src_h), dev(y_h), 1.0 / 0.9, dev(idx_h), H, p, seed),
+          R.gather_sum_dropmask(src_h, y_h, 1.0 / 0.9, idx_h, H, p, seed), f"rr_gather_sum_dropmask_f32 {name} K={K} p={p}")
+
+
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 5])
+@pytest.mark.parametrize("n_srcs", [2, 3, 4])
+def test_gather_sum_multi_at_every_source_count_and_pair_remainder(n_srcs, K):
+    """gather_sum_multi_kernel<NS>: two rows x NS loads in flight, (acc + t0) + t1 per pair and an odd last entry - every source
+    count with no pair, whole pairs only, and pairs with a remainder."""
+    H, n_out, g = _geometry("plain_h300")
+    srcs_h = [_src(H, seed=s) for s in range(n_srcs)]
+    idx_h = _idx(n_out, K, 19 * K + n_srcs)
+    _bits(Fn.gather_sum_multi([dev(s) for s in srcs_h], dev(idx_h), H), R.gather_sum_multi(srcs_h, idx_h, H),
+          f"rr_gather_sum_multi_f32 n_srcs={n_srcs} K={K}")
+
+
 # ------------------------------------------------------------------------------------------------ rr_gather_sum_csr_f32
 def _csr_table(n_out, rng, big=1000):
     """Row source counts cycling through 0, 1, 2, 3, 4 with one row of `big` sources; the first and the last row are empty."""
