@@ -25,6 +25,10 @@ method='distribution').
 calibration set and reports on the other half (uncertainty.evaluate_calibration): the fitted sigma scale with the pointwise
 calibration before and after it, the top-1 calibration of p_top1, and the conformal top-1 sets at --alpha.  A distributional
 head is read with method='distribution', any other with MC dropout.
+
+--attribute grad_x_input | integrated_gradients [--ig-steps N] (listwise task types, one process) explains the first validation
+query's predicted top candidate (attribution.attribute): the five product atoms and three bonds of largest |attribution|, the
+attributions' total next to the score and, for integrated gradients, the gap that is left.
 """
 import argparse
 import logging
@@ -37,7 +41,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import ranknet_baseline, uncertainty             # noqa: E402
+from reactranker_amd import attribution, ranknet_baseline, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -74,6 +78,24 @@ def halves(b):
         out.append(dict(r=featurization.BatchMolGraph(b["mols_r"][ms], K=4), p=featurization.BatchMolGraph(b["mols_p"][ms], K=4),
                         scope=list(b["scope"][qs]), targets=b["targets"][ms], add=b["add"][ms]))
     return out
+
+
+def explain_top_candidate(model, b, method, steps, gpu, log):
+    """The atoms and bonds of the product that moved the score of the first query's predicted top candidate."""
+    res = attribution.attribute(model, b["r"], b["p"], b["add"], column=0, method=method, steps=steps, gpu=gpu)
+    n0 = int(b["scope"][0])
+    top = int(torch.argmax(res["score"][:n0]))
+    start, size = b["p"].a_scope[top]
+    b_start, b_size = b["p"].b_scope[top]
+    atom = res["atom_p"][start:start + size].cpu().numpy()
+    sym = res["bond_sym_p"][b_start:b_start + b_size].cpu().numpy()[0::2]        # one number per undirected bond
+    edges = b["mols_p"][top].edges
+    log.info("attribution (%s) of candidate %d of query 0: score %.5f, total %.5f%s", method, top, float(res["score"][top]),
+             float(res["total"][top]), f", gap {float(res['gap'][top]):.2e}" if "gap" in res else "")
+    for i in np.argsort(-np.abs(atom))[:5]:
+        log.info("  atom %2d  %+.5f", int(i), float(atom[i]))
+    for e in np.argsort(-np.abs(sym))[:3]:
+        log.info("  bond %2d-%-2d  %+.5f", int(edges[e][0]), int(edges[e][1]), float(sym[e]))
 
 
 PAIRWISE = {   # --task-type -> (train_strategy or None = --train-strategy, run_train's task_type)
@@ -120,6 +142,9 @@ def main():
                     "of the validation queries and report on the other half")
     ap.add_argument("--alpha", type=float, default=0.1, help="with --evaluate-calibration: the top-1 sets miss the best candidate with "
                     "probability at most alpha")
+    ap.add_argument("--attribute", choices=attribution.METHODS, default=None, help="listwise task types: after training, which atoms "
+                    "and bonds moved the score of the first validation query's predicted top candidate")
+    ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(message)s")
@@ -198,6 +223,8 @@ def main():
                  t1["confidence"], t1["ece"], t1["brier"])
         log.info("conformal top-1 sets at alpha %.2f: tau %.4f, coverage %.3f, mean set size %.2f of %.2f candidates", args.alpha,
                  res["tau"], res["coverage"], res["mean_set_size"], float(np.mean(res["scope"])))
+    if world == 1 and args.attribute:
+        explain_top_candidate(model, val_b[0], args.attribute, args.ig_steps, args.gpu, log)
     if world > 1:
         dist.destroy_process_group()
 

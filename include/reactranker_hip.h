@@ -906,6 +906,54 @@ int rr_top1_sets_f32(const float* p, int64_t p_stride, const float* targets, con
 int rr_top1_sets_waves(void);
 int rr_top1_sets_set_waves(int waves);
 
+/* Atom / bond attributions (additive: three new symbols, the ABI revision stays 8).  This library's own definition.
+ * The adjoint of a layer's FIRST linear map, fused with the product by the layer's input and a per-row reduction over column
+ * segments, so the dense input gradient need not be written:
+ *   dX[m,k]   = sum_n dz[m,n] * w[n,k]  (+ add[add_idx[m], k] when add != NULL)        m < M, k < K, n < N
+ *   attr[m,s] (+)= alpha * sum_{k in segment s} x[m,k] * dX[m,k]                        when attr != NULL (x required)
+ *   dx[m,k]   (+)= alpha * dX[m,k]                                                      when dx != NULL
+ * dz [M,N] (ld_dz), w [N,K] (ld_w: the torch Linear.weight layout; a column window of a wider weight is a pointer offset plus
+ * ld_w), x [M,K] (ld_x), add [*,K] (ld_add) indexed through add_idx (int32 [M], device; every entry must name a row of add),
+ * attr [M,n_seg] (ld_attr), dx [M,K] (ld_dx); all f32 device memory.  seg_end: HOST array of n_seg <= RR_ATTR_MAX_SEG ascending
+ * column ends, the last equal to K (read only when attr != NULL).  accumulate (0 / 1) applies to both outputs.
+ * K <= RR_ATTR_MAX_K (RR_ERR_UNSUPPORTED above); N >= 1 is any value; M == 0 returns RR_OK without a launch; any leading
+ * dimension >= the logical width is accepted (16-byte loads are used where a pointer and its pitch allow, 4-byte loads
+ * otherwise - same values).  The bytes between the logical width and the pitch of an operand never reach a result.
+ * Arithmetic: f32 throughout on v_mfma_f32_16x16x4_f32 (one rounding per product); the chain of dX[m,k] runs over n in tiles
+ * of 16 ascending, inside a tile n = 16 t + 4 q + j for j = 0..3 (outer), q = 0..3 (inner); then + add; a segment sum is four
+ * per-lane chains over the columns 16 kt + 4 q + e (kt, then e ascending; q = 0..3 the lane) joined as (q0 + q1) + (q2 + q3)
+ * - no atomics, and a row's bits depend on that row's operands and (N, K, segments) only: not on M, not on the row's position.
+ * Status: RR_ERR_ARG for a null dz / w, both outputs null, attr without x or seg_end, add without add_idx (or the reverse),
+ * seg_end not strictly ascending or not ending at K, n_seg outside [1, 4], a leading dimension below its width, M < 0,
+ * N < 1, K < 1 or accumulate outside {0, 1} - all before any launch.
+ *   rr_input_attribution_max_k   RR_ATTR_MAX_K as the library was compiled (the Python layer checks its widths against it) */
+#define RR_ATTR_MAX_K 128
+#define RR_ATTR_MAX_SEG 4
+int rr_input_attribution_f32(const float* dz, int64_t ld_dz, const float* w, int64_t ld_w, const float* x, int64_t ld_x,
+                             const float* add, int64_t ld_add, const int32_t* add_idx, int64_t M, int N, int K,
+                             const int32_t* seg_end, int n_seg, float alpha, int accumulate, float* attr, int64_t ld_attr,
+                             float* dx, int64_t ld_dx, rr_stream_t stream);
+int rr_input_attribution_max_k(void);
+
+/* The finish of an attribution: per-row terms -> atom, bond and molecule numbers of one packed graph.
+ *   attr_fa [nA] (element a at attr_fa[a * ld_fa]): the atom's own term (the W_o call)
+ *   attr_fb [nB,2] (ld_fb >= 2): per directed bond, column 0 the source-atom columns' term, column 1 the bond columns' term
+ *   a2b [nA,K] (incoming bonds, right-padded with bond 0), b2revb [nB], a_scope [M,2] (first atom, atom count) - the packer's
+ *   atom[a]      = attr_fa[a] + attr_fb[b2revb[a2b[a,0]], 0] + ... + attr_fb[b2revb[a2b[a,K-1]], 0]: one f32 chain in column
+ *                  order (the bonds that LEAVE a are the reverses of its incoming ones; a padding entry names bond 0, whose
+ *                  row is zero because f_bonds row 0 is)
+ *   bond[b]      = attr_fb[b,1]                 bond_sym[b] = bond[b] + bond[b2revb[b]]
+ *   mol_total[m] = f64: 0.0 + c_a for the molecule's atoms in ascending order, c_a = (double)atom[a] + (double)bond[b] over the
+ *                  real (non-padding) entries of a2b[a,:] in column order, b = b2revb[a2b[a,k]]
+ * One wavefront per molecule, lane = atom (strided); workgroup 0 also writes atom 0 / bond 0 (the padding rows).  A directed
+ * bond leaves exactly one atom, so every output element is written once.  No atomics: bit-reproducible.  An index outside
+ * its table reads row 0 instead (values change, never an address).
+ * Status: RR_ERR_ARG for a null pointer (a_scope / mol_total may be null when M == 0), nA < 1, nB < 1, M < 0, K < 1,
+ * ld_fa < 1 or ld_fb < 2. */
+int rr_attribution_reduce_f32(const float* attr_fa, int64_t ld_fa, const float* attr_fb, int64_t ld_fb, const int32_t* a2b,
+                              const int32_t* b2revb, const int32_t* a_scope, int64_t nA, int64_t nB, int64_t M, int K,
+                              float* atom, float* bond, float* bond_sym, double* mol_total, rr_stream_t stream);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

@@ -294,6 +294,11 @@ _SIGS = {
                                c_stream]),
     "rr_top1_sets_waves": (i32, []),
     "rr_top1_sets_set_waves": (i32, [i32]),
+    "rr_input_attribution_f32": (i32, [c_f32p, i64, c_f32p, i64, c_f32p, i64, c_f32p, i64, c_i32p, i64, i32, i32, C.c_void_p, i32,
+                                       f32, i32, c_f32p, i64, c_f32p, i64, c_stream]),
+    "rr_input_attribution_max_k": (i32, []),
+    "rr_attribution_reduce_f32": (i32, [c_f32p, i64, c_f32p, i64, c_i32p, c_i32p, c_i32p, i64, i64, i64, i32, c_f32p, c_f32p,
+                                        c_f32p, C.c_void_p, c_stream]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
