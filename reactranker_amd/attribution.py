@@ -234,7 +234,7 @@ def _fbs_route(pg):
     """add_idx of the product graph's W_i call: bond b receives d fb_sum of its TARGET atom; bond 0 (the padding bond) the
     extra row nA (see _diff_input_backward).  Cached on nothing: a [nB] int32 copy per call."""
     idx = pg.b2t.reshape(-1).clone()
-    idx[0] = pg.nA
+    idx[:1].fill_(pg.nA)                           # (idx[0] = ... copies a host scalar and blocks the host on the caller's stream)
     return idx
 
 

@@ -954,28 +954,48 @@ class _WorkspacePool:
     """Workspaces of the step plans (one ~2 GB buffer per step, live from forward to backward).  The steps of an epoch
     differ in size by a few per cent; asking the caching allocator for a new size every step costs a fresh hipMalloc
     (~80-180 ms) whenever no cached block fits.  The pool hands a returned buffer to the next step if it is large enough
-    and allocates with 25 % headroom otherwise, so it stops growing after the first steps.  Reuse is stream-ordered like
-    the allocator's own: a buffer comes back after its backward was enqueued, and that backward joins the library's
-    side streams to the caller's stream before it returns."""
+    and allocates with 25 % headroom otherwise, so it stops growing after the first steps.
+
+    Reuse is stream-ordered like the allocator's own, which means PER STREAM: a buffer comes back as soon as its backward
+    (or its forward, when no input wants a gradient) was ENQUEUED on the caller's stream - that call joins the library's side streams to the
+    caller's stream before it returns, but nothing has run yet.  Only work enqueued later on that same stream is ordered
+    behind it, so give() remembers the stream it was called under (as `_rr_stream` on the tensor, the way `_rr_bits` rides
+    on a mask) and take() hands a buffer out only under the same device AND stream.  Buffers of other streams are left
+    alone - neither handed out nor dropped on a miss - until the cap of four evicts the oldest of them."""
     free: List[torch.Tensor] = []
     allocs = 0               # buffers allocated so far (bench.py: none should fall inside a timed region)
 
+    @staticmethod
+    def stream_key(device) -> int:
+        """handle of the caller's stream on `device` (0 where the device has no streams: the CPU tensors of the host tests)"""
+        device = torch.device(device)
+        return int(torch.cuda.current_stream(device).cuda_stream) if device.type == "cuda" else 0
+
     @classmethod
     def take(cls, nbytes: int, device) -> torch.Tensor:
+        key = cls.stream_key(device)
+
+        def mine(t):
+            return t.device == device and getattr(t, "_rr_stream", 0) == key
         best = None
         for i, t in enumerate(cls.free):
-            if t.device == device and t.numel() >= nbytes and (best is None or t.numel() < cls.free[best].numel()):
+            if mine(t) and t.numel() >= nbytes and (best is None or t.numel() < cls.free[best].numel()):
                 best = i
         if best is not None:
             return cls.free.pop(best)
-        cls.free = [t for t in cls.free if t.device != device]          # too small for this model now: let them go
+        cls.free = [t for t in cls.free if not mine(t)]                 # too small for this model now: let them go
         cls.allocs += 1
         return torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=device)
 
     @classmethod
     def give(cls, t: torch.Tensor) -> None:
-        if len(cls.free) < 4:
-            cls.free.append(t)
+        t._rr_stream = key = cls.stream_key(t.device)
+        if len(cls.free) >= 4:                                           # full: only another stream's buffer makes room
+            old = next((i for i, q in enumerate(cls.free) if q.device != t.device or getattr(q, "_rr_stream", 0) != key), None)
+            if old is None:
+                return
+            cls.free.pop(old)
+        cls.free.append(t)
 
 
 class StepPlan:
