@@ -95,9 +95,10 @@ __global__ void __launch_bounds__(256) axpby_kernel(float alpha, const float* __
       if (b) r = r + reinterpret_cast<const f32x4*>(b)[i] * beta;
       reinterpret_cast<f32x4*>(out)[i] = r;
     }
-    for (int64_t i = n4 * 4 + t0; i < n; i += stride) out[i] = alpha * a[i] + (b ? beta * b[i] : 0.f);
+    // (b == nullptr: no add at all, as in the body above - alpha * a + 0.f would turn a product of -0 into +0)
+    for (int64_t i = n4 * 4 + t0; i < n; i += stride) out[i] = b ? alpha * a[i] + beta * b[i] : alpha * a[i];
   } else {
-    for (int64_t i = t0; i < n; i += stride) out[i] = alpha * a[i] + (b ? beta * b[i] : 0.f);
+    for (int64_t i = t0; i < n; i += stride) out[i] = b ? alpha * a[i] + beta * b[i] : alpha * a[i];
   }
 }
 
