@@ -95,6 +95,43 @@ int rr_gather_sum_dropmask_f32(const float* src, int64_t n_src, int64_t ld_src, 
                                const int32_t* idx, int64_t n_out, int K, int H, float drop_p, uint64_t drop_seed,
                                float scale, float* out, int64_t ld_out, rr_stream_t stream);
 
+/* rr_gather_sum_epi_f32 without a mask or addends into an intermediate [n_mid, H], then rr_gather_sum_dropmask_f32 over that
+ * intermediate - in one pass that never stores the intermediate (additive to ABI revision 8):
+ *   inner(j, c) = ((0 + src[in_idx[j*Ki + 0], c]) + src[in_idx[j*Ki + 1], c]) + ...      negative entry: the +0.0 chunk
+ *   out[u, c]   = ((0 + t(j_0)) + t(j_1)) + ...,   j_t = out_idx[u*Ko + t]
+ *   t(j)        = (j >= 0 && kept(drop_seed, j * H + c) && y[u, c] > 0) ? inner(j, c) * scale : 0
+ * The same additions and products in the same order as the two launches, so the result equals theirs bit for bit.  The
+ * shared-prefix reactant backward forms d message of every copy only to sum it over the copies: this removes the write and the
+ * read of that [copies, H] tensor.  in_idx is [n_mid, Ki] with values < n_src, out_idx is [n_out, Ko] with values < n_mid,
+ * y is [n_out, ld_y].
+ * row0_partial (may be NULL): as in rr_gather_sum_padrow_f32, intermediate row 0 is the fixed-order sum of the n_partial
+ * partial rows instead of a gather.  PRECONDITION with row0_partial: intermediate row 0 is named by OUTPUT ROW 0 ONLY
+ * (the packer's transposed copy table starts with the row [0, -1, ...] and lists copy row 0 nowhere else); any other output
+ * row that names it gets the gathered row 0, not the partials' sum.  Needs n_out >= 1.
+ * Writes out[u, 0:H] for every u < n_out and nothing else: columns H .. ld_out of a pitched `out` keep what they held.  No
+ * scratch.  Needs H % 4 == 0 and 16-byte aligned pointers and pitches (RR_ERR_ALIGN otherwise). */
+int rr_gather2_sum_dropmask_f32(const float* src, int64_t n_src, int64_t ld_src, const int32_t* in_idx, int64_t n_mid, int Ki,
+                                const float* row0_partial, int64_t n_partial, int64_t ld_partial,
+                                const float* y, int64_t ld_y, const int32_t* out_idx, int64_t n_out, int Ko, int H,
+                                float drop_p, uint64_t drop_seed, float scale, float* out, int64_t ld_out,
+                                rr_stream_t stream);
+
+/* rr_gather_dropout_f32(y, map, ..., drop_p, drop_seed) into copies [n_map, H], then rr_gather_sum_f32 over the copies -
+ * without reading (or needing) the copies (additive to ABI revision 8):
+ *   out[a, c] = ((0 + v(j_0)) + v(j_1)) + ...,   j_k = idx[a*K + k]
+ *   v(j)      = j < 0 ? +0 : ( kept(drop_seed, j * H + c) ? y[map[j], c] / (1 - drop_p) : 0 )       (map[j] < 0: the zero row)
+ * Every v(j) is bit for bit the element rr_gather_dropout_f32 stores in row j, so the sum equals rr_gather_sum_f32's over the
+ * materialised tensor.  Row 0 is an ordinary row.  map is [n_map] with values < n_y, idx is [n_out, K] with values < n_map.
+ * In the shared-prefix reactant forward the first per-copy layer's atom sums could be formed from the distinct bonds'
+ * activations this way.  The step plans do NOT use it: at the headline shape it takes 52 us stand-alone against 44 us of
+ * rr_gather_sum_f32 over the copies, which rr_gather_dropout_amax_f32 has to write anyway for the GEMM and the weight gradient
+ * (profiles/prefix_fuse_ab.txt).  It is kept as a tested library entry for callers that do not materialise the copies.
+ * Writes out[a, 0:H] for every a < n_out and nothing else: pad columns of a pitched `out` keep what they held.  No scratch.
+ * Needs H % 4 == 0 and 16-byte aligned pointers and pitches (RR_ERR_ALIGN otherwise). */
+int rr_gather_sum_dropsrc_f32(const float* y, int64_t n_y, int64_t ld_y, const int32_t* map, int64_t n_map,
+                              const int32_t* idx, int64_t n_out, int K, int H, float drop_p, uint64_t drop_seed,
+                              float* out, int64_t ld_out, rr_stream_t stream);
+
 /* The sum over idx of a tensor that is itself a sum of n_srcs tensors of one shape (ABI revision 8):
  *   out[r, :] = sum_{k<K, j = idx[r*K+k] >= 0} ( ((srcs[0][j, :] + srcs[1][j, :]) + srcs[2][j, :]) + ... )
  * In the shared-prefix reactant backward a copy's d input is the sum of the dZ of every per-copy layer (models/mpn.py:94-97)

@@ -179,6 +179,9 @@ _SIGS = {
                                              c_f32p, i64, c_f32p, c_stream]),
     "rr_gather_sum_masked_f32": (i32, [c_f32p, c_f32p, i64, i64, c_i32p, i64, i32, i32, f32, c_f32p, i64, c_stream]),
     "rr_gather_sum_dropmask_f32": (i32, [c_f32p, i64, i64, c_f32p, i64, c_i32p, i64, i32, i32, f32, u64, f32, c_f32p, i64, c_stream]),
+    "rr_gather2_sum_dropmask_f32": (i32, [c_f32p, i64, i64, c_i32p, i64, i32, c_f32p, i64, i64, c_f32p, i64, c_i32p, i64, i32, i32,
+                                          f32, u64, f32, c_f32p, i64, c_stream]),
+    "rr_gather_sum_dropsrc_f32": (i32, [c_f32p, i64, i64, c_i32p, i64, c_i32p, i64, i32, i32, f32, u64, c_f32p, i64, c_stream]),
     "rr_gather_sum_csr_f32": (i32, [c_f32p, i64, i64, c_i32p, c_i32p, i64, i32, c_f32p, i64, c_stream]),
     "rr_build_fbonds_f32": (i32, [c_f32p, i64, i64, i32, c_i32p, c_f32p, i64, i32, i64, c_f32p, i64, c_stream]),
     "rr_gather_diff_f32": (i32, [c_f32p, i64, i64, c_i32p, c_f32p, i64, i64, c_i32p, i64, i32, c_f32p, i64, c_stream]),

@@ -366,6 +366,230 @@ __global__ void __launch_bounds__(256) gather_sum_multi_kernel(GatherSrcs S, int
   }
 }
 
+// ------------------------------------------------------------------------ the shared-prefix pass without [copies, H] round trips
+// An index entry that may not be read (past the table row's end, or under a negative row) loads this instead: the pointer is
+// selected, the load is unconditional (see ld_row).
+__device__ const int32_t gather_none[1] = {-1};
+
+// gather_sum_dropmask_kernel over an intermediate that is itself a gather-sum and is never stored:
+//   inner(j, c) = ((0 + src[in_idx[j,0], c]) + src[in_idx[j,1], c]) + ...        what the unmasked gather_sum_epi_kernel<0> stores in row j
+//   out[u, c]   = ((0 + t(j_0)) + t(j_1)) + ...,  j_t = out_idx[u, t],  t(j) = gather_sum_dropmask_kernel's term of inner(j, c)
+// The shared-prefix backward forms d message of every copy [copies, H] only to sum it over the copies in the next launch: that
+// tensor is written once and read once.  Here the thread that owns (u, c) forms the inner sums of its copies itself, G2 copies
+// in flight together (their index rows, then all their source rows), and adds the terms in table order - the additions,
+// products and order of the two launches, so every bit is the same.  A table position past Ko counts as a negative entry:
+// its term is +0.0 and acc is never -0.0 (it starts from +0.0), so acc + 0 leaves every bit alone.
+// Intermediate row 0 is the padding row: with row0_partial it is padrow_sum's tree over the GEMM's column-sum partials, not a
+// gather.  Then HV more blocks follow the gather blocks; block g of them forms inner(0, 4g) that way and its thread 0 walks
+// output row 0's table row (row 0 by the partials, anything else by the gather) - the other blocks skip output row 0.
+// PRECONDITION: intermediate row 0 is named by output row 0 only.
+// KI: the inner pad width, 1..4 unrolled; 0: a run-time loop per copy (gather_plain_sum).
+constexpr int G2 = 8;
+struct Gather2 {
+  const float* src;        int64_t ld_src;
+  const int32_t* in_idx;   int Ki;
+  const float* y;          int64_t ld_y;
+  const int32_t* out_idx;  int64_t n_out; int Ko;
+  int HV, H;
+  uint32_t thr; uint64_t seed; float scale;
+  float* out;              int64_t ld_out;
+  const float* row0_partial; int64_t n_partial, ld_partial;
+};
+// gather_sum_dropmask_kernel's term (mask > 0 ? v * scale : 0) in two steps: which of the chunk's four elements pass - copy
+// row j is real, its keep bit is set, y > 0 - depends on no gathered value, so a thread works it out (two hash levels: most of
+// this kernel's arithmetic) while its row loads are in flight; mask_select then forms the same products.
+__device__ __forceinline__ uint32_t dropmask_bits(const Gather2& A, int32_t j, int c, f32x4 yv) {
+  uint32_t w = 0u;
+  if (A.thr != 0u) w = rr_hash_group(A.seed, (static_cast<uint64_t>(j < 0 ? 0 : j) * static_cast<uint64_t>(A.H) + static_cast<uint64_t>(c)) >> 2);
+  uint32_t nib = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const bool keep = A.thr == 0u || rr_hash_lane(w, q) >= A.thr;
+    if (j >= 0 && keep && yv[q] > 0.f) nib |= 1u << q;
+  }
+  return nib;
+}
+__device__ __forceinline__ f32x4 dropmask_term(const Gather2& A, int32_t j, int c, f32x4 yv, f32x4 v) {
+  return mask_select(v, dropmask_bits(A, j, c, yv), A.scale);
+}
+template <int KI>
+__global__ void __launch_bounds__(256) gather2_sum_dropmask_kernel(const Gather2 A) {
+  const int HV = A.HV, Ko = A.Ko, Ki = A.Ki;
+  const int64_t total = A.n_out * HV;
+  const int gblocks = A.row0_partial ? static_cast<int>(gridDim.x) - HV : static_cast<int>(gridDim.x);
+  if (A.row0_partial != nullptr && static_cast<int>(blockIdx.x) >= gblocks) {
+    const int c = (static_cast<int>(blockIdx.x) - gblocks) * 4;
+    padrow_sum<4>(A.row0_partial, A.n_partial, A.ld_partial, c, [&](f32x4 pad) {
+      const f32x4 yv = ld<4>(A.y + c);
+      f32x4 acc = f32x4(0.0f);
+      for (int t = 0; t < Ko; ++t) {
+        const int32_t j = A.out_idx[t];
+        f32x4 inner = pad;
+        if (j > 0) inner = gather_plain_sum<4>(A.src, A.ld_src, A.in_idx + static_cast<int64_t>(j) * Ki, Ki, c);
+        acc = acc + dropmask_term(A, j, c, yv, inner);
+      }
+      st<4>(A.out + c, acc);
+    });
+    return;
+  }
+  RR_GATHER_LOOP(e, gblocks, total) {
+    const int64_t r = e / HV;
+    const int c = static_cast<int>(e - r * HV) * 4;
+    if (r == 0 && A.row0_partial != nullptr) continue;  // written by the reduction blocks
+    const int32_t* orow = A.out_idx + r * Ko;
+    const f32x4 yv = ld<4>(A.y + r * A.ld_y + c);
+    f32x4 acc = f32x4(0.0f);
+    if constexpr (KI > 0) {
+      int32_t jn[G2];
+#pragma unroll
+      for (int g = 0; g < G2; ++g) jn[g] = *(g < Ko ? orow + g : gather_none);
+      for (int t = 0; t < Ko; t += G2) {
+        int32_t j[G2];
+#pragma unroll
+        for (int g = 0; g < G2; ++g) {                  // this group's copies; the next group's are fetched under its loads
+          j[g] = jn[g];
+          jn[g] = *(t + G2 + g < Ko ? orow + (t + G2 + g) : gather_none);
+        }
+        int32_t i[G2][KI];
+#pragma unroll
+        for (int g = 0; g < G2; ++g)
+#pragma unroll
+          for (int k = 0; k < KI; ++k) i[g][k] = *(j[g] >= 0 ? A.in_idx + static_cast<int64_t>(j[g]) * KI + k : gather_none);
+        f32x4 v[G2][KI];
+#pragma unroll
+        for (int g = 0; g < G2; ++g)
+#pragma unroll
+          for (int k = 0; k < KI; ++k) v[g][k] = ld_row<4>(A.src, A.ld_src, i[g][k], c);
+        uint32_t nib[G2];
+#pragma unroll
+        for (int g = 0; g < G2; ++g) nib[g] = dropmask_bits(A, j[g], c, yv);   // (under the row loads)
+#pragma unroll
+        for (int g = 0; g < G2; ++g) {
+          f32x4 inner = f32x4(0.0f) + v[g][0];
+#pragma unroll
+          for (int k = 1; k < KI; ++k) inner = inner + v[g][k];
+          acc = acc + mask_select(inner, nib[g], A.scale);
+        }
+      }
+    } else {
+      for (int t = 0; t < Ko; ++t) {
+        const int32_t j = orow[t];
+        f32x4 inner = f32x4(0.0f);
+        if (j >= 0) inner = gather_plain_sum<4>(A.src, A.ld_src, A.in_idx + static_cast<int64_t>(j) * Ki, Ki, c);
+        acc = acc + dropmask_term(A, j, c, yv, inner);
+      }
+    }
+    st<4>(A.out + r * A.ld_out + c, acc);
+  }
+}
+
+// out[a] = sum_k drop_j(y[map[j]]),  j = idx[a, k]: gather_sum_kernel over the copies gather_dropout_kernel materialises,
+// without reading them - every addend is re-derived from the small shared tensor y and the copy row's own keep bits (element
+// j * H + c of the stream) by the device functions and the keep_scale gather_dropout_kernel uses, so it is bit for bit the
+// element that kernel stores; summed in table order from +0.0.  A negative table entry adds the zero chunk (dropped or kept,
+// a zero stays +0.0).  KT: the pad width, 1..4 as a walk (all KT rows in flight, the following chunks' index rows and map
+// entries fetched under them); 0: the run-time loop.  Not used by the step plans: 52 us against the 44 us of gather_sum_kernel
+// over the materialised copies at the headline shape (profiles/prefix_fuse_ab.txt).
+struct DropSrc {
+  const float* y;          int64_t ld_y;
+  const int32_t* map;
+  const int32_t* idx;      int64_t n_out; int K;
+  int HV, H;
+  uint32_t thr; float keep_scale; uint64_t seed;
+  float* out;              int64_t ld_out;
+};
+__device__ __forceinline__ f32x4 dropsrc_term(const DropSrc& A, int32_t j, int c, f32x4 v) {
+  if (A.thr != 0u) v = keep_scale4(v, A.seed, static_cast<uint64_t>(j < 0 ? 0 : j) * static_cast<uint64_t>(A.H) + static_cast<uint64_t>(c), A.thr, A.keep_scale);
+  return v;
+}
+template <int KT>
+__global__ void __launch_bounds__(256) gather_sum_dropsrc_kernel(const DropSrc A) {
+  const int HV = A.HV, K = A.K;
+  const int64_t total = A.n_out * HV;
+#ifdef RR_GATHER_WALK
+  if constexpr (KT > 0) {
+    int64_t beg, end;
+    gather_block_range(static_cast<int>(gridDim.x), total, &beg, &end);
+    int64_t e = beg + threadIdx.x;
+    if (e >= end) return;
+    const int quo = 256 / HV, rem = 256 - quo * HV;
+    int64_t r = e / HV;
+    int q = static_cast<int>(e - r * HV);
+    // Three dependent levels per chunk (index row -> map -> rows of y): the chunk after next's index row and the next chunk's
+    // map entries are fetched while this chunk's rows are, so a pass waits for one round trip.  Loads are unconditional from
+    // clamped (valid) positions, the pad is selected afterwards (n_map, n_y >= 1: the host shell).
+    auto next = [&](int64_t& rr, int& qq) {
+      rr += quo;
+      qq += rem;
+      if (qq >= HV) {
+        qq -= HV;
+        ++rr;
+      }
+    };
+    auto maps = [&](const int32_t (&jj)[KT], int32_t (&mm)[KT]) {
+#pragma unroll
+      for (int k = 0; k < KT; ++k) mm[k] = A.map[jj[k] < 0 ? 0 : jj[k]];
+    };
+    int64_t r1 = r;
+    int q1 = q;
+    next(r1, q1);
+    bool has1 = e + 256 < end;
+    int32_t j[KT], m[KT], j1[KT], m1[KT], j2[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) j[k] = A.idx[r * KT + k];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) j1[k] = A.idx[(has1 ? r1 : r) * KT + k];
+    maps(j, m);
+    while (true) {
+      int64_t r2 = r1;
+      int q2 = q1;
+      next(r2, q2);
+      const bool has2 = e + 512 < end;
+#pragma unroll
+      for (int k = 0; k < KT; ++k) j2[k] = A.idx[(has2 ? r2 : r) * KT + k];
+      maps(j1, m1);
+      const int c = q * 4;
+      f32x4 v[KT];
+#pragma unroll
+      for (int k = 0; k < KT; ++k) v[k] = ld<4>(A.y + static_cast<int64_t>((j[k] < 0 || m[k] < 0) ? 0 : m[k]) * A.ld_y + c);
+      f32x4 acc = f32x4(0.0f);
+#pragma unroll
+      for (int k = 0; k < KT; ++k) {
+        // a pad entry skips the keep bits (two hash levels): a row's chunks share a wave, so the branch rarely diverges,
+        // and no load sits under it
+        f32x4 t = f32x4(0.0f);
+        if (j[k] >= 0 && m[k] >= 0) t = dropsrc_term(A, j[k], c, v[k]);
+        acc = acc + t;
+      }
+      st<4>(A.out + r * A.ld_out + c, acc);
+      if (!has1) break;
+      e += 256;
+      r = r1;
+      q = q1;
+      r1 = r2;
+      q1 = q2;
+      has1 = has2;
+#pragma unroll
+      for (int k = 0; k < KT; ++k) {
+        j[k] = j1[k];
+        m[k] = m1[k];
+        j1[k] = j2[k];
+      }
+    }
+    return;
+  }
+#endif
+  RR_GATHER_LOOP(e, static_cast<int>(gridDim.x), total) {
+    const int64_t r = e / HV;
+    const int c = static_cast<int>(e - r * HV) * 4;
+    const f32x4 acc = gather_row_sum<f32x4>(
+        A.idx + r * K, K,
+        [&](int32_t j) { return ld_row<4>(A.y, A.ld_y, *(j >= 0 ? A.map + j : gather_none), c); },
+        [&](int32_t j, f32x4 v) { return dropsrc_term(A, j, c, v); });
+    st<4>(A.out + r * A.ld_out + c, acc);
+  }
+}
+
 // ------------------------------------------------------------------------ gather-sum with a fused epilogue
 // out[r] = mask_r (.) (sum_k src[idx[r,k]]) * scale  +  sum_j adds[j][r]
 // The backward chain never needs a gathered gradient as such: d message of one layer is consumed masked by the ReLU /
@@ -916,6 +1140,61 @@ int rr_gather_sum_dropmask_f32(const float* src, int64_t n_src, int64_t ld_src, 
   const int HV = H / 4;
   gather_sum_dropmask_kernel<<<rr_grid_for(n_out * HV, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(
       src, ld_src, y, ld_y, idx, n_out, K, HV, H, rr_drop_threshold(drop_p), drop_seed, scale, out, ld_out);
+  return rr_launch_status();
+}
+
+int rr_gather2_sum_dropmask_f32(const float* src, int64_t n_src, int64_t ld_src, const int32_t* in_idx, int64_t n_mid, int Ki,
+                                const float* row0_partial, int64_t n_partial, int64_t ld_partial, const float* y, int64_t ld_y,
+                                const int32_t* out_idx, int64_t n_out, int Ko, int H, float drop_p, uint64_t drop_seed,
+                                float scale, float* out, int64_t ld_out, rr_stream_t stream) {
+  RR_CHECK_ARG(src && in_idx && y && out_idx && out && n_src >= 0 && n_mid >= 0 && n_out >= 0 && Ki >= 1 && Ko >= 1 && H >= 1 &&
+               ld_src >= H && ld_y >= H && ld_out >= H);
+  RR_CHECK_ARG(!row0_partial || (n_out >= 1 && n_mid >= 1 && n_partial >= 0 && ld_partial >= H));
+  RR_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
+  bool vec = rows_are_chunks(H, {ld_src, ld_y, ld_out}, {src, y, out});
+  if (row0_partial) vec = vec && rows_are_chunks(H, {ld_partial}, {row0_partial});
+  if (!vec) return RR_ERR_ALIGN;
+  if (n_out == 0) return RR_OK;
+  Gather2 A;
+  A.src = src; A.ld_src = ld_src; A.in_idx = in_idx; A.Ki = Ki; A.y = y; A.ld_y = ld_y; A.out_idx = out_idx; A.n_out = n_out; A.Ko = Ko;
+  A.HV = H / 4; A.H = H; A.thr = rr_drop_threshold(drop_p); A.seed = drop_seed; A.scale = scale; A.out = out; A.ld_out = ld_out;
+  A.row0_partial = row0_partial; A.n_partial = n_partial; A.ld_partial = ld_partial;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int grid = rr_grid_for(n_out * A.HV, 256) + (row0_partial ? A.HV : 0);
+  switch (Ki) {
+    case 1: gather2_sum_dropmask_kernel<1><<<grid, 256, 0, s>>>(A); break;
+    case 2: gather2_sum_dropmask_kernel<2><<<grid, 256, 0, s>>>(A); break;
+    case 3: gather2_sum_dropmask_kernel<3><<<grid, 256, 0, s>>>(A); break;
+    case 4: gather2_sum_dropmask_kernel<4><<<grid, 256, 0, s>>>(A); break;
+    default: gather2_sum_dropmask_kernel<0><<<grid, 256, 0, s>>>(A); break;
+  }
+  return rr_launch_status();
+}
+
+int rr_gather_sum_dropsrc_f32(const float* y, int64_t n_y, int64_t ld_y, const int32_t* map, int64_t n_map, const int32_t* idx,
+                              int64_t n_out, int K, int H, float drop_p, uint64_t drop_seed, float* out, int64_t ld_out,
+                              rr_stream_t stream) {
+  RR_CHECK_ARG(y && map && idx && out && n_y >= 0 && n_map >= 0 && n_out >= 0 && K >= 1 && H >= 1 && ld_y >= H && ld_out >= H);
+  RR_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f);
+  if (!rows_are_chunks(H, {ld_y, ld_out}, {y, out})) return RR_ERR_ALIGN;
+  if (n_out == 0) return RR_OK;
+  DropSrc A;
+  A.y = y; A.ld_y = ld_y; A.map = map; A.idx = idx; A.n_out = n_out; A.K = K; A.HV = H / 4; A.H = H;
+  A.thr = rr_drop_threshold(drop_p); A.keep_scale = 1.0f / (1.0f - drop_p); A.seed = drop_seed; A.out = out; A.ld_out = ld_out;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n_map == 0 || n_y == 0) {                         // nothing to name: every entry is a pad, every sum +0.0 (the walk loads map[0], y[0])
+    if (hipMemset2DAsync(out, static_cast<size_t>(ld_out) * sizeof(float), 0, static_cast<size_t>(H) * sizeof(float),
+                         static_cast<size_t>(n_out), s) != hipSuccess) return RR_ERR_LAUNCH;
+    return RR_OK;
+  }
+  const int grid = rr_grid_for(n_out * A.HV, 256);
+  switch (K) {
+    case 1: gather_sum_dropsrc_kernel<1><<<grid, 256, 0, s>>>(A); break;
+    case 2: gather_sum_dropsrc_kernel<2><<<grid, 256, 0, s>>>(A); break;
+    case 3: gather_sum_dropsrc_kernel<3><<<grid, 256, 0, s>>>(A); break;
+    case 4: gather_sum_dropsrc_kernel<4><<<grid, 256, 0, s>>>(A); break;
+    default: gather_sum_dropsrc_kernel<0><<<grid, 256, 0, s>>>(A); break;
+  }
   return rr_launch_status();
 }
 

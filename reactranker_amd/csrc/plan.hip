@@ -137,6 +137,7 @@ struct Ctx {
   bool ffn_chain = true;              // the FFN head and its input-gradient chain as one launch each (rr_ffn_chain_f32)
   bool timing = false;                // RR_PLAN_TIME: events around the heavy launches
   bool gather_multi = false;          // sums of per-copy tensors ride on the gather over the copies (rr_gather_sum_multi_f32)
+  bool prefix_fuse = false;           // the shared-prefix backward sums over the copies without storing each copy's d message (not with f16)
   bool wgrad_early = false;           // RR_PLAN_WGRAD_EARLY: W_h weight gradients issued in front of the dX GEMM of their layer
   bool tail_pass = false;             // the encoder pass being enqueued is the last one of the backward call (see wgrad)
   bool side_joined = false;           // the chain has waited for the side stream and nothing was put there since
@@ -162,6 +163,7 @@ Ctx make_ctx(int flags, void* workspace, size_t workspace_bytes, bool launch) {
   c.ffn_chain = (flags & RR_PLAN_NO_FFN_CHAIN) == 0 && !getenv("RR_NO_FFN_CHAIN");
   c.timing = (flags & RR_PLAN_TIME) != 0;
   c.gather_multi = !getenv("RR_NO_GATHER_MULTI");
+  c.prefix_fuse = !getenv("RR_NO_PREFIX_FUSE");
   c.wgrad_early = (flags & RR_PLAN_WGRAD_EARLY) != 0 || getenv("RR_WGRAD_EARLY") != nullptr;
   return c;
 }
@@ -534,6 +536,9 @@ void mpn_forward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr_
   S.msgs[1] = c.alloc(g.nB, H);
   S.seed0 = site_seed(seed, 0);
   RR_TRY(c, rr_gather_dropout_amax_f32(S.z1_u, gu.nB, H, bmap, g.nB, H, p, S.seed0, S.msgs[1], H, amax_claim(c, S.msgs[1]), st));   // per-copy masks
+  // (The first per-copy layer's sum of msgs[1] over a2b could be re-derived from z1_u and the stream instead of reading the
+  // [copies, H] tensor back - rr_gather_sum_dropsrc_f32 does that, bit for bit - but stand-alone it takes 52 us against the
+  // 44 us of this gather_sum at the headline shape (profiles/prefix_fuse_ab.txt), so the plan keeps the gather_sum.)
   for (int it = 1; it < depth - 1; ++it)
     wh_forward(c, R, H, pk.enc_wh, m.enc_wh.b, S.msgs[it], S.amsgs[it], S.msgs[it + 1], &S.bits[it + 1], inp_u, bmap, p,
                site_seed(seed, it), st);
@@ -777,8 +782,16 @@ void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr
   const float* d_a = wo_backward(c, m, g, wo_t, sign * ks, S, dH, G, accumulate, part);
   // per-copy W_h layers (it >= 1): gradients arrive masked from the gather that forms them (see mp_backward); the one
   // that reaches the shared prefix stays unmasked - rr_gather_sum_masked_f32 masks it while summing over the copies
-  float* d_msg = gather_epi(c, d_a, g.nA, R.fwd_t, g.nB, R.Kt, H, part, depth - 2 >= 1, S.msgs[depth - 1], S.bits[depth - 1], ks,
-                            nullptr, 0);
+  // The LAST of these gathers (unmasked) forms d message of every copy, whose only reader is the sum over the copies below:
+  // with `fuse` it is not launched and its tensor not allocated - the sum over the copies forms each copy's row itself
+  // (rr_gather2_sum_dropmask_f32: the same additions in the same order).  Not on the two-f16-term layout, which wants that
+  // launch's magnitude output.
+  const bool fuse = c.prefix_fuse && !c.f16 && H % 4 == 0;
+  struct { const float* src; int64_t n_src; const int32_t* idx; int K; const float* part; } last = {nullptr, 0, nullptr, 0, nullptr};
+  float* d_msg = nullptr;
+  if (fuse && depth - 2 < 1) last = {d_a, g.nA, R.fwd_t, R.Kt, part};
+  else d_msg = gather_epi(c, d_a, g.nA, R.fwd_t, g.nB, R.Kt, H, part, depth - 2 >= 1, S.msgs[depth - 1], S.bits[depth - 1], ks,
+                          nullptr, 0);
   const float* fulls[RR_MAX_GATHER_SRCS];   // the per-copy layers' dZ, oldest first (counted, not pointer-tested: a layout pass
   int n_full = 0;                           // hands out null pointers)
   const bool multi = H % 4 == 0 && c.gather_multi;
@@ -802,13 +815,17 @@ void mpn_backward_shared(Ctx& c, const rr_model& m, const rr_graph& gu, const rr
         fulls[n_full - 1] = dz;
       }
     }
-    d_msg = gather_epi(c, d_min, g.nB, R.back, g.nB, R.Kb, H, part, it - 1 >= 1, S.msgs[it], S.bits[it], ks, nullptr, 0);
+    if (fuse && it == 1) last = {d_min, g.nB, R.back, R.Kb, part};
+    else d_msg = gather_epi(c, d_min, g.nB, R.back, g.nB, R.Kb, H, part, it - 1 >= 1, S.msgs[it], S.bits[it], ks, nullptr, 0);
   }
   // ---- shared prefix: msgs[1] = drop_copy(z1_u[bmap]),  z1_u = relu(inp_u + m_in0_u W_h^T + b_h)
   // dz1 of every copy is read once, by the sum over the copies: mask and gather in one pass (no [nB, H] round trip), the
   // copies' masks re-derived from the dropout stream and z1_u instead of read back from msgs[1]
   float* dz1_u = c.alloc(gu.nB, H);
-  if (H % 4 == 0)
+  if (fuse)
+    RR_TRY(c, rr_gather2_sum_dropmask_f32(last.src, last.n_src, H, last.idx, g.nB, last.K, last.part, rr_linear_colsum_rows(last.n_src),
+                                          r4(H), S.z1_u, H, bmap_t, gu.nB, bmap_t_cols, H, p, S.seed0, ks, dz1_u, H, st));
+  else if (H % 4 == 0)
     RR_TRY(c, rr_gather_sum_dropmask_f32(d_msg, g.nB, H, S.z1_u, H, bmap_t, gu.nB, bmap_t_cols, H, p, S.seed0, ks, dz1_u, H, st));
   else
     RR_TRY(c, rr_gather_sum_masked_f32(d_msg, S.msgs[1], g.nB, H, bmap_t, gu.nB, bmap_t_cols, H, ks, dz1_u, H, st));
@@ -1082,6 +1099,7 @@ size_t rr_reaction_workspace_bytes(const rr_model* model, const rr_step* step) {
     c.train = (v & 1) != 0;
     c.ffn_chain = true;
     c.gather_multi = false;             // (the layout with the pre-summed buffers: the larger one)
+    c.prefix_fuse = false;              // (... and with the per-copy d message of the shared-prefix backward)
     Plan P;
     memset(&P, 0, sizeof(P));
     forward_all(c, *model, *step, P);

@@ -163,6 +163,38 @@ def gather_sum_dropmask(src, y, scale: float, idx, H: int, p: float, seed: int, 
     return out
 
 
+def gather2_sum_dropmask(src, in_idx, y, scale: float, out_idx, H: int, p: float, seed: int, row0_partial=None, out=None):
+    """gather_sum_dropmask(gather_sum(src, in_idx, H, row0_partial=...), y, scale, out_idx, H, p, seed) without the
+    intermediate [in_idx rows, H] tensor (rr_gather2_sum_dropmask_f32): bit-identical to the two launches.  With row0_partial,
+    intermediate row 0 may be named by output row 0 only."""
+    in_idx = in_idx if in_idx.dim() == 2 else in_idx.reshape(-1, 1)
+    n_mid, Ki = in_idx.shape
+    n_out, Ko = out_idx.shape
+    if out is None:
+        out = _new(src, n_out, H)
+    assert y.shape[0] == n_out
+    with _Timed("gather2_sum_dropmask_kernel", 0, 4 * (src.shape[0] * H + 2 * n_out * H + n_out * Ko + n_mid * Ki)):
+        check(lib().rr_gather2_sum_dropmask_f32(ptr(src), src.shape[0], _ld(src), ptr(in_idx), n_mid, Ki, ptr(row0_partial),
+                                                0 if row0_partial is None else row0_partial.shape[0], _ld(row0_partial),
+                                                ptr(y), _ld(y), ptr(out_idx), n_out, Ko, H, float(p),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, float(scale), ptr(out), _ld(out), stream()),
+              "rr_gather2_sum_dropmask_f32")
+    return out
+
+
+def gather_sum_dropsrc(y, copies, idx, H: int, p: float, seed: int, out=None):
+    """gather_sum(gather_dropout(y, copies, H, p, seed), idx, H) without reading the materialised copies
+    (rr_gather_sum_dropsrc_f32): every addend is re-derived from y and the copy row's keep bits; bit-identical."""
+    n_out, K = (idx.shape[0], idx.shape[1]) if idx.dim() == 2 else (idx.shape[0], 1)
+    if out is None:
+        out = _new(y, n_out, H)
+    with _Timed("gather_sum_dropsrc_kernel", 0, 4 * (y.shape[0] * H + n_out * H + n_out * K + copies.shape[0])):
+        check(lib().rr_gather_sum_dropsrc_f32(ptr(y), y.shape[0], _ld(y), ptr(copies), copies.shape[0], ptr(idx), n_out, K, H,
+                                              float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), _ld(out), stream()),
+              "rr_gather_sum_dropsrc_f32")
+    return out
+
+
 MAX_GATHER_SRCS = _lib.RR_MAX_GATHER_SRCS
 
 
