@@ -29,6 +29,10 @@ head is read with method='distribution', any other with MC dropout.
 --attribute grad_x_input | integrated_gradients [--ig-steps N] (listwise task types, one process) explains the first validation
 query's predicted top candidate (attribution.attribute): the five product atoms and three bonds of largest |attribution|, the
 attributions' total next to the score and, for integrated gradients, the gap that is left.
+
+--neighbors K (listwise task types, one process) builds a bank of the training reactions' embeddings (neighbors.ReactionBank),
+prints how the distance to the K nearest of them tracks the error on the validation set (neighbors.evaluate_applicability) and,
+for every candidate of the first validation query, its K nearest training reactions with their targets.
 """
 import argparse
 import logging
@@ -41,7 +45,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import attribution, ranknet_baseline, uncertainty   # noqa: E402
+from reactranker_amd import attribution, neighbors, ranknet_baseline, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -98,6 +102,25 @@ def explain_top_candidate(model, b, method, steps, gpu, log):
         log.info("  bond %2d-%-2d  %+.5f", int(edges[e][0]), int(edges[e][1]), float(sym[e]))
 
 
+def nearest_training_reactions(model, train_b, val_b, checkpoint, k, gpu, log):
+    """Applicability domain and explanation by example from a bank of the training reactions' embeddings."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], b["targets"], b["add"])          # noqa: E731
+    bank = neighbors.ReactionBank.from_batches(model, [as_tuple(b) for b in train_b], gpu)
+    res = neighbors.evaluate_applicability(model, bank, val_b, checkpoint, gpu, k=k, target_name=None)
+    cal = res["calibration"]
+    log.info("applicability (bank of %d training reactions, k %d): Spearman(error, latent distance) %.3f; mean latent distance %.4f",
+             len(bank), k, cal["spearman"], float(res["distance"].mean()))
+    log.info("  error left after removing the most distant rows: %s",
+             ", ".join(f"{f:.1f}: mae {m:.4f}" for f, m in zip(cal["fractions"][::3], cal["mae"][::3])))
+    b = val_b[0]
+    n0 = int(b["scope"][0])
+    vec = neighbors.reaction_vectors(model, [as_tuple(b)], gpu)[:n0]
+    dist, idx, tgt = bank.query(vec, k)
+    for c in range(n0):
+        near = ", ".join(f"#{int(i)} (d {float(d):.4f}, target {float(t):+.3f})" for d, i, t in zip(dist[c], idx[c], tgt[c]))
+        log.info("  query 0 candidate %2d (target %+.3f): %s", c, float(b["targets"][c]), near)
+
+
 PAIRWISE = {   # --task-type -> (train_strategy or None = --train-strategy, run_train's task_type)
     "ranknet": (None, "baseline"), "betanet": ("sum_session", "BetaNet"),
     "betanet_evidential": ("sum_session", "BetaNet_envidential"), "pair_baseline": ("baseline", "baseline"),
@@ -144,6 +167,8 @@ def main():
                     "probability at most alpha")
     ap.add_argument("--attribute", choices=attribution.METHODS, default=None, help="listwise task types: after training, which atoms "
                     "and bonds moved the score of the first validation query's predicted top candidate")
+    ap.add_argument("--neighbors", type=int, default=0, metavar="K", help="listwise task types: after training, the applicability "
+                    "calibration of the distance to the K nearest training reactions, and the first validation query's neighbours")
     ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
@@ -225,6 +250,8 @@ def main():
                  res["tau"], res["coverage"], res["mean_set_size"], float(np.mean(res["scope"])))
     if world == 1 and args.attribute:
         explain_top_candidate(model, val_b[0], args.attribute, args.ig_steps, args.gpu, log)
+    if world == 1 and args.neighbors:
+        nearest_training_reactions(model, train_b, val_b, args.checkpoint, args.neighbors, args.gpu, log)
     if world > 1:
         dist.destroy_process_group()
 

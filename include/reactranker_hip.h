@@ -991,6 +991,50 @@ int rr_attribution_reduce_f32(const float* attr_fa, int64_t ld_fa, const float* 
                               const int32_t* b2revb, const int32_t* a_scope, int64_t nA, int64_t nB, int64_t M, int K,
                               float* atom, float* bond, float* bond_sym, double* mol_total, rr_stream_t stream);
 
+/* Nearest-neighbour search over reaction embeddings (additive: seven new symbols, the ABI revision stays 8).  This library's
+ * own definition.  For query rows q [M,H] (ld_q) and bank rows bank [N,H] (ld_b), all f32 device memory:
+ *   d(m,n) = max(0, (qn[m] + bn[n]) - 2 * dot(m,n))                                           all f32
+ *   qn[m] = sum_h q[m,h]^2      bn[n] = sum_h bank[n,h]^2      dot(m,n) = sum_h q[m,h] * bank[n,h]
+ * A pair (m,n) is EXCLUDED when the group arrays are given and q_group[m] == b_group[n] >= 0 (int32 device arrays, both NULL
+ * or both given; a negative id never matches), or when d(m,n) is a NaN.  For every row m the k non-excluded bank rows that are
+ * smallest under the total order (d ascending, then n ascending): dist [M,k] f32 ascending, idx [M,k] int32, both dense.  When
+ * fewer than k rows qualify the remaining slots hold dist = +inf, idx = -1; a bank row whose distance overflowed to +inf is an
+ * ordinary candidate (after every finite one, before the padding).  Every element of both outputs is written.  The [M,N]
+ * distance matrix is never formed: distances come tile by tile from the matrix core and a sorted list per query row (one
+ * wavefront lane per slot, hence RR_KNN_MAX_K = 64) takes them in.
+ * Arithmetic: dot on v_mfma_f32_16x16x4_f32 (f32, one rounding per product); its chain runs over h in tiles of 16 ascending,
+ * inside a tile h = 16 t + 4 c + j with j = 0..3 outer (one instruction each) and c = 0..3 inside the instruction; the
+ * columns from H to the next multiple of 16 enter as zeros.  qn / bn (rr_row_sqnorm_f32, also run inside the search): 64
+ * chains, chain l = 0.0f + x[l]^2 + x[l+64]^2 + ... (each square rounded, then added), joined by the butterfly over lane
+ * distances 32, 16, 8, 4, 2, 1.  So the bits of d(m,n) depend on row m of q, row n of the bank and H only: not on M, N, the
+ * rows' positions, the pitches, the pointers' alignment, the number of bank splits or the grid.  No atomics, nothing depends
+ * on an order of arrival: run-to-run identical.
+ * Limits: k in [1, RR_KNN_MAX_K] (RR_ERR_UNSUPPORTED above); H >= 1 is any value; N <= 2^31 - 1 (RR_ERR_UNSUPPORTED above);
+ * any pitch >= H is accepted (16-byte loads where a pointer and its pitch allow, 4-byte loads otherwise - same values); the
+ * bytes between H and the pitch never reach a result.  M == 0 returns RR_OK without a launch; N == 0 writes the padding.
+ *   rr_row_sqnorm_f32        out[r] = sum_h x[r,h]^2 by the chain above, so that a bank's norms are computed once and kept
+ *   rr_knn_workspace_bytes   bytes of caller-owned scratch one search of this shape needs UNDER THE CURRENT SPLIT SETTING: the
+ *                            query norms, the bank norms (used when bank_sqnorm == NULL) and the per-split lists [M, S, k]
+ *   rr_knn_f32               the search; bank_sqnorm [N] may be NULL (then computed into the workspace by the same chain);
+ *                            nothing is retained after the call's work has run
+ *   rr_knn_geometry          query rows per workgroup, bank rows per tile and RR_KNN_MAX_K as the library was compiled
+ *   rr_knn_splits / rr_knn_set_splits   how many contiguous ranges the bank is cut into (grid = row tiles x splits, the lists
+ *                            of a row merged by a second kernel under the same order): 0 = automatic (two workgroups per CU, at
+ *                            least four bank tiles per split), 1 .. 1024 fixed (never more than bank tiles).  The result is the
+ *                            same bits for every value; a process-wide word, NOT thread-safe, for the bench tool and the tests.
+ * Status, all before any launch: RR_ERR_ARG for a null q / bank / dist / idx / workspace / x / out / bytes, one group array
+ * without the other, a negative M, N or rows, H < 1, k < 1, a pitch below H or a split count outside [0, 1024];
+ * RR_ERR_UNSUPPORTED as above; RR_ERR_WORKSPACE for a workspace below rr_knn_workspace_bytes. */
+#define RR_KNN_MAX_K 64
+int rr_row_sqnorm_f32(const float* x, int64_t ld, int64_t rows, int H, float* out, rr_stream_t stream);
+int rr_knn_workspace_bytes(int64_t M, int64_t N, int k, size_t* bytes);
+int rr_knn_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, int k,
+               const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, float* dist, int32_t* idx,
+               void* workspace, size_t workspace_bytes, rr_stream_t stream);
+void rr_knn_geometry(int* row_tile, int* bank_tile, int* max_k);
+int rr_knn_splits(void);
+int rr_knn_set_splits(int splits);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

@@ -1,0 +1,425 @@
+// Nearest-neighbour search over reaction embeddings.  A definition of this library, not a port.
+//
+//   d(m, n) = max(0, (qn[m] + bn[n]) - 2 * dot(m, n))     qn, bn = squared row norms, dot = q[m,:] . bank[n,:], all f32
+// and, per query row m, the k bank rows that are smallest under the total order (d ascending, then n ascending) among the rows
+// that are not excluded (same non-negative group id, or a NaN distance).  The [M, N] distance matrix is never written.
+//
+// knn_tile_kernel: grid = row tiles x bank splits, four waves.  A workgroup owns KN_ROWS = 64 query rows and walks its
+// contiguous range of the bank in tiles of KN_BANK = 128 rows; both operands stream through LDS in chunks of KN_KC = 64
+// columns (fetched into registers one chunk ahead, behind the MFMAs of the chunk before; k-tiles of 16 that lie wholly past H
+// are skipped), so H is any value.  Wave w owns the
+// bank rows 32 w .. 32 w + 31 of a tile against all 64 query rows: 2 x 4 accumulators of v_mfma_f32_16x16x4_f32
+//   A operand  bank[n0 + 32 w + 16 a + (lane & 15)][16 t + 4 (lane >> 4) + j]     one 16-byte LDS read per k-tile, element j ->
+//   B operand  q[m0 + 16 b + (lane & 15)][16 t + 4 (lane >> 4) + j]               instruction j
+//   C / D      lane holds bank rows 32 w + 16 a + 4 (lane >> 4) + e, e = 0..3, of query row 16 b + (lane & 15)
+// The chain of dot(m, n): k-tiles of 16 ascending, inside a tile h = 16 t + 4 qd + j with j = 0..3 outer (one instruction each)
+// and qd = 0..3 inside the instruction; columns from H to the next multiple of 16 are zeros.  It depends on the two rows and H only.
+// After a tile's MFMAs the distances go to an LDS tile [64][128] (it reuses the staging buffers); wave w then serves the query rows 16 w .. 16 w + 15: a row's
+// list of the 64 best so far lives in registers, one slot per lane, sorted.  A tile's 128 candidates are compared against the
+// row's k-th best (one readlane, one ballot per half); only survivors are inserted (compare and shift by one lane).
+// With more than one split a workgroup writes its rows' lists to the workspace [M, S, k] and knn_merge_kernel (one wave per
+// row) merges them under the same order; with one split the lists are the result.  The order is total (n is unique), so the
+// result does not depend on the order of insertion: no atomics, run-to-run identical, the same bits for every split count.
+//
+// row_sqnorm_kernel: one wave per row; lane l sums x[h]^2 over h = l, l + 64, ... ascending (product rounded, then added), the
+// 64 partial sums are joined by the butterfly xor 32, 16, 8, 4, 2, 1.  4-byte loads only (a wave reads 256 contiguous bytes).
+#include "rr_common.h"
+
+#include <atomic>
+
+namespace {
+
+constexpr int KN_ROWS = 64;                       // query rows per workgroup
+constexpr int KN_BANK = 128;                      // bank rows per tile
+constexpr int KN_KC = 64;                         // columns staged per chunk
+constexpr int KN_NT = 256;                        // threads (4 waves)
+constexpr int KN_SP = KN_KC + 4;                  // pitch of the staged operands (== 4 mod 32: 16 rows x 16 bytes hit 64 banks)
+constexpr int KN_DP = KN_BANK + 4;                // pitch of the distance tile
+constexpr int KN_RPP = KN_NT / (KN_KC / 4);       // rows of a chunk the 256 threads stage per pass (16 bytes per thread)
+constexpr int KN_QU = KN_ROWS / KN_RPP, KN_BU = KN_BANK / KN_RPP;   // passes per chunk: query tile, bank tile
+constexpr int KN_STAGE = (KN_ROWS + KN_BANK) * KN_SP, KN_DT = KN_ROWS * KN_DP;
+constexpr int KN_LDS = KN_STAGE > KN_DT ? KN_STAGE : KN_DT;        // the distance tile reuses the staging buffers
+constexpr int KN_MAX_SPLITS = 1024;
+constexpr int KN_PAD = 0x7fffffff;                // index of an empty slot inside the kernels (N <= 2^31 - 1: above every row)
+
+std::atomic<int> g_splits{0};
+
+struct KnnParams {
+  const float* q; int64_t ld_q; int64_t M;
+  const float* b; int64_t ld_b; int64_t N;
+  int H, k, S;
+  const int32_t* qg; const int32_t* bg;
+  const float* qn; const float* bn;
+  float* out_d; int32_t* out_i;                   // S == 1: the result
+  float* part_d; int32_t* part_i;                 // S > 1: [M, S, k]
+};
+
+typedef const __attribute__((address_space(1))) f32x4* kn_gptr4;
+
+// four consecutive elements of a row from column c (c % 4 == 0), every load unconditional; elements at or past `width`, and
+// rows that do not exist, read as 0 (the address is clamped to a valid one and the value replaced)
+template <bool VEC>
+__device__ __forceinline__ f32x4 kn_load4(const float* row, int c, int width, bool row_ok) {
+  f32x4 v;
+  if (VEC) {
+    v = *(kn_gptr4)(row + (c < width ? c : 0));   // (VEC: ld % 4 == 0, so the chunk lies inside the row's pitch)
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = row[c + e < width ? c + e : 0];
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (row_ok && c + e < width) ? v[e] : 0.f;
+  return v;
+}
+
+__device__ __forceinline__ bool kn_less(float d1, int i1, float d2, int i2) { return d1 < d2 || (d1 == d2 && i1 < i2); }
+__device__ __forceinline__ float kn_lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ int kn_lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+
+// the sorted list (ld, li), one slot per lane: candidate (d, n) takes its place, everything behind it moves one lane up
+__device__ __forceinline__ void kn_insert(float& ld, int& li, float d, int n, int lane) {
+  const bool mine_less = kn_less(ld, li, d, n);
+  const float ud = __shfl_up(ld, 1, 64);
+  const int ui = __shfl_up(li, 1, 64);
+  const bool up_less = lane == 0 || kn_less(ud, ui, d, n);
+  if (!mine_less) {
+    ld = up_less ? d : ud;
+    li = up_less ? n : ui;
+  }
+}
+
+// one candidate per lane: those below the list's slot km1 are inserted, lowest lane first (all 64 lanes active)
+__device__ __forceinline__ void kn_offer(float& ld, int& li, float d, int n, bool valid, int km1, int lane) {
+  float td = kn_lane_f(ld, km1);
+  int ti = kn_lane_i(li, km1);
+  uint64_t mask = __ballot(valid && kn_less(d, n, td, ti));
+  while (mask != 0) {                             // (uniform)
+    const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask));
+    mask &= mask - 1;
+    const float cd = kn_lane_f(d, src);
+    const int cn = kn_lane_i(n, src);
+    if (kn_less(cd, cn, td, ti)) {
+      kn_insert(ld, li, cd, cn, lane);
+      td = kn_lane_f(ld, km1);
+      ti = kn_lane_i(li, km1);
+    }
+  }
+}
+
+template <bool QV, bool BV>
+__global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
+  __shared__ __attribute__((aligned(16))) float smem[KN_LDS];
+  float* const qs = smem;
+  float* const bs = smem + KN_ROWS * KN_SP;
+  float* const dt = smem;                         // between a tile's last MFMA and the next tile's first chunk
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, qd = lane >> 4;
+  const int H = P.H, km1 = P.k - 1;
+  const int64_t m0 = static_cast<int64_t>(blockIdx.x) * KN_ROWS;
+  const int64_t T = (P.N + KN_BANK - 1) / KN_BANK;
+  const int64_t t0 = static_cast<int64_t>(blockIdx.y) * T / P.S, t1 = (static_cast<int64_t>(blockIdx.y) + 1) * T / P.S;
+  const int nch = (H + KN_KC - 1) / KN_KC;
+  const int64_t total = (t1 - t0) * nch;
+
+  // the lists of this wave's 16 query rows
+  float ld[16];
+  int li[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    ld[r] = __builtin_inff();
+    li[r] = KN_PAD;
+  }
+  float qnv[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int64_t m = m0 + 16 * b + l15;
+    qnv[b] = P.qn[m < P.M ? m : 0];
+  }
+  int qgv = -1;                                   // lane r < 16: the group of query row 16 wave + r
+  if (P.qg != nullptr) {
+    const int64_t m = m0 + 16 * wave + l15;
+    qgv = P.qg[m < P.M ? m : 0];
+  }
+
+  // staging: thread -> (row, 4 columns) of the chunk; KN_QU pieces of q and KN_BU of the bank per thread
+  const int srow = tid / (KN_KC / 4), sc4 = (tid % (KN_KC / 4)) * 4;
+  f32x4 qv[KN_QU], bv[KN_BU];
+  auto fetch = [&](int64_t it) {
+    const int64_t tile = it / nch;
+    const int c = static_cast<int>(it - tile * nch) * KN_KC + sc4;
+    const int64_t n0 = (t0 + tile) * KN_BANK;
+#pragma unroll
+    for (int u = 0; u < KN_QU; ++u) {
+      const int64_t m = m0 + srow + KN_RPP * u;
+      const bool ok = m < P.M;
+      qv[u] = kn_load4<QV>(P.q + (ok ? m : 0) * P.ld_q, c, H, ok);
+    }
+#pragma unroll
+    for (int u = 0; u < KN_BU; ++u) {
+      const int64_t n = n0 + srow + KN_RPP * u;
+      const bool ok = n < P.N;
+      bv[u] = kn_load4<BV>(P.b + (ok ? n : 0) * P.ld_b, c, H, ok);
+    }
+  };
+
+  f32x4 acc[2][4];
+  float bnv[2][4];                                // this lane's bank norms and the candidates' groups of the tile in flight,
+  int cn[2], cg[2];                               // loaded at the tile's first chunk, used after its last
+  bool cin[2];
+  if (total > 0) fetch(0);
+  int ch = 0;
+  int64_t n0 = t0 * KN_BANK;
+  for (int64_t it = 0; it < total; ++it) {
+    __syncthreads();                              // the chunk before this one has been read by every wave
+#pragma unroll
+    for (int u = 0; u < KN_QU; ++u) *reinterpret_cast<f32x4*>(qs + (srow + KN_RPP * u) * KN_SP + sc4) = qv[u];
+#pragma unroll
+    for (int u = 0; u < KN_BU; ++u) *reinterpret_cast<f32x4*>(bs + (srow + KN_RPP * u) * KN_SP + sc4) = bv[u];
+    __syncthreads();
+    if (it + 1 < total) fetch(it + 1);            // (uniform)
+    if (ch == 0) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4(0.f);
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int64_t n = n0 + 32 * wave + 16 * a + 4 * qd + e;
+          bnv[a][e] = P.bn[n < P.N ? n : 0];
+        }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int64_t n = n0 + lane + 64 * h;
+        cin[h] = n < P.N;
+        cn[h] = static_cast<int>(cin[h] ? n : 0);
+        cg[h] = (P.bg != nullptr) ? P.bg[cn[h]] : -1;
+      }
+    }
+    const int nt = (H - ch * KN_KC + 15) / 16;    // k-tiles of this chunk that hold anything (uniform)
+#pragma unroll
+    for (int t = 0; t < KN_KC / 16; ++t) {
+      if (t >= nt) break;
+      f32x4 af[2], bf[4];
+#pragma unroll
+      for (int a = 0; a < 2; ++a) af[a] = *reinterpret_cast<const f32x4*>(bs + (32 * wave + 16 * a + l15) * KN_SP + 16 * t + 4 * qd);
+#pragma unroll
+      for (int b = 0; b < 4; ++b) bf[b] = *reinterpret_cast<const f32x4*>(qs + (16 * b + l15) * KN_SP + 16 * t + 4 * qd);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[a][j], bf[b][j], acc[a][b], 0, 0, 0);
+    }
+    if (++ch < nch) continue;
+    ch = 0;
+
+    // ---- the tile is complete: distances -> LDS (over the staging buffers, once every wave has read its last operands)
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const int col = 32 * wave + 16 * a + 4 * qd;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        f32x4 d;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v = (qnv[b] + bnv[a][e]) - 2.0f * acc[a][b][e];
+          d[e] = v < 0.f ? 0.f : v;               // (a NaN stays a NaN: it is excluded below)
+        }
+        *reinterpret_cast<f32x4*>(dt + (16 * b + l15) * KN_DP + col) = d;
+      }
+    }
+    __syncthreads();
+    // ---- selection: this wave's 16 rows against the tile's 128 candidates, lane = candidate (two halves)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int g = kn_lane_i(qgv, r);
+      const float* drow = dt + (16 * wave + r) * KN_DP;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float d = drow[lane + 64 * h];
+        const bool valid = cin[h] && d == d && !(g >= 0 && g == cg[h]);
+        kn_offer(ld[r], li[r], d, cn[h], valid, km1, lane);
+      }
+    }
+    n0 += KN_BANK;
+  }
+
+  // ---- the lists: the result (one split) or this split's partial lists
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t m = m0 + 16 * wave + r;
+    if (m < P.M && lane < P.k) {
+      if (P.S == 1) {
+        P.out_d[m * P.k + lane] = ld[r];
+        P.out_i[m * P.k + lane] = li[r] == KN_PAD ? -1 : li[r];
+      } else {
+        const int64_t o = (m * P.S + blockIdx.y) * P.k + lane;
+        P.part_d[o] = ld[r];
+        P.part_i[o] = li[r];
+      }
+    }
+  }
+}
+
+// one wave per row: the S partial lists of a row -> the row's result (S == 0: all padding)
+__global__ void __launch_bounds__(KN_NT) knn_merge_kernel(const float* part_d, const int32_t* part_i, int64_t M, int S, int k,
+                                                          float* out_d, int32_t* out_i) {
+  const int lane = threadIdx.x & 63;
+  const int64_t m = static_cast<int64_t>(blockIdx.x) * (KN_NT / 64) + (threadIdx.x >> 6);
+  if (m >= M) return;                             // (uniform per wave)
+  float ld = __builtin_inff();
+  int li = KN_PAD;
+  for (int s = 0; s < S; ++s) {
+    const int64_t o = (m * S + s) * k + (lane < k ? lane : 0);
+    const float d = part_d[o];
+    const int n = part_i[o];
+    kn_offer(ld, li, d, n, lane < k && n != KN_PAD, k - 1, lane);
+  }
+  if (lane < k) {
+    out_d[m * k + lane] = ld;
+    out_i[m * k + lane] = li == KN_PAD ? -1 : li;
+  }
+}
+
+__global__ void __launch_bounds__(KN_NT) row_sqnorm_kernel(const float* x, int64_t ld, int64_t rows, int H, float* out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * (KN_NT / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;                          // (uniform per wave)
+  const float* row = x + r * ld;
+  float s = 0.f;
+  for (int h = lane; h < H; h += 64) {
+    const float v = row[h];
+    s += v * v;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) out[r] = s;
+}
+
+inline bool kn_vec_ok(const float* p, int64_t ld) { return rr_aligned16(p) && (ld % 4 == 0); }
+inline size_t kn_round(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
+
+// the split count a search of this shape runs with
+int kn_splits(int64_t M, int64_t N) {
+  const int64_t T = (N + KN_BANK - 1) / KN_BANK;
+  if (T <= 1 || M <= 0) return 1;
+  int64_t S = g_splits.load(std::memory_order_relaxed);
+  if (S == 0) {                                   // automatic: two workgroups per CU, at least four bank tiles per split
+    const int64_t row_tiles = (M + KN_ROWS - 1) / KN_ROWS;
+    S = (2 * RR_NUM_CU + row_tiles - 1) / row_tiles;
+    if (S > T / 4) S = T / 4;
+    if (S < 1) S = 1;
+  }
+  if (S > KN_MAX_SPLITS) S = KN_MAX_SPLITS;
+  if (S > T) S = T;
+  return static_cast<int>(S);
+}
+
+struct KnLayout { size_t qn, bn, part_d, part_i, total; };
+KnLayout kn_layout(int64_t M, int64_t N, int k, int S) {
+  KnLayout L;
+  size_t o = 0;
+  L.qn = o; o += kn_round(static_cast<size_t>(M) * 4);
+  L.bn = o; o += kn_round(static_cast<size_t>(N) * 4);
+  const size_t part = S > 1 ? kn_round(static_cast<size_t>(M) * S * k * 4) : 0;
+  L.part_d = o; o += part;
+  L.part_i = o; o += part;
+  L.total = o > 256 ? o : 256;
+  return L;
+}
+
+int sqnorm_launch(const float* x, int64_t ld, int64_t rows, int H, float* out, hipStream_t s) {
+  const int64_t blocks = (rows + KN_NT / 64 - 1) / (KN_NT / 64);
+  if (blocks > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  row_sqnorm_kernel<<<static_cast<unsigned>(blocks), KN_NT, 0, s>>>(x, ld, rows, H, out);
+  return rr_launch_status();
+}
+
+}  // namespace
+
+extern "C" {
+
+void rr_knn_geometry(int* row_tile, int* bank_tile, int* max_k) {
+  if (row_tile) *row_tile = KN_ROWS;
+  if (bank_tile) *bank_tile = KN_BANK;
+  if (max_k) *max_k = RR_KNN_MAX_K;
+}
+
+int rr_knn_splits(void) { return g_splits.load(std::memory_order_relaxed); }
+
+int rr_knn_set_splits(int splits) {
+  RR_CHECK_ARG(splits >= 0 && splits <= KN_MAX_SPLITS);
+  g_splits.store(splits, std::memory_order_relaxed);
+  return RR_OK;
+}
+
+int rr_row_sqnorm_f32(const float* x, int64_t ld, int64_t rows, int H, float* out, rr_stream_t stream) {
+  RR_CHECK_ARG(x && out && rows >= 0 && H >= 1 && ld >= H);
+  if (rows == 0) return RR_OK;
+  return sqnorm_launch(x, ld, rows, H, out, static_cast<hipStream_t>(stream));
+}
+
+int rr_knn_workspace_bytes(int64_t M, int64_t N, int k, size_t* bytes) {
+  RR_CHECK_ARG(bytes && M >= 0 && N >= 0 && k >= 1);
+  if (k > RR_KNN_MAX_K || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  *bytes = kn_layout(M, N, k, kn_splits(M, N)).total;
+  return RR_OK;
+}
+
+int rr_knn_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, int k,
+               const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, float* dist, int32_t* idx,
+               void* workspace, size_t workspace_bytes, rr_stream_t stream) {
+  RR_CHECK_ARG(q && bank && dist && idx && workspace);
+  RR_CHECK_ARG((q_group == nullptr) == (b_group == nullptr));
+  RR_CHECK_ARG(M >= 0 && N >= 0 && H >= 1 && k >= 1 && ld_q >= H && ld_b >= H);
+  if (k > RR_KNN_MAX_K || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  const int S = kn_splits(M, N);
+  const KnLayout L = kn_layout(M, N, k, S);
+  if (workspace_bytes < L.total) return RR_ERR_WORKSPACE;
+  if (M == 0) return RR_OK;
+  const int64_t row_tiles = (M + KN_ROWS - 1) / KN_ROWS, merge_blocks = (M + KN_NT / 64 - 1) / (KN_NT / 64);
+  if (merge_blocks > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(workspace);
+  if (N == 0) {                                   // nothing to search: the merge of zero lists writes the padding
+    knn_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(nullptr, nullptr, M, 0, k, dist, idx);
+    return rr_launch_status();
+  }
+  KnnParams P;
+  P.q = q; P.ld_q = ld_q; P.M = M;
+  P.b = bank; P.ld_b = ld_b; P.N = N;
+  P.H = H; P.k = k; P.S = S;
+  P.qg = q_group; P.bg = b_group;
+  float* qn = reinterpret_cast<float*>(ws + L.qn);
+  int st = sqnorm_launch(q, ld_q, M, H, qn, s);
+  if (st != RR_OK) return st;
+  P.qn = qn;
+  if (bank_sqnorm) {
+    P.bn = bank_sqnorm;
+  } else {
+    float* bn = reinterpret_cast<float*>(ws + L.bn);
+    st = sqnorm_launch(bank, ld_b, N, H, bn, s);
+    if (st != RR_OK) return st;
+    P.bn = bn;
+  }
+  P.out_d = dist; P.out_i = idx;
+  P.part_d = reinterpret_cast<float*>(ws + L.part_d);
+  P.part_i = reinterpret_cast<int32_t*>(ws + L.part_i);
+  const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(S));
+  const bool qv = kn_vec_ok(q, ld_q), bv = kn_vec_ok(bank, ld_b);
+  if (qv && bv) knn_tile_kernel<true, true><<<grid, KN_NT, 0, s>>>(P);
+  else if (qv) knn_tile_kernel<true, false><<<grid, KN_NT, 0, s>>>(P);
+  else if (bv) knn_tile_kernel<false, true><<<grid, KN_NT, 0, s>>>(P);
+  else knn_tile_kernel<false, false><<<grid, KN_NT, 0, s>>>(P);
+  st = rr_launch_status();
+  if (st != RR_OK || S == 1) return st;
+  knn_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(P.part_d, P.part_i, M, S, k, dist, idx);
+  return rr_launch_status();
+}
+
+}  // extern "C"

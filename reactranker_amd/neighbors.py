@@ -1,0 +1,310 @@
+"""Nearest-neighbour search over reaction embeddings: has the model seen anything like this reaction?
+
+The embedding is the model's own reaction vector (the diff encoder's readout, RR_SAVED_VECS of a step plan); the search is
+rr_knn_f32 (csrc/knn.hip): squared Euclidean distances from the matrix core, tile by tile, into a sorted list per query row -
+the [M, N] distance matrix is never written.  On top of it:
+
+  reaction_vectors        the embedding of every candidate of a list of batches, one eval-mode forward each
+  knn                     (dist [M, k] float32, idx [M, k] int64) of query rows against bank rows, with optional group exclusion
+  ReactionBank            vectors + squared norms + targets + query index per row of a set of reactions; save / load / query
+  latent_distance         mean distance to the k nearest bank rows: a one-forward uncertainty for every task type
+  evaluate_applicability  that distance against the model's error on a test set (uncertainty.uncertainty_calibration)
+  split_overlap           test rows that have a (near-)duplicate in the bank
+
+There is no CPU path: tensors on the CPU raise."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import eval as E
+from . import uncertainty as U
+from ._lib import check, lib, ptr, stream
+from .functions import StepPlan
+from .utils import load_checkpoint
+
+MAX_K = _lib.RR_KNN_MAX_K
+METRICS = ("sqeuclidean", "cosine")
+
+
+def geometry() -> Tuple[int, int, int]:
+    """(query rows per workgroup, bank rows per tile, largest k) of the compiled library (rr_knn_geometry)"""
+    a, b, c = C.c_int(), C.c_int(), C.c_int()
+    lib().rr_knn_geometry(C.byref(a), C.byref(b), C.byref(c))
+    return a.value, b.value, c.value
+
+
+def _matrix(t, name: str) -> None:
+    if not torch.is_tensor(t) or t.dim() != 2:
+        raise ValueError(f"knn: `{name}` must be a matrix [rows, H] (got {type(t).__name__}"
+                         + (f" of shape {tuple(t.shape)})" if torch.is_tensor(t) else ")"))
+    if t.dtype != torch.float32:
+        raise ValueError(f"knn: `{name}` must be float32 (got {t.dtype})")
+
+
+def _rows(t, name: str) -> torch.Tensor:
+    """a float32 GPU matrix whose rows are contiguous (any row pitch is taken as it is)"""
+    _matrix(t, name)
+    if not t.is_cuda:
+        raise ValueError(f"knn: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
+    t = t.detach()
+    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def _group(g, rows: int, dev, name: str) -> torch.Tensor:
+    g = torch.as_tensor(g)
+    if g.numel() != rows:
+        raise ValueError(f"knn: `{name}` has {g.numel()} entries for {rows} rows")
+    if g.is_floating_point():
+        raise ValueError(f"knn: `{name}` must hold integers")
+    return g.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+
+def row_sqnorm(x: torch.Tensor) -> torch.Tensor:
+    """sum_h x[r, h]^2 per row by the library's fixed f32 chain (rr_row_sqnorm_f32): what knn() takes as `bank_sqnorm`"""
+    x = _rows(x, "x")
+    if x.shape[1] < 1:
+        raise ValueError("row_sqnorm: rows of width 0")
+    out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return out
+    with torch.cuda.device(x.device):
+        check(lib().rr_row_sqnorm_f32(ptr(x), x.stride(0) if x.shape[0] > 1 else x.shape[1], x.shape[0], x.shape[1], ptr(out),
+                                      stream()), "rr_row_sqnorm_f32")
+    return out
+
+
+def _unit_rows(x: torch.Tensor) -> torch.Tensor:
+    n = x.norm(dim=1, keepdim=True)
+    return torch.where(n > 0, x / torch.where(n > 0, n, torch.ones_like(n)), torch.zeros_like(x))
+
+
+def knn(queries: torch.Tensor, bank: torch.Tensor, k: int, q_group=None, b_group=None, bank_sqnorm=None,
+        metric: str = "sqeuclidean") -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k nearest bank rows of every query row: (dist [M, k] float32 ascending, idx [M, k] int64).
+
+    dist = max(0, |q|^2 + |b|^2 - 2 q.b) in f32 (include/reactranker_hip.h states the chains); ties go to the lower bank
+    index.  A pair is excluded when q_group[m] == b_group[n] >= 0 (both or neither given; integer arrays, one entry per row)
+    or when its distance is a NaN.  When fewer than k rows qualify the remaining slots hold dist = +inf, idx = -1.
+    bank_sqnorm: row_sqnorm(bank) kept from an earlier call (metric 'sqeuclidean' only).
+    metric 'cosine': rows are divided by their norm with torch first (a zero row stays zero) and the result is halved, so
+    dist = 1 - cos for non-zero rows; a zero row is then at distance 1/2 from every unit row (and 0 from another zero row).
+    Scratch comes from torch's allocator on the current stream, and the call is ordered on that stream.
+    ValueError - before any launch - for CPU tensors, k outside [1, 64], widths that differ or are 0, or one group array
+    without the other."""
+    if metric not in METRICS:
+        raise ValueError(f"knn: metric must be one of {METRICS} (got {metric!r})")
+    _matrix(queries, "queries")
+    _matrix(bank, "bank")
+    kk = int(k)
+    if kk != k or not (1 <= kk <= MAX_K):
+        raise ValueError(f"knn: k must be an integer in [1, {MAX_K}] (got {k!r})")
+    if queries.shape[1] != bank.shape[1] or queries.shape[1] < 1:
+        raise ValueError(f"knn: queries have width {queries.shape[1]}, the bank {bank.shape[1]} (equal and >= 1 required)")
+    if (q_group is None) != (b_group is None):
+        raise ValueError("knn: q_group and b_group go together (both or neither)")
+    q, b = _rows(queries, "queries"), _rows(bank, "bank")
+    if q.device != b.device:
+        raise ValueError(f"knn: queries on {q.device}, bank on {b.device}")
+    M, N, H = q.shape[0], b.shape[0], q.shape[1]
+    dev = q.device
+    qg = bg = None
+    if q_group is not None:
+        qg, bg = _group(q_group, M, dev, "q_group"), _group(b_group, N, dev, "b_group")
+    bn = None
+    if metric == "cosine":
+        if bank_sqnorm is not None:
+            raise ValueError("knn: bank_sqnorm belongs to metric 'sqeuclidean' (cosine normalises the rows first)")
+        q, b = _unit_rows(q), _unit_rows(b)
+    elif bank_sqnorm is not None:
+        bn = torch.as_tensor(bank_sqnorm)
+        if not bn.is_cuda or bn.dtype != torch.float32 or bn.numel() != N:
+            raise ValueError(f"knn: bank_sqnorm must be {N} float32 values on the GPU")
+        bn = bn.reshape(-1).contiguous()
+    dist = torch.empty(M, kk, dtype=torch.float32, device=dev)
+    idx = torch.empty(M, kk, dtype=torch.int32, device=dev)
+    if M == 0:
+        return dist, idx.to(torch.int64)
+    if N == 0:                                             # (the C entry wants a bank pointer even when it holds no row)
+        b = torch.zeros(1, H, dtype=torch.float32, device=dev)
+        bg = None if bg is None else torch.full((1,), -1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = C.c_size_t()
+        check(lib().rr_knn_workspace_bytes(M, N, kk, C.byref(nbytes)), "rr_knn_workspace_bytes")
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        check(lib().rr_knn_f32(ptr(q), q.stride(0) if M > 1 else H, M, ptr(b), b.stride(0) if N > 1 else H, N, H, kk, ptr(qg),
+                               ptr(bg), ptr(bn), ptr(dist), ptr(idx), ptr(ws), C.c_size_t(nbytes.value), stream()), "rr_knn_f32")
+    if metric == "cosine":
+        dist = dist * 0.5
+    return dist, idx.to(torch.int64)
+
+
+# ------------------------------------------------------------------------------------------------ the embedding
+def _forward_with_vectors(model, r_batch, p_batch, add_features, gpu):
+    """(model output, reaction vectors [M, H + F] as a copy) of one batch; the caller has set eval mode, no_grad and
+    StepPlan.keep_last.  On the step-plan path the vectors are RR_SAVED_VECS of the forward that made the output; where a
+    model does not qualify for a plan (hidden size % 4 != 0) the encoder modules are run once more, as
+    encoder(p) - encoder(r) -> diff_encoder: the same kernels launch by launch."""
+    StepPlan.last = None
+    out = model(r_batch, p_batch, gpu=gpu, add_features=add_features)
+    if StepPlan.last is not None:                          # (the saved rows are padded to the plan's pitch: keep H + F columns)
+        return out, StepPlan.saved(_lib.RR_SAVED_VECS)[:, :int(model.ffn.hidden_size)].clone()
+    if torch.is_tensor(add_features):
+        add_features = add_features.detach().cpu().numpy()
+    r_h, p_h = model.encoder(r_batch, gpu), model.encoder(p_batch, gpu)
+    return out, model.diff_encoder(p_h - r_h, p_batch, gpu, features_batch=add_features).clone()
+
+
+def reaction_vectors(model, batches: Iterable, gpu, include_features: bool = False) -> torch.Tensor:
+    """The model's reaction vector of every candidate of `batches` ((r, p, scope, targets, add_features) tuples, the form
+    the evaluators take; batches without queries are skipped): one eval-mode forward per batch under no_grad (on the step-plan
+    path; _forward_with_vectors says what happens without one), the first H columns of RR_SAVED_VECS (all of them - the additional features behind the H readout columns - with
+    include_features) copied out of the step's workspace before another step can reuse it.  [sum M, H] float32 on the device.
+    model.training, StepPlan.keep_last and StepPlan.last are left as found."""
+    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
+    H = int(model.encoder.hidden_size)
+    out = []
+    try:
+        model.eval()
+        StepPlan.keep_last = True
+        with torch.no_grad():
+            for r_batch, p_batch, scope, _targets, add_features in batches:
+                if len(scope) == 0:
+                    continue
+                _, v = _forward_with_vectors(model, r_batch, p_batch, add_features, gpu)
+                out.append(v if include_features else v[:, :H].contiguous())
+    finally:
+        StepPlan.keep_last, StepPlan.last = old_keep, old_last
+        model.train(was_training)
+    if not out:
+        dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
+        return torch.zeros(0, H, dtype=torch.float32, device=dev)
+    return torch.cat(out, 0)
+
+
+class ReactionBank:
+    """The reactions a model was trained on, as the search needs them: vectors [N, H], sqnorm [N] (row_sqnorm of them),
+    targets [N] float32 and group [N] int32 = the running index of the query a row belongs to (so that "neighbours from
+    OTHER queries" and leave-one-query-out of the bank against itself are one knn call)."""
+
+    def __init__(self, vectors: torch.Tensor, targets, group, sqnorm: Optional[torch.Tensor] = None):
+        self.vectors = _rows(vectors, "vectors").contiguous()
+        dev, N = self.vectors.device, self.vectors.shape[0]
+        self.targets = torch.as_tensor(targets).reshape(-1).to(device=dev, dtype=torch.float32)
+        if self.targets.numel() != N:
+            raise ValueError(f"ReactionBank: {self.targets.numel()} targets for {N} rows")
+        self.group = _group(group, N, dev, "group")
+        self.sqnorm = row_sqnorm(self.vectors) if sqnorm is None else sqnorm.to(device=dev, dtype=torch.float32).reshape(-1)
+        if self.sqnorm.numel() != N:
+            raise ValueError(f"ReactionBank: {self.sqnorm.numel()} norms for {N} rows")
+
+    def __len__(self) -> int:
+        return int(self.vectors.shape[0])
+
+    @classmethod
+    def from_batches(cls, model, batches: Sequence, gpu, include_features: bool = False) -> "ReactionBank":
+        batches = [b for b in batches if len(b[2]) > 0]
+        vec = reaction_vectors(model, batches, gpu, include_features)
+        targets = torch.cat([torch.as_tensor(b[3]).reshape(-1).to(torch.float32) for b in batches]) if batches else torch.zeros(0)
+        sizes = [int(c) for b in batches for c in b[2]]
+        group = torch.repeat_interleave(torch.arange(len(sizes), dtype=torch.int32), torch.tensor(sizes, dtype=torch.int64))
+        return cls(vec, targets, group)
+
+    def save(self, path) -> None:
+        torch.save(dict(vectors=self.vectors.cpu(), sqnorm=self.sqnorm.cpu(), targets=self.targets.cpu(),
+                        group=self.group.cpu()), path)
+
+    @classmethod
+    def load(cls, path, device) -> "ReactionBank":
+        d = torch.load(path, map_location="cpu")
+        dev = torch.device(device)
+        return cls(d["vectors"].to(dev), d["targets"], d["group"], sqnorm=d["sqnorm"])
+
+    def query(self, vectors: torch.Tensor, k: int, group=None):
+        """(dist [M, k], idx [M, k] int64, targets [M, k]) of the k nearest bank rows; `group` (one query index per row)
+        excludes the bank rows of the same query; targets of padding slots (idx -1) are NaN."""
+        bg = None if group is None else self.group
+        dist, idx = knn(vectors, self.vectors, k, q_group=group, b_group=bg, bank_sqnorm=self.sqnorm)
+        if len(self) == 0:
+            return dist, idx, torch.full_like(dist, float("nan"))
+        t = self.targets[idx.clamp_min(0)]
+        return dist, idx, torch.where(idx >= 0, t, torch.full_like(t, float("nan")))
+
+
+def latent_distance(bank: ReactionBank, vectors: torch.Tensor, k: int, group=None) -> torch.Tensor:
+    """Per row, the mean of sqrt(d) over the (at most k) neighbours found in the bank; +inf when there are none."""
+    dist, idx, _ = bank.query(vectors, k, group)
+    found = idx >= 0
+    n = found.sum(dim=1)
+    s = torch.where(found, dist.sqrt(), torch.zeros_like(dist)).sum(dim=1)
+    return torch.where(n > 0, s / n.clamp_min(1).to(s.dtype), torch.full_like(s, float("inf")))
+
+
+def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dict], path_checkpoints, gpu: int, k: int = 8,
+                           target_name: str = "ea", fractions=U.DEFAULT_FRACTIONS) -> dict:
+    """Applicability domain of a trained model: the latent distance of every test candidate to `bank` against its error.
+    `test_batches` are the dicts main.test takes (r, p, scope, targets, add); the checkpoint is loaded and the targets are
+    standardised as evaluate_uncertainty does.  One eval-mode forward per batch gives both the scores (column 0) and the
+    reaction vectors.  Returns dict(distance [n], pred [n], targets [n] (standardised), scope, calibration =
+    uncertainty_calibration(pred, targets, distance, fractions) - Spearman rho of error and distance plus the
+    error-confidence curve -, qstats [Q, 12] = eval.ranking_stats per query, query_distance [Q] = mean distance per query).
+    A bank without rows gives +inf distances, which the calibration sorts like any other value."""
+    if not isinstance(path_checkpoints, (str, bytes)) and hasattr(path_checkpoints, "__len__"):
+        raise ValueError("evaluate_applicability takes one checkpoint path")
+    U._check_fractions(fractions)
+    f = U._standardizer(U._scaler_of(path_checkpoints), target_name)
+    batches = []
+    for b in test_batches:
+        y = np.asarray(torch.as_tensor(b["targets"]).cpu(), np.float64).reshape(-1)
+        if len(b["scope"]) > 0:
+            batches.append((b["r"], b["p"], b["scope"], torch.tensor(f(y), dtype=torch.float32), b.get("add")))
+    if not batches:
+        raise ValueError("no queries to evaluate")
+    model = model.cuda(gpu)
+    load_checkpoint(path_checkpoints, model, map_location="cpu")
+    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
+    H = int(model.encoder.hidden_size)
+    if bank.vectors.shape[1] != H:
+        raise ValueError(f"the bank holds vectors of width {bank.vectors.shape[1]}, the model's are {H}")
+    preds, dists, stats = [], [], []
+    try:
+        model.eval()
+        StepPlan.keep_last = True
+        with torch.no_grad():
+            for r_batch, p_batch, scope, targets, add in batches:
+                out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
+                vec = vec[:, :H]
+                pred = U._first_column(out)
+                preds.append(pred)
+                dists.append(latent_distance(bank, vec, k))
+                stats.append(E.ranking_stats(pred, scope, targets, gpu, 0.25)[0])
+    finally:
+        StepPlan.keep_last, StepPlan.last = old_keep, old_last
+        model.train(was_training)
+    pred, distance = torch.cat(preds), torch.cat(dists)
+    targets = torch.cat([b[3].reshape(-1) for b in batches]).to(pred.device)
+    scope = [int(c) for b in batches for c in b[2]]
+    seg = torch.repeat_interleave(torch.arange(len(scope), device=pred.device), torch.tensor(scope, device=pred.device))
+    qd = torch.zeros(len(scope), dtype=torch.float64, device=pred.device).index_add_(0, seg, distance.double())
+    qd = qd / torch.tensor(scope, dtype=torch.float64, device=pred.device)
+    return dict(distance=distance, pred=pred, targets=targets, scope=scope,
+                calibration=U.uncertainty_calibration(pred, targets, distance, fractions),
+                qstats=torch.cat(stats, 0), query_distance=qd)
+
+
+def split_overlap(bank: ReactionBank, vectors: torch.Tensor, rel_tol: float = 1e-6) -> dict:
+    """Leakage between a bank and another split: dict(count, rows [count] int64, nearest [M] int64, dist [M]) where `rows`
+    are the rows of `vectors` whose nearest bank row lies within d <= rel_tol * (|q|^2 + |b|^2)."""
+    dist, idx = knn(vectors, bank.vectors, 1, bank_sqnorm=bank.sqnorm)
+    dist, idx = dist[:, 0], idx[:, 0]
+    qn = row_sqnorm(vectors) if vectors.shape[0] > 0 else dist
+    bn = bank.sqnorm[idx.clamp_min(0)] if len(bank) > 0 else torch.zeros_like(dist)
+    hit = (idx >= 0) & (dist <= float(rel_tol) * (qn + bn))
+    rows = hit.nonzero().reshape(-1)
+    return dict(count=int(rows.numel()), rows=rows, nearest=idx, dist=dist)
