@@ -33,6 +33,10 @@ attributions' total next to the score and, for integrated gradients, the gap tha
 --neighbors K (listwise task types, one process) builds a bank of the training reactions' embeddings (neighbors.ReactionBank),
 prints how the distance to the K nearest of them tracks the error on the validation set (neighbors.evaluate_applicability) and,
 for every candidate of the first validation query, its K nearest training reactions with their targets.
+
+--acquire N (listwise task types, one process) treats the validation reactions as an unlabelled pool and prints which N of
+them to compute next (neighbors.acquire: greedy k-center from the bank of training embeddings, weighted by the head's own
+predictive std where it has one), with the pool's coverage radius before and after.
 """
 import argparse
 import logging
@@ -121,6 +125,21 @@ def nearest_training_reactions(model, train_b, val_b, checkpoint, k, gpu, log):
         log.info("  query 0 candidate %2d (target %+.3f): %s", c, float(b["targets"][c]), near)
 
 
+def reactions_to_compute_next(model, train_b, val_b, n, gpu, log):
+    """Batch acquisition: the validation reactions as the pool, the training reactions as what is labelled already."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], None, b["add"])                  # noqa: E731  (a pool has no targets)
+    bank = neighbors.ReactionBank.from_batches(model, [(b["r"], b["p"], b["scope"], b["targets"], b["add"]) for b in train_b], gpu)
+    weight = "std" if model.ffn.head() in uncertainty.MOMENT_KIND_OF_HEAD else None   # no predicted variance: pure coverage
+    res = neighbors.acquire(model, bank, [as_tuple(b) for b in val_b], n, gpu, weight=weight)
+    log.info("acquisition (pool of %d validation reactions, bank of %d, weight %s): coverage radius %.4f -> %.4f after %d picks",
+             res["min_dist"].numel(), len(bank), weight, float(res["radius_before"]), float(res["radius_after"]),
+             int((res["rows"] >= 0).sum()))
+    for t, (row, bt, q, c, gain) in enumerate(zip(*[res[k].cpu().tolist() for k in ("rows", "batch", "query", "candidate", "gain")])):
+        if row >= 0:
+            log.info("  pick %2d: pool row %4d = batch %d, query %2d, candidate %2d  (score %.5f; %d pool rows are nearest to it)",
+                     t, row, bt, q, c, gain, int((res["assign"] == t).sum()))
+
+
 PAIRWISE = {   # --task-type -> (train_strategy or None = --train-strategy, run_train's task_type)
     "ranknet": (None, "baseline"), "betanet": ("sum_session", "BetaNet"),
     "betanet_evidential": ("sum_session", "BetaNet_envidential"), "pair_baseline": ("baseline", "baseline"),
@@ -169,6 +188,8 @@ def main():
                     "and bonds moved the score of the first validation query's predicted top candidate")
     ap.add_argument("--neighbors", type=int, default=0, metavar="K", help="listwise task types: after training, the applicability "
                     "calibration of the distance to the K nearest training reactions, and the first validation query's neighbours")
+    ap.add_argument("--acquire", type=int, default=0, metavar="N", help="listwise task types: after training, which N validation "
+                    "reactions to compute next (greedy k-center from the training embeddings) and the coverage radius before and after")
     ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
@@ -252,6 +273,8 @@ def main():
         explain_top_candidate(model, val_b[0], args.attribute, args.ig_steps, args.gpu, log)
     if world == 1 and args.neighbors:
         nearest_training_reactions(model, train_b, val_b, args.checkpoint, args.neighbors, args.gpu, log)
+    if world == 1 and args.acquire:
+        reactions_to_compute_next(model, train_b, val_b, args.acquire, args.gpu, log)
     if world > 1:
         dist.destroy_process_group()
 

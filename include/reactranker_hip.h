@@ -1035,6 +1035,51 @@ void rr_knn_geometry(int* row_tile, int* bank_tile, int* max_k);
 int rr_knn_splits(void);
 int rr_knn_set_splits(int splits);
 
+/* Greedy k-center selection over reaction embeddings (additive: four new symbols, the ABI revision stays 8).  This library's
+ * own definition.  For pool rows x [P,H] (ld), f32 device memory, pick n_pick rows one after the other, each the row that lies
+ * farthest (optionally times a weight) from everything that init_dist stands for and from every row picked before it.
+ * Distance of row i to a centre row c, all f32, every difference, product and sum rounded on its own:
+ *   columns are cut into groups of four, group g = columns 4g .. min(4g+3, H-1); lane l of a 64-lane wavefront owns the groups
+ *   with g mod 64 == l and walks them ascending, the columns inside a group ascending:
+ *     acc = 0.0f;   t = x[i,h] - x[c,h];   acc = acc + t * t
+ *   the 64 chains are joined by the butterfly over lane distances 32, 16, 8, 4, 2, 1 (acc = acc + acc of lane ^ distance).
+ * So the bits of d(i,c) depend on the two rows and H only: not on P, the rows' positions, ld, the pointer's alignment, the
+ * grid or the blocks setting.  (Not knn's |q|^2 + |b|^2 - 2 q.b: the difference form has no cancellation, and d(i,i) = 0.)
+ * State: min_dist[i] = init_dist ? init_dist[i] : +inf, but NaN for a row that holds any non-finite value; assign[i] = -1.
+ * Row i is ELIGIBLE in a round when it has not been taken, min_dist[i] is not a NaN and, with weights, 0 < weight[i] < +inf;
+ * its score is s_i = weight ? weight[i] * min_dist[i] : min_dist[i].  Round t = 0 .. n_pick-1 takes the eligible row i that is
+ * largest under the total order (score descending, then i ascending): picks[t] = i, gain[t] = s_i; then every row r whose
+ * min_dist is not a NaN and for which d(r,i) < min_dist[r] (strict) gets min_dist[r] = d(r,i), assign[r] = t.  With no eligible
+ * row left picks[t] = -1 and gain[t] = -1.0f.  Every element of picks, gain [n_pick] and min_dist, assign [P] is written.  A
+ * picked row ends at min_dist = 0, as do its exact duplicates, which stay eligible and are taken last, in index order.
+ * How it runs: n_pick + 1 launches of one kernel on `stream`, nothing else - no host synchronisation, no copy to the host, no
+ * atomics, nothing that depends on an order of arrival, no workgroup that waits for another.  Launch 0 writes the state (the one
+ * extra read of the pool: it finds the non-finite rows) and scores round 0; launch t reads the (score, index) pair every
+ * workgroup of launch t-1 left in the workspace, reduces them to the winner in every workgroup alike, keeps the winner's columns
+ * in registers (H <= 1024; wider rows re-read them) and streams the pool once: one wavefront per row, rows grid-strided, four
+ * rows per workgroup and grid pass (256 threads).  16-byte loads where x and ld allow, 4-byte loads otherwise - same values;
+ * the bytes between H and ld never reach a result.
+ * Limits: n_pick <= RR_KCENTER_MAX_PICKS and P <= 2^31 - 1 (RR_ERR_UNSUPPORTED above); H >= 1 is any value.  P == 0 writes the
+ * padding of picks / gain; n_pick == 0 still writes min_dist / assign.
+ *   rr_kcenter_workspace_bytes   bytes of caller-owned scratch: the pairs of two launches at the largest grid plus one byte
+ *                                per row; it does not depend on the blocks setting; nothing is retained after the call's work
+ *   rr_kcenter_blocks / rr_kcenter_set_blocks   workgroups per launch: 0 = automatic (two rows per wavefront and launch at
+ *                                least, 4 workgroups per CU at most), 1 .. 4096 fixed.  The result is the same bits for every
+ *                                value; a process-wide word, NOT thread-safe, for the bench tool and the tests.
+ * Status, all before any launch: RR_ERR_ARG for a null x / picks / gain / min_dist / assign / workspace / bytes, a negative P
+ * or n_pick, H < 1, ld < H or blocks outside [0, 4096]; RR_ERR_UNSUPPORTED as above; RR_ERR_WORKSPACE for a workspace below
+ * rr_kcenter_workspace_bytes. */
+#define RR_KCENTER_MAX_PICKS 65536
+int rr_kcenter_workspace_bytes(int64_t P, int n_pick, size_t* bytes);
+int rr_kcenter_f32(const float* x, int64_t ld, int64_t P, int H, int n_pick,
+                   const float* init_dist,   /* [P] or NULL (= +inf everywhere) */
+                   const float* weight,      /* [P] or NULL (= 1 everywhere)    */
+                   int32_t* picks, float* gain,          /* [n_pick] each */
+                   float* min_dist, int32_t* assign,     /* [P] each      */
+                   void* workspace, size_t workspace_bytes, rr_stream_t stream);
+int rr_kcenter_blocks(void);
+int rr_kcenter_set_blocks(int blocks);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

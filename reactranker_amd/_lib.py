@@ -309,6 +309,11 @@ _SIGS = {
     "rr_knn_geometry": (None, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "rr_knn_splits": (i32, []),
     "rr_knn_set_splits": (i32, [i32]),
+    "rr_kcenter_workspace_bytes": (i32, [i64, i32, C.POINTER(C.c_size_t)]),
+    "rr_kcenter_f32": (i32, [c_f32p, i64, i64, i32, i32, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p, C.c_void_p,
+                             C.c_size_t, c_stream]),
+    "rr_kcenter_blocks": (i32, []),
+    "rr_kcenter_set_blocks": (i32, [i32]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
@@ -349,6 +354,7 @@ RR_MAX_ADAM = 64
 RR_AMAX_LANES, RR_AMAX_STRIDE = 16, 32
 RR_AMAX_FLOATS = RR_AMAX_LANES * RR_AMAX_STRIDE
 RR_KNN_MAX_K = 64
+RR_KCENTER_MAX_PICKS = 65536
 ABI_VERSION = 8
 (RR_SAVED_R_MSG, RR_SAVED_R_H, RR_SAVED_P_MSG, RR_SAVED_P_H, RR_SAVED_D_MSG, RR_SAVED_D_HID, RR_SAVED_VECS, RR_SAVED_FFN_H,
  RR_SAVED_R_MSG0_U, RR_SAVED_R_Z1_U) = range(10)

@@ -10,6 +10,10 @@ the [M, N] distance matrix is never written.  On top of it:
   latent_distance         mean distance to the k nearest bank rows: a one-forward uncertainty for every task type
   evaluate_applicability  that distance against the model's error on a test set (uncertainty.uncertainty_calibration)
   split_overlap           test rows that have a (near-)duplicate in the bank
+  kcenter_greedy          greedy k-center selection (rr_kcenter_f32): n rows of a pool, each the farthest
+                          (optionally times a weight) from a labelled set and from the rows taken before it
+  acquire                 which reactions to compute next: kcenter_greedy over a model's embedding of a pool, started from the
+                          distance to a ReactionBank, optionally weighted by the predictive uncertainty
 
 There is no CPU path: tensors on the CPU raise."""
 from __future__ import annotations
@@ -28,6 +32,8 @@ from .functions import StepPlan
 from .utils import load_checkpoint
 
 MAX_K = _lib.RR_KNN_MAX_K
+MAX_PICKS = _lib.RR_KCENTER_MAX_PICKS
+KCENTER_ROWS_PER_WORKGROUP = 4                             # one wavefront per row, 256 threads (csrc/kcenter.hip)
 METRICS = ("sqeuclidean", "cosine")
 
 
@@ -308,3 +314,139 @@ def split_overlap(bank: ReactionBank, vectors: torch.Tensor, rel_tol: float = 1e
     hit = (idx >= 0) & (dist <= float(rel_tol) * (qn + bn))
     rows = hit.nonzero().reshape(-1)
     return dict(count=int(rows.numel()), rows=rows, nearest=idx, dist=dist)
+
+
+# ------------------------------------------------------------------------------------------------ selection
+def _per_row(t, rows: int, dev, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or t.numel() != rows:
+        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"kcenter_greedy: `{name}` must be {rows} float32 values on {dev} (got {got})")
+    return t.detach().reshape(-1).contiguous()
+
+
+def kcenter_greedy(vectors: torch.Tensor, n: int, init_dist=None, weight=None) -> dict:
+    """Greedy k-center (farthest-first) selection of `n` rows of `vectors` [P, H]: dict(picks [n] int64, gain [n] float32,
+    min_dist [P] float32, assign [P] int64) - rr_kcenter_f32, include/reactranker_hip.h states the arithmetic.
+
+    min_dist starts as init_dist (squared distance of every row to what is labelled already; None: +inf) and assign as -1; a
+    row that holds a NaN or an infinity gets min_dist NaN and is never picked.  Round t takes the row with the largest score
+    weight[i] * min_dist[i] (weight None: min_dist[i]) among the rows not taken yet whose min_dist is not NaN and, with
+    weights, whose weight lies in (0, +inf).  TIES go to the LOWER row index, so the picks are the same on every run.  Then
+    every row r with d(r, pick) < min_dist[r] gets that distance and assign[r] = t.  When no row is eligible the remaining
+    slots hold picks = -1, gain = -1.  gain[t] is the score the pick had when it was taken; min_dist / assign describe the
+    state after the last round (the coverage radius squared is min_dist.max(), the clustering is assign).
+    The rounds use d(r, c) = sum_h (x[r,h] - x[c,h])^2 in f32 (a picked row and its exact duplicates end at exactly 0);
+    an init_dist that comes from knn() carries knn's |q|^2 + |b|^2 - 2 q.b arithmetic instead - both are kept as given and
+    compared as numbers.
+    `vectors`: float32 GPU matrix with contiguous rows, any pitch.  Scratch comes from torch's allocator on the current
+    stream, and the call is ordered on that stream: n + 1 launches, no host synchronisation in between.
+    ValueError - before any launch - for CPU tensors, width 0, n outside [0, 65536], or an init_dist / weight that is not
+    P float32 values on the same device."""
+    _matrix(vectors, "vectors")
+    nn = int(n)
+    if nn != n or not (0 <= nn <= MAX_PICKS):
+        raise ValueError(f"kcenter_greedy: n must be an integer in [0, {MAX_PICKS}] (got {n!r})")
+    if vectors.shape[1] < 1:
+        raise ValueError("kcenter_greedy: rows of width 0")
+    x = _rows(vectors, "vectors")
+    P, H, dev = x.shape[0], x.shape[1], x.device
+    if P > 2 ** 31 - 1:
+        raise ValueError(f"kcenter_greedy: {P} rows (at most 2^31 - 1)")
+    init = None if init_dist is None else _per_row(init_dist, P, dev, "init_dist")
+    w = None if weight is None else _per_row(weight, P, dev, "weight")
+    picks = torch.empty(nn, dtype=torch.int32, device=dev)
+    gain = torch.empty(nn, dtype=torch.float32, device=dev)
+    min_dist = torch.empty(P, dtype=torch.float32, device=dev)
+    assign = torch.empty(P, dtype=torch.int32, device=dev)
+    if P > 0 or nn > 0:
+        with torch.cuda.device(dev):
+            nbytes = C.c_size_t()
+            check(lib().rr_kcenter_workspace_bytes(P, nn, C.byref(nbytes)), "rr_kcenter_workspace_bytes")
+            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            one = torch.empty(1, dtype=torch.float32, device=dev)         # (the C entry wants non-null pointers for empty arrays)
+            check(lib().rr_kcenter_f32(ptr(x) if P > 0 else ptr(one), x.stride(0) if P > 1 else H, P, H, nn, ptr(init), ptr(w),
+                                       ptr(picks) if nn > 0 else ptr(one), ptr(gain) if nn > 0 else ptr(one),
+                                       ptr(min_dist) if P > 0 else ptr(one), ptr(assign) if P > 0 else ptr(one), ptr(ws),
+                                       C.c_size_t(nbytes.value), stream()), "rr_kcenter_f32")
+    return dict(picks=picks.to(torch.int64), gain=gain, min_dist=min_dist, assign=assign.to(torch.int64))
+
+
+def acquire(model, bank: ReactionBank, pool_batches: Sequence, n: int, gpu, weight=None) -> dict:
+    """Which `n` candidates of a pool to label next: kcenter_greedy over the model's reaction vectors of `pool_batches`
+    ((r, p, scope, targets, add_features) tuples as reaction_vectors takes them; the targets are ignored and may be None;
+    batches without queries are skipped), started from init_dist = the squared distance of every pool row to its nearest row
+    of `bank` (knn with k = 1 and bank.sqnorm; an empty bank gives +inf everywhere).  One eval-mode forward per batch.
+    weight: None (pure coverage), a [rows] float32 tensor on the model's device (e.g. the std of
+    uncertainty.mc_dropout_predict), or 'std': the per-candidate predictive std of the model's distributional head, read
+    from the same forward as uncertainty.distribution_predict reads it (ValueError for a head that has none).
+    Returns dict(rows [n] int64 into the concatenated pool; batch, query, candidate [n] int64: the batch (counting only
+    batches with queries), the query inside it and the candidate inside that query; gain [n]; radius_before, radius_after:
+    0-dim tensors, sqrt of the largest min_dist before and after the picks over the rows whose vectors are finite (NaN when
+    there is no such row, +inf before the picks with an empty bank); min_dist [rows]; assign [rows]; init_dist [rows]: what
+    the rounds started from).  Padding picks (rows = -1) have batch = query = candidate = -1.
+    Ties go to the lower row index (kcenter_greedy).  init_dist carries knn's distance arithmetic (norms minus twice the dot
+    product), the rounds the difference form.  knn's form leaves a rounding residue (a few 2^-21 at unit scale) between a row
+    and itself, so one case is set exactly: a pool row whose nearest bank row holds the same bits starts at 0 - a reaction
+    that is labelled already scores 0 and is taken last, in index order, never on that residue.
+    model.training, StepPlan.keep_last and StepPlan.last are left as found."""
+    batches = [b for b in pool_batches if len(b[2]) > 0]
+    kind = None
+    if isinstance(weight, str):
+        if weight != "std":
+            raise ValueError(f"acquire: weight must be None, a tensor or 'std' (got {weight!r})")
+        kind = U._kind_of(model, None)
+    H = int(model.encoder.hidden_size)
+    if bank.vectors.shape[1] != H:
+        raise ValueError(f"the bank holds vectors of width {bank.vectors.shape[1]}, the model's are {H}")
+    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
+    vecs, stds = [], []
+    try:
+        model.eval()
+        StepPlan.keep_last = True
+        with torch.no_grad():
+            for r_batch, p_batch, scope, _targets, add in batches:
+                out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
+                vecs.append(vec[:, :H].contiguous())
+                if kind is not None:
+                    zeros = torch.zeros(vec.shape[0], dtype=torch.float32)
+                    stds.append(U.analytic_stats(out, scope, zeros, kind, gpu=gpu)["std"])
+    finally:
+        StepPlan.keep_last, StepPlan.last = old_keep, old_last
+        model.train(was_training)
+    dev = bank.vectors.device
+    vec = torch.cat(vecs, 0) if vecs else torch.zeros(0, H, dtype=torch.float32, device=dev)
+    if kind is not None:
+        weight = torch.cat(stds) if stds else torch.zeros(0, dtype=torch.float32, device=dev)
+    init = None
+    if len(bank) > 0 and vec.shape[0] > 0:
+        dist, idx, _ = bank.query(vec, 1)
+        dist, idx = dist[:, 0], idx[:, 0]
+        # a pool row that IS its nearest bank row (the same bits) is at distance 0; knn's norms-minus-dot arithmetic leaves a
+        # rounding residue there, on which reactions that are labelled already would otherwise be picked first
+        labelled = (idx >= 0) & (vec == bank.vectors[idx.clamp_min(0)]).all(dim=1)
+        init = torch.where(labelled, torch.zeros_like(dist), dist).contiguous()
+    res = kcenter_greedy(vec, n, init_dist=init, weight=weight)
+    rows, min_dist = res["picks"], res["min_dist"]
+    finite = ~torch.isnan(min_dist)
+    before = torch.full_like(min_dist, float("inf")) if init is None else init
+
+    def radius(d):                                         # (no finite row: sqrt(-inf) is the NaN the docstring promises)
+        if d.numel() == 0:
+            return torch.full((), float("nan"), dtype=torch.float32, device=vec.device)
+        return torch.where(finite, d, torch.full_like(d, float("-inf"))).max().sqrt()
+    sizes = [[int(c) for c in b[2]] for b in batches]
+    q_start = np.cumsum([0] + [c for s in sizes for c in s])[:-1]
+    q_batch = [j for j, s in enumerate(sizes) for _ in s]
+    q_index = [i for s in sizes for i in range(len(s))]
+    if len(q_batch) > 0:
+        as_dev = lambda a: torch.as_tensor(np.asarray(a, np.int64), device=rows.device)   # noqa: E731
+        q_start, q_batch, q_index = as_dev(q_start), as_dev(q_batch), as_dev(q_index)
+        q = (torch.bucketize(rows.clamp_min(0), q_start, right=True) - 1)
+        none = torch.full_like(rows, -1)
+        batch = torch.where(rows >= 0, q_batch[q], none)
+        query = torch.where(rows >= 0, q_index[q], none)
+        cand = torch.where(rows >= 0, rows - q_start[q], none)
+    else:
+        batch, query, cand = rows.clone(), rows.clone(), rows.clone()
+    return dict(rows=rows, batch=batch, query=query, candidate=cand, gain=res["gain"], radius_before=radius(before),
+                radius_after=radius(min_dist), min_dist=min_dist, assign=res["assign"], init_dist=before)
