@@ -37,6 +37,11 @@ for every candidate of the first validation query, its K nearest training reacti
 --acquire N (listwise task types, one process) treats the validation reactions as an unlabelled pool and prints which N of
 them to compute next (neighbors.acquire: greedy k-center from the bank of training embeddings, weighted by the head's own
 predictive std where it has one), with the pool's coverage radius before and after.
+
+--bootstrap N (listwise task types, one process) prints the validation metrics of the restored best checkpoint with their 95 %
+bootstrap intervals over the validation queries (significance.metric_intervals, N resamples), and the paired comparison of that
+checkpoint against the last epoch's weights on the same queries: the difference per metric, its interval and the two-sided
+sign-flip p-value (significance.paired_test, 5 N sign vectors).
 """
 import argparse
 import logging
@@ -49,7 +54,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import attribution, neighbors, ranknet_baseline, uncertainty   # noqa: E402
+from reactranker_amd import attribution, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -140,6 +145,22 @@ def reactions_to_compute_next(model, train_b, val_b, n, gpu, log):
                      t, row, bt, q, c, gain, int((res["assign"] == t).sum()))
 
 
+def intervals_and_comparison(model, val_b, last_table, n, gpu, log):
+    """What the validation means are worth: their bootstrap intervals, and whether the best checkpoint really beats the last epoch."""
+    val = [(b["r"], b["p"], b["scope"], b["targets"], b["add"]) for b in val_b]
+    iv = significance.metric_intervals(model, gpu, val, n_resamples=n)
+    log.info("validation metrics of the best checkpoint, 95 %% bootstrap intervals over %d queries (%d resamples):",
+             iv["top1"]["n"], n)
+    for name, v in iv.items():
+        log.info("  %-22s %8.4f  [%8.4f, %8.4f]  se %.4f  (n %d)", name, v["estimate"], v["lo"], v["hi"], v["se"], v["n"])
+    best_table, names = significance.query_table(model, gpu, val)
+    cmp = significance.paired_test(best_table, last_table, n_resamples=5 * n, names=names)
+    log.info("best checkpoint against the last epoch's weights, paired over the same queries (sign-flip test, %d sign vectors):", 5 * n)
+    for name, v in cmp.items():
+        log.info("  %-22s diff %+8.4f  [%+8.4f, %+8.4f]  p %.4f  (wins %d, ties %d, losses %d)", name, v["diff"], v["lo"], v["hi"],
+                 v["p_value"], v["wins"], v["ties"], v["losses"])
+
+
 PAIRWISE = {   # --task-type -> (train_strategy or None = --train-strategy, run_train's task_type)
     "ranknet": (None, "baseline"), "betanet": ("sum_session", "BetaNet"),
     "betanet_evidential": ("sum_session", "BetaNet_envidential"), "pair_baseline": ("baseline", "baseline"),
@@ -190,6 +211,8 @@ def main():
                     "calibration of the distance to the K nearest training reactions, and the first validation query's neighbours")
     ap.add_argument("--acquire", type=int, default=0, metavar="N", help="listwise task types: after training, which N validation "
                     "reactions to compute next (greedy k-center from the training embeddings) and the coverage radius before and after")
+    ap.add_argument("--bootstrap", type=int, default=0, metavar="N", help="listwise task types: after training, the validation metrics "
+                    "with 95 %% bootstrap intervals (N resamples of the queries) and the paired test of the best checkpoint against the last epoch")
     ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
@@ -244,6 +267,9 @@ def main():
         dist.barrier()                                    # rank 0 wrote the checkpoint
     if rank == 0:
         log.info("best epoch %d: NDCG@all %.4f top1 %.4f", best["epoch"], best["ndcg"][3], best["top1"])
+    last_table = None
+    if world == 1 and args.bootstrap:                     # the last epoch's per-query rows, before the best checkpoint replaces the weights
+        last_table = significance.query_table(model, args.gpu, [(b["r"], b["p"], b["scope"], b["targets"], b["add"]) for b in val_b])[0]
     load_checkpoint(args.checkpoint, model)
     if rank == 0:
         log.info("checkpoint %s restored", args.checkpoint)
@@ -275,6 +301,8 @@ def main():
         nearest_training_reactions(model, train_b, val_b, args.checkpoint, args.neighbors, args.gpu, log)
     if world == 1 and args.acquire:
         reactions_to_compute_next(model, train_b, val_b, args.acquire, args.gpu, log)
+    if world == 1 and args.bootstrap:
+        intervals_and_comparison(model, val_b, last_table, args.bootstrap, args.gpu, log)
     if world > 1:
         dist.destroy_process_group()
 

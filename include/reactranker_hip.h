@@ -1080,6 +1080,51 @@ int rr_kcenter_f32(const float* x, int64_t ld, int64_t P, int H, int n_pick,
 int rr_kcenter_blocks(void);
 int rr_kcenter_set_blocks(int blocks);
 
+/* Resampled column means of a per-query table: bootstrap intervals and paired sign-flip tests (additive: four new symbols, the
+ * ABI revision stays 8).  This library's own definition.  x [Q,M] (ld >= M) is f64 device memory, one row per query, one column
+ * per statistic (the tables of rr_ranking_metrics_f32 / rr_rank_correlation_f32, or differences of two such tables).
+ * The draw stream - splitmix64's finaliser, NOT the dropout hash, whose four elements per first-level word are correlated:
+ *   mix64(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)    (mod 2^64)
+ *   word(seed, n) = mix64(mix64(seed) + (n + 1) * 0x9E3779B97F4A7C15 mod 2^64),   n = 0, 1, 2, ...
+ *   draw(seed, j) = high 32 bits of word(seed, j >> 1) for even j, low 32 bits for odd j            (uint64 j)
+ *   Qe = Q rounded up to even;  resample b, position i (0 <= i < Q)  ->  j = b * Qe + i              (uint64 arithmetic)
+ *   row(b, i)  = (draw * Q) >> 32                        (bootstrap)
+ *   sign(b, i) = +1 if bit 31 of draw is 0, else -1      (sign flip)
+ * row() is not exactly uniform: a row gets floor or ceil of 2^32 / Q of the 2^32 draw values, a relative non-uniformity of at
+ * most Q / 2^32 - hence Q <= 2^20 (2.4e-4 at the limit, 2.3e-5 at 10^5 queries; RR_ERR_UNSUPPORTED above).
+ * The sums, all f64, every addition rounded on its own: lane l of a 64-lane wavefront owns the positions i of a resample with
+ * i mod 64 == l and walks them ascending; per column c it keeps acc = +0.0 and n = 0:
+ *   bootstrap:  v = x[row(b,i), c];  if v is not a NaN:  acc = acc + v,               n = n + 1
+ *   sign flip:  v = x[i, c];         if v is not a NaN:  acc = acc + sign(b,i) * v,   n = n + 1
+ * the 64 chains are joined by the butterfly over lane distances 32, 16, 8, 4, 2, 1 (acc = acc + acc of lane ^ distance, the
+ * same for n);  mean[k,c] = acc / n, NaN when n == 0;  count[k,c] = n.  +-inf entries take part in the sums.  Output row k is
+ * resample b = b0 + k, so a caller may cut B into calls and gets the rows of the uncut call bit for bit.  The bits of a result
+ * depend on x's values, Q, the column, seed and b only: not on ld, the pointer's alignment, B, where b0 cuts, the grid, the
+ * blocks setting or the width of the loads.
+ * How it runs: one launch on `stream` (none when B == 0), one wavefront per resample, resamples grid-strided, 256 threads; no
+ * atomics, no host synchronisation, no workspace, nothing that depends on an order of arrival.  Every element of mean (and of
+ * count when given) is written; Q == 0 gives NaN / 0 everywhere.  16-byte loads where x and ld allow, 8-byte loads otherwise -
+ * same values; nothing at or past column M of a row is read.
+ *   rr_resample_blocks / rr_resample_set_blocks   workgroups per launch: 0 = automatic (one resample per wavefront up to a
+ *                            cap by the table's size Q M 8: 4096 workgroups up to 32 KiB, two per CU up to 4 MiB, beyond that one
+ *                            per CU for the bootstrap and three per two CUs for the sign flip - measured),
+ *                            1 .. 4096 fixed.  The result is the same bits for every value; a process-wide
+ *                            word, NOT thread-safe, for the bench tool and the tests.
+ *   rr_resample_draw_host    draw(seed, j) on the host, so a test can hold the stream against its numpy restatement.
+ * Status, all before any launch: RR_ERR_ARG for a null x (with Q > 0) or mean, a negative Q, B or b0, M < 1, ld < M, an unknown
+ * mode or blocks outside [0, 4096]; RR_ERR_UNSUPPORTED for M > RR_RESAMPLE_MAX_COLS, Q > 2^20 or (b0 + B) * Qe not below 2^63. */
+#define RR_RESAMPLE_MAX_COLS 32
+#define RR_RESAMPLE_BOOTSTRAP 0
+#define RR_RESAMPLE_SIGNFLIP  1
+int rr_resample_means_f64(const double* x, int64_t ld, int64_t Q, int M,      /* [Q, M], ld >= M, device */
+                          int mode, uint64_t seed, int64_t b0, int64_t B,
+                          double* mean,      /* [B, M] */
+                          int32_t* count,    /* [B, M] or NULL */
+                          rr_stream_t stream);
+int rr_resample_blocks(void);
+int rr_resample_set_blocks(int blocks);
+uint32_t rr_resample_draw_host(uint64_t seed, uint64_t j);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

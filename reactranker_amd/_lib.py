@@ -314,6 +314,10 @@ _SIGS = {
                              C.c_size_t, c_stream]),
     "rr_kcenter_blocks": (i32, []),
     "rr_kcenter_set_blocks": (i32, [i32]),
+    "rr_resample_means_f64": (i32, [C.c_void_p, i64, i64, i32, i32, u64, i64, i64, C.c_void_p, c_i32p, c_stream]),
+    "rr_resample_blocks": (i32, []),
+    "rr_resample_set_blocks": (i32, [i32]),
+    "rr_resample_draw_host": (C.c_uint32, [u64, u64]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
@@ -355,6 +359,9 @@ RR_AMAX_LANES, RR_AMAX_STRIDE = 16, 32
 RR_AMAX_FLOATS = RR_AMAX_LANES * RR_AMAX_STRIDE
 RR_KNN_MAX_K = 64
 RR_KCENTER_MAX_PICKS = 65536
+RR_RESAMPLE_MAX_COLS = 32
+RR_RESAMPLE_MAX_ROWS = 1 << 20
+RR_RESAMPLE_BOOTSTRAP, RR_RESAMPLE_SIGNFLIP = 0, 1
 ABI_VERSION = 8
 (RR_SAVED_R_MSG, RR_SAVED_R_H, RR_SAVED_P_MSG, RR_SAVED_P_H, RR_SAVED_D_MSG, RR_SAVED_D_HID, RR_SAVED_VECS, RR_SAVED_FFN_H,
  RR_SAVED_R_MSG0_U, RR_SAVED_R_Z1_U) = range(10)

@@ -104,6 +104,25 @@ __host__ __device__ static inline bool rr_keep(uint64_t seed, uint64_t index, ui
   return rr_hash_u32(seed, index) >= threshold;
 }
 
+// Counter-based draw stream of the resampling kernels (csrc/resample.hip): NOT the dropout hash above, whose
+// four elements per first-level word are correlated (harmless for a mask, not for resampling indices).  splitmix64's finaliser,
+// as reactranker_amd.uncertainty._mix64 / sample_seed:
+//   word(seed, n) = mix64(mix64(seed) + (n + 1) * 0x9E3779B97F4A7C15),  draw(seed, j) = high half of word(seed, j >> 1) for even
+//   j, low half for odd j.  tests/resample_ref.py restates it bit for bit in numpy.
+__host__ __device__ static inline uint64_t rr_mix64(uint64_t x) {
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+// mixed_seed = rr_mix64(seed): the same for every word of a call, so the host computes it once
+__host__ __device__ static inline uint64_t rr_resample_word(uint64_t mixed_seed, uint64_t n) {
+  return rr_mix64(mixed_seed + (n + 1) * 0x9E3779B97F4A7C15ull);
+}
+__host__ __device__ static inline uint32_t rr_resample_draw(uint64_t seed, uint64_t j) {
+  const uint64_t w = rr_resample_word(rr_mix64(seed), j >> 1);
+  return (j & 1) ? static_cast<uint32_t>(w) : static_cast<uint32_t>(w >> 32);
+}
+
 #if defined(__HIPCC__)
 // torch.nn.Softplus(beta=1, threshold=20): x > 20 -> x, else log1p(exp(x)).
 __device__ static inline float rr_softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
