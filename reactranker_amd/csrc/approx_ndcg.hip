@@ -29,20 +29,14 @@ enum Mode { RANK_FWD, RANK_BWD, NDCG_FWD, NDCG_BWD, NDCG_STEP, NDCG_A };
 constexpr bool is_ndcg(int mode) { return mode >= NDCG_FWD; }
 constexpr int lds_arrays(int mode) { return mode == RANK_FWD ? 1 : (mode == RANK_BWD ? 2 : 5); }
 
-// rr_approx_ndcg_set_waves: 0 = by max_len, 1 or 4 = pinned.  A plain process-wide word that every launch reads: the setter
-// is for the bench tool and the tests, and is not safe against launches or setters on other threads.
-int g_waves = 0;
+WaveKnob g_knob;                     // rr_approx_ndcg_set_waves
 
 struct SumF64 {
-  __device__ static double wave(double v) { return wave_sum_f64(v); }
+  __device__ static double wave(double v) { return rr_wave_sum(v); }
   __device__ static double join(double a, double b) { return a + b; }
 };
 struct MaxF64 {
-  __device__ static double wave(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, RR_WAVE));
-    return v;
-  }
+  __device__ static double wave(double v) { return rr_wave_max(v); }
   __device__ static double join(double a, double b) { return fmax(a, b); }
 };
 
@@ -95,7 +89,7 @@ __device__ inline double soft_rank_of(const float* s, const float* t, int C, int
     f2 = j + 2 == i ? 0.f : f2;
     f3 = j + 3 == i ? 0.f : f3;
     r += (static_cast<double>(f0) + static_cast<double>(f1)) + (static_cast<double>(f2) + static_cast<double>(f3));
-    if constexpr (RT) {
+    if constexpr (RT) {                                            // rr_precedes, written out: the call costs NDCG_A two SGPRs
       const float4 t4 = *reinterpret_cast<const float4*>(t + j);
       rt += (t4.x > ti || (t4.x == ti && j < i)) ? 1 : 0;
       rt += (t4.y > ti || (t4.y == ti && j + 1 < i)) ? 1 : 0;
@@ -106,7 +100,7 @@ __device__ inline double soft_rank_of(const float* s, const float* t, int C, int
   for (int j = C4; j < C; ++j) {
     const float f = sigmoid_e((s[j] - si) * inv_t);
     r += j == i ? 0.0 : static_cast<double>(f);
-    if constexpr (RT) rt += (t[j] > ti || (t[j] == ti && j < i)) ? 1 : 0;
+    if constexpr (RT) rt += rr_precedes(t[j], j, ti, i) ? 1 : 0;
   }
   if constexpr (RT) *rt_out = rt;
   return r;
@@ -272,14 +266,11 @@ inline bool temperature_ok(float temperature) {
   return temperature > 0.f && temperature < INFINITY && 1.0f / temperature < INFINITY;
 }
 
-inline int waves_for(int max_len) { return g_waves != 0 ? g_waves : (max_len <= RR_WAVE ? 1 : 4); }
-
 template <int MODE>
 int approx_launch(ApproxArgs a, int Q, int max_len, hipStream_t s) {
-  a.L = max_len > 8 ? (max_len + 3) & ~3 : 8;                      // float4 reads; 4 doubles of reduction scratch
-  constexpr size_t bytes = lds_arrays(MODE) * sizeof(float);
-  return waves_for(max_len) == 1 ? launch_per_query(approx_ndcg_kernel<MODE, 1>, Q, a.L, bytes, RR_WAVE, s, a)
-                                 : launch_per_query(approx_ndcg_kernel<MODE, 4>, Q, a.L, bytes, 4 * RR_WAVE, s, a);
+  a.L = max_len > 8 ? list_words4(max_len) : 8;                    // float4 reads; 4 doubles of reduction scratch
+  return launch_waves(approx_ndcg_kernel<MODE, 1>, approx_ndcg_kernel<MODE, 4>, g_knob.pick(max_len), Q,
+                      a.L * lds_arrays(MODE) * sizeof(float), s, a);
 }
 
 inline bool rank_args_ok(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len, float temperature) {
@@ -308,13 +299,8 @@ inline ApproxArgs ndcg_args(const float* score, int64_t score_stride, const floa
 
 extern "C" {
 
-int rr_approx_ndcg_waves(void) { return g_waves; }
-
-int rr_approx_ndcg_set_waves(int waves) {
-  RR_CHECK_ARG(waves == 0 || waves == 1 || waves == 4);
-  g_waves = waves;
-  return RR_OK;
-}
+int rr_approx_ndcg_waves(void) { return g_knob.waves; }
+int rr_approx_ndcg_set_waves(int waves) { return g_knob.set(waves); }
 
 int rr_soft_rank_fwd_f32(const float* score, int64_t score_stride, const int32_t* seg_off, int Q, int max_len, float temperature,
                          float* rank, int64_t rank_stride, rr_stream_t stream) {

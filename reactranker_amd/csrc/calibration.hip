@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(kCalBlock) gauss_partial_kernel(const float* _
     }
   }
 #pragma unroll
-  for (int k = 0; k < kNSums; ++k) v[k] = wave_sum_f64(v[k]);
+  for (int k = 0; k < kNSums; ++k) v[k] = rr_wave_sum(v[k]);
   if ((tid & (RR_WAVE - 1)) == 0) {
 #pragma unroll
     for (int k = 0; k < kNSums; ++k) red[tid / RR_WAVE][k] = v[k];
@@ -103,39 +103,12 @@ __global__ void __launch_bounds__(kCalBlock) gauss_finish_kernel(const double* _
 }
 
 // ---------------------------------------------------------------- rr_top1_sets_f32
-// rr_top1_sets_set_waves: 0 = by max_len, 1 or 4 = pinned.  A plain process-wide word that every launch reads: the setter
-// is for the bench tool and the tests, and is not safe against launches or setters on other threads.
-int g_waves = 0;
+WaveKnob g_knob;                       // rr_top1_sets_set_waves
 
 constexpr int kTopScratch = 96;        // the true top's (before, rank, in_set) and four waves' partials of two reductions
 
-__device__ inline int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RR_WAVE);
-  return v;
-}
-
-__device__ inline int wave_min_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int w = __shfl_xor(v, o, RR_WAVE);
-    v = w < v ? w : v;
-  }
-  return v;
-}
-
-// (value, position) of the first maximum across the wave; position -1 = this lane saw no candidate
-__device__ inline void wave_first_max(float& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(v, o, RR_WAVE);
-    const int oi = __shfl_xor(i, o, RR_WAVE);
-    if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
-  }
-}
-
 __device__ inline void walk_step(float pj, int j, float pi, int i, int& ahead, double& before) {
-  const bool a = pj > pi || (pj == pi && j < i);
+  const bool a = rr_precedes(pj, j, pi, i);
   ahead += a ? 1 : 0;
   before += a ? static_cast<double>(pj) : 0.0;
 }
@@ -174,7 +147,7 @@ __global__ void __launch_bounds__(NW * RR_WAVE) top1_sets_kernel(const float* __
       if (bti < 0 || ti > bt) { bt = ti; bti = i; }                // i grows: a later equal value never replaces
     }
   }
-  wave_first_max(bt, bti);
+  rr_wave_first_max(bt, bti);
   if ((tid & (RR_WAVE - 1)) == 0) {
     red_v[wave] = bt;
     red_i[wave] = bti;
@@ -212,8 +185,8 @@ __global__ void __launch_bounds__(NW * RR_WAVE) top1_sets_kernel(const float* __
       *top_in = in ? 1 : 0;
     }
   }
-  n_in = wave_sum_i32(n_in);
-  first = wave_min_i32(first);
+  n_in = rr_wave_sum(n_in);
+  first = rr_wave_min(first);
   if ((tid & (RR_WAVE - 1)) == 0) {
     red_n[wave] = n_in;
     red_f[wave] = first;
@@ -248,16 +221,6 @@ __global__ void __launch_bounds__(NW * RR_WAVE) top1_sets_kernel(const float* __
   }
 }
 
-template <int NW>
-int top1_sets_launch(const float* p, int64_t p_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
-                     double tau, int32_t* rank, double* before, uint8_t* in_set, double* stats, hipStream_t s) {
-  const int L = max_len > 4 ? (max_len + 3) & ~3 : 4;              // float4 reads
-  const size_t lds = static_cast<size_t>(L) * sizeof(float) + kTopScratch;
-  if (set_lds(top1_sets_kernel<NW>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  top1_sets_kernel<NW><<<Q, NW * RR_WAVE, lds, s>>>(p, p_stride, targets, seg_off, L, tau, rank, before, in_set, stats);
-  return rr_launch_status();
-}
-
 }  // namespace
 
 extern "C" {
@@ -278,24 +241,17 @@ int rr_gauss_calibration_f64(const float* mean, const float* std_dev, const floa
   return rr_launch_status();
 }
 
-int rr_top1_sets_waves(void) { return g_waves; }
-
-int rr_top1_sets_set_waves(int waves) {
-  RR_CHECK_ARG(waves == 0 || waves == 1 || waves == 4);
-  g_waves = waves;
-  return RR_OK;
-}
+int rr_top1_sets_waves(void) { return g_knob.waves; }
+int rr_top1_sets_set_waves(int waves) { return g_knob.set(waves); }
 
 int rr_top1_sets_f32(const float* p, int64_t p_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
                      double tau, int32_t* rank, double* before, uint8_t* in_set, double* stats, rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(p, targets, seg_off, Q, max_len) && p_stride >= 1 && rank && before && in_set && stats);
   RR_CHECK_ARG(tau >= 0.0);                                        // (a NaN fails; +inf passes: every candidate is in the set)
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int waves = g_waves != 0 ? g_waves : (max_len <= RR_WAVE ? 1 : 4);
-  return waves == 1 ? top1_sets_launch<1>(p, p_stride, targets, seg_off, Q, max_len, tau, rank, before, in_set, stats, s)
-                    : top1_sets_launch<4>(p, p_stride, targets, seg_off, Q, max_len, tau, rank, before, in_set, stats, s);
+  const int L = list_words4(max_len);
+  return launch_waves(top1_sets_kernel<1>, top1_sets_kernel<4>, g_knob.pick(max_len), Q, L * sizeof(float) + kTopScratch,
+                      static_cast<hipStream_t>(stream), p, p_stride, targets, seg_off, L, tau, rank, before, in_set, stats);
 }
 
 }  // extern "C"

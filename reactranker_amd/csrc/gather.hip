@@ -176,8 +176,7 @@ __device__ __forceinline__ float amax_fold(float m, float v) { return fmaxf(m, f
 __device__ inline void amax_commit(float m, float* out) {      // every thread of the workgroup calls it (out is uniform)
   if (out == nullptr) return;
   __shared__ float amax_part[4];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = rr_wave_max(m);
   if ((threadIdx.x & 63) == 0) amax_part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -44,11 +44,6 @@ struct KcParams {
 
 typedef const __attribute__((address_space(1))) f32x4* kc_gptr4;
 
-// (s1, i1) comes before (s2, i2): score descending, then index ascending; a pair without a row comes last
-__device__ __forceinline__ bool kc_better(float s1, int i1, float s2, int i2) {
-  return i1 >= 0 && (i2 < 0 || s1 > s2 || (s1 == s2 && i1 < i2));
-}
-
 // columns c .. c + 3 of a row (c % 4 == 0, c < H); elements at or past H hold anything and are masked where they are used
 template <bool VEC>
 __device__ __forceinline__ f32x4 kc_load4(const float* row, int c, int H) {
@@ -71,12 +66,6 @@ __device__ __forceinline__ void kc_load_row(const float* row, int lane, int H, f
   }
 }
 
-__device__ __forceinline__ float kc_butterfly(float acc) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
-  return acc;
-}
-
 __device__ __forceinline__ float kc_step(float acc, float a, float b, bool on) {
   float t = a - b;
   t = on ? t : 0.f;                               // (acc >= 0, so acc + 0 is acc: a masked column is a skipped one)
@@ -90,7 +79,7 @@ __device__ __forceinline__ float kc_dist(const f32x4 (&a)[NG], const f32x4 (&b)[
   for (int j = 0; j < NG; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc = kc_step(acc, a[j][e], b[j][e], 4 * (lane + 64 * j) + e < H);
-  return kc_butterfly(acc);
+  return rr_wave_sum(acc);
 }
 
 // any width: the same chain with both rows read group by group
@@ -105,7 +94,7 @@ __device__ __forceinline__ float kc_dist_any(const float* row, const float* cent
       for (int e = 0; e < 4; ++e) acc = kc_step(acc, a[e], b[e], c + e < H);
     }
   }
-  return kc_butterfly(acc);
+  return rr_wave_sum(acc);
 }
 
 __device__ __forceinline__ bool kc_finite(float v) { return fabsf(v) < __builtin_inff(); }
@@ -151,20 +140,15 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
     int bi = -1;
     for (int k = tid; k < static_cast<int>(gridDim.x); k += KC_NT) {
       const KcPair q = p.prev[k];
-      if (kc_better(q.s, q.i, bs, bi)) { bs = q.s; bi = q.i; }
+      if (rr_first_max_replaces(q.s, q.i, bs, bi)) { bs = q.s; bi = q.i; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float os = __shfl_xor(bs, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (kc_better(os, oi, bs, bi)) { bs = os; bi = oi; }
-    }
+    rr_wave_first_max(bs, bi);
     if (lane == 0) { s_prev[wave].s = bs; s_prev[wave].i = bi; }
     __syncthreads();
     bs = s_prev[0].s; bi = s_prev[0].i;
 #pragma unroll
     for (int w = 1; w < KC_WAVES; ++w)
-      if (kc_better(s_prev[w].s, s_prev[w].i, bs, bi)) { bs = s_prev[w].s; bi = s_prev[w].i; }
+      if (rr_first_max_replaces(s_prev[w].s, s_prev[w].i, bs, bi)) { bs = s_prev[w].s; bi = s_prev[w].i; }
     c = __builtin_amdgcn_readfirstlane(bi);
     if (blockIdx.x == 0 && tid == 0) {
       p.picks[t - 1] = c;
@@ -215,7 +199,7 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
     }
     if (e && !p.last) {
       const float s = weighted ? w * md : md;
-      if (kc_better(s, static_cast<int>(r), best_s, best_i)) { best_s = s; best_i = static_cast<int>(r); }
+      if (rr_first_max_replaces(s, static_cast<int>(r), best_s, best_i)) { best_s = s; best_i = static_cast<int>(r); }
     }
   };
 
@@ -252,7 +236,7 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
     int bi = s_out[0].i;
 #pragma unroll
     for (int w = 1; w < KC_WAVES; ++w)
-      if (kc_better(s_out[w].s, s_out[w].i, bs, bi)) { bs = s_out[w].s; bi = s_out[w].i; }
+      if (rr_first_max_replaces(s_out[w].s, s_out[w].i, bs, bi)) { bs = s_out[w].s; bi = s_out[w].i; }
     p.out[blockIdx.x].s = bs;
     p.out[blockIdx.x].i = bi;
   }

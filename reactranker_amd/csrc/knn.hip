@@ -296,8 +296,7 @@ __global__ void __launch_bounds__(KN_NT) row_sqnorm_kernel(const float* x, int64
     const float v = row[h];
     s += v * v;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = rr_wave_sum(s);
   if (lane == 0) out[r] = s;
 }
 

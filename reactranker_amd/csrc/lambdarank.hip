@@ -29,8 +29,8 @@ __device__ inline int lambdarank_prepare(const float* s, const float* t, float* 
     int rp = 0, rt = 0;                                             // 0-based ranks by score and by target
     for (int j = 0; j < C; ++j) {
       const float sj = s[j], tj = t[j];
-      rp += (sj > si || (sj == si && j < i)) ? 1 : 0;
-      rt += (tj > ti || (tj == ti && j < i)) ? 1 : 0;
+      rp += rr_precedes(sj, j, si, i) ? 1 : 0;
+      rt += rr_precedes(tj, j, ti, i) ? 1 : 0;
       npos += (ti > tj) ? 1 : 0;
     }
     const double g = exp(static_cast<double>(ti) - static_cast<double>(tmax));
@@ -39,9 +39,8 @@ __device__ inline int lambdarank_prepare(const float* s, const float* t, float* 
     if (rt < k) dcg += g / log2(static_cast<double>(rt) + 2.0);
     gn[i] = static_cast<float>(g);
   }
-  dcg = wave_sum_f64(dcg);                                          // >= 1: the best target has gain 1 at position 1
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) npos += __shfl_xor(npos, o, RR_WAVE);
+  dcg = rr_wave_sum(dcg);                                           // >= 1: the best target has gain 1 at position 1
+  npos = rr_wave_sum(npos);
   for (int i = lane; i < C; i += RR_WAVE) gn[i] = static_cast<float>(static_cast<double>(gn[i]) / dcg);
   wave_sync();
   return npos;
@@ -76,7 +75,7 @@ __device__ inline double lambdarank_pairs(const float* s, const float* t, const 
     }
     if constexpr (GRAD) lam[i] = static_cast<float>(li);
   }
-  return LOSS ? wave_sum_f64(acc) : 0.0;
+  return LOSS ? rr_wave_sum(acc) : 0.0;
 }
 
 // MODE 0: forward (partial).  MODE 1: backward (dscore = gloss[0] * d loss_sum / d score).  MODE 2: step - both, for the

@@ -177,10 +177,8 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_fwd_kernel(const float* __res
       }
     }
   }
-  int tot = npos;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, RR_WAVE);
-  acc = wave_sum_f64(acc);
+  const int tot = rr_wave_sum(npos);
+  acc = rr_wave_sum(acc);
   if (lane == 0) {
     partial[2 * q] = tot > 0 ? static_cast<float>(acc) : 0.f;      // pair-less queries are skipped, :103-104
     reinterpret_cast<int32_t*>(partial)[2 * q + 1] = 2 * tot;      // num_pairs, train_pairwise.py:106
@@ -221,9 +219,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_bwd_kernel(const float* __res
     }
     lamv[i] = static_cast<float>(lam);
   }
-  int tot = npos;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, RR_WAVE);
+  const int tot = rr_wave_sum(npos);
   // C_ij is symmetric, so d(sum_ij C_ij)/ds_i = 2 * lambda_i (mode 0); mode 1 = accelerate_grad's row sum
   const float g = tot > 0 ? gloss[0] * (mode == 0 ? 2.0f : 1.0f) : 0.f;
   for (int i = lane; i < C; i += RR_WAVE) dscore[static_cast<int64_t>(off + i) * dstride] = g * lamv[i];
@@ -316,8 +312,8 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
     int rp = 0, rt = 0;
     for (int j = 0; j < C; ++j) {
       const float sj = s[j], tj = t[j];
-      rp += (sj > si || (sj == si && j < i)) ? 1 : 0;
-      rt += (tj > ti || (tj == ti && j < i)) ? 1 : 0;
+      rp += rr_precedes(sj, j, si, i) ? 1 : 0;
+      rt += rr_precedes(tj, j, ti, i) ? 1 : 0;
     }
     po[rp] = static_cast<uint16_t>(i);
     to[rt] = static_cast<uint16_t>(i);
@@ -337,8 +333,8 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
     hits += in;
     if (i == 0) hit0 = in;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { hits += __shfl_xor(hits, o, RR_WAVE); hit0 += __shfl_xor(hit0, o, RR_WAVE); }
+  hits = rr_wave_sum(hits);
+  hit0 = rr_wave_sum(hit0);
   // DCG sums with exp gains (compute_NDCG) over the first len25 / all positions, and exp2 gains over the first 10
   double d25 = 0, i25 = 0, dall = 0, iall = 0, d10 = 0, i10 = 0;
   for (int i = lane; i < C; i += RR_WAVE) {
@@ -352,9 +348,9 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
       i10 += (exp2(static_cast<double>(t[to[i]])) - 1.0) / disc;
     }
   }
-  d25 = wave_sum_f64(d25); i25 = wave_sum_f64(i25);
-  dall = wave_sum_f64(dall); iall = wave_sum_f64(iall);
-  d10 = wave_sum_f64(d10); i10 = wave_sum_f64(i10);
+  d25 = rr_wave_sum(d25); i25 = rr_wave_sum(i25);
+  dall = rr_wave_sum(dall); iall = rr_wave_sum(iall);
+  d10 = rr_wave_sum(d10); i10 = rr_wave_sum(i10);
   // evaluate_top_scores (eval.py:76-177) at its `ratio`: cut = python round(C * ratio), at least 1 (:144-146);
   // recall of the predicted top-cut in the target top-cut (:147-151) and the TARGET's first maximum looked up in the
   // predicted top-cut (:156-159).  The first maximum (list.index(max)) is rank 0 of the stable descending order.
@@ -368,8 +364,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
     for (int j = 0; j < lenr; ++j) in |= (to[j] == pi) ? 1 : 0;
     hitr += in;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) hitr += __shfl_xor(hitr, o, RR_WAVE);
+  hitr = rr_wave_sum(hitr);
   // calculate_ndcg (eval.py:329-457): KL(softmax(targets) || softmax(scores)) with un-shifted f32 exponentials
   // (:401-404: an overflowing exp gives inf / inf = NaN there and here), and NDCG over the first ceil(C * cut)
   // positions of the TARGET order with rank-derived gains C + 1 - predicted rank (:406-425, cal_NDCG :309-325).
@@ -378,7 +373,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
     se_t += static_cast<double>(expf(t[i]));
     se_s += static_cast<double>(expf(s[i]));
   }
-  se_t = wave_sum_f64(se_t); se_s = wave_sum_f64(se_s);
+  se_t = rr_wave_sum(se_t); se_s = rr_wave_sum(se_s);
   int ncut = static_cast<int>(ceil(static_cast<double>(C) * ndcg_cut));
   if (ncut > C) ncut = C;
   double kl = 0, dcut = 0, icut = 0;
@@ -391,13 +386,13 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
       const int cand = to[i];
       const float sc = s[cand];
       int rank = 0;
-      for (int j = 0; j < C; ++j) rank += (s[j] > sc || (s[j] == sc && tr[j] < i)) ? 1 : 0;
+      for (int j = 0; j < C; ++j) rank += rr_precedes(s[j], tr[j], sc, i) ? 1 : 0;
       const double disc = log2(static_cast<double>(i) + 2.0);
       dcut += static_cast<double>(C - rank) / disc;
       icut += static_cast<double>(C - i) / disc;
     }
   }
-  kl = wave_sum_f64(kl); dcut = wave_sum_f64(dcut); icut = wave_sum_f64(icut);
+  kl = rr_wave_sum(kl); dcut = rr_wave_sum(dcut); icut = rr_wave_sum(icut);
   if (lane == 0) {
     st[8] = (pr[to[0]] < lenr) ? 1.0 : 0.0;
     st[9] = dcut / icut;

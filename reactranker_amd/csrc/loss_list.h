@@ -40,10 +40,7 @@ __device__ inline void rank_sort(const ListView& v, int C, int lane) {
   for (int i = lane; i < C; i += RR_WAVE) {
     const float ti = v.t[i];
     int r = 0;
-    for (int j = 0; j < C; ++j) {
-      const float tj = v.t[j];
-      r += (tj > ti || (tj == ti && j < i)) ? 1 : 0;
-    }
+    for (int j = 0; j < C; ++j) r += rr_precedes(v.t[j], j, ti, i) ? 1 : 0;
     v.ss[r] = v.s[i];
     v.perm[r] = i;
   }

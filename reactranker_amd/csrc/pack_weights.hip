@@ -99,8 +99,7 @@ __global__ void __launch_bounds__(1024) pack_scale_kernel(const PackMany P) {
   }
   for (; e < total; e += ST) m4[0] = fmaxf(m4[0], val(e));
   float m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = rr_wave_max(m);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -175,8 +174,7 @@ __global__ void __launch_bounds__(256) amax_kernel(const float* __restrict__ x, 
     }
   }
   float r = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) r = fmaxf(r, __shfl_xor(r, o));
+  r = rr_wave_max(r);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = r;
   __syncthreads();
   if (threadIdx.x == 0) {

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(RR_WAVE) betanet_fwd_kernel(const float* __res
     }
     acc += row;
   }
-  acc = wave_sum_f64(acc);
+  acc = rr_wave_sum(acc);
   if (lane == 0) partial[q] = acc;
 }
 
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(RR_WAVE) beta_evi_kernel(const float* __restri
       acc += row;
   }
   if (!BWD) {
-    acc = wave_sum_f64(acc);
+    acc = rr_wave_sum(acc);
     if (lane == 0) partial[q] = acc;
   }
 }
@@ -265,12 +265,9 @@ __global__ void __launch_bounds__(RR_WAVE) pairwise_eval_kernel(const float* __r
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    npos += __shfl_xor(npos, o, RR_WAVE);
-    mism += __shfl_xor(mism, o, RR_WAVE);
-  }
-  ce = wave_sum_f64(ce);
+  npos = rr_wave_sum(npos);
+  mism = rr_wave_sum(mism);
+  ce = rr_wave_sum(ce);
   if (lane == 0) {
     double* o = qstats + 4 * static_cast<int64_t>(q);
     o[0] = npos;

@@ -35,9 +35,7 @@
 
 namespace {
 
-// rr_rank_correlation_set_waves: 0 = by max_len, 1 or 4 = pinned.  A plain process-wide word that every launch reads: the
-// setter is for the bench tool and the tests, and is not safe against launches or setters on other threads.
-int g_waves = 0;
+WaveKnob g_knob;                     // rr_rank_correlation_set_waves
 
 constexpr int kSums = 9;             // 2P, 2D, 2X, 2Y, sum ab, sum aa, sum bb, first maximum of t, first maximum of s
 constexpr int kScratch = 4 * (kSums + 1) * sizeof(long long);      // four waves' partials of phase 3 and of phase 4
@@ -54,21 +52,6 @@ __device__ inline void count_pair(float sj, float tj, float si, float ti, PairCo
   n.lt += tl ? 1 : 0;
   n.conc += ((sg && tg) || (sl && tl)) ? 1 : 0;
   n.disc += ((sg && tl) || (sl && tg)) ? 1 : 0;
-}
-
-__device__ inline long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RR_WAVE);
-  return v;
-}
-
-__device__ inline long long wave_min_i64(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long w = __shfl_xor(v, o, RR_WAVE);
-    v = w < v ? w : v;
-  }
-  return v;
 }
 
 template <int NW>
@@ -124,7 +107,7 @@ __global__ void __launch_bounds__(NW * RR_WAVE) rank_corr_kernel(const float* __
   }
 
 #pragma unroll
-  for (int k = 0; k < kSums; ++k) v[k] = k < 7 ? wave_sum_i64(v[k]) : wave_min_i64(v[k]);
+  for (int k = 0; k < kSums; ++k) v[k] = k < 7 ? rr_wave_sum(v[k]) : rr_wave_min(v[k]);
   if constexpr (NW > 1) {
     if ((tid & (RR_WAVE - 1)) == 0) {
 #pragma unroll
@@ -147,8 +130,8 @@ __global__ void __launch_bounds__(NW * RR_WAVE) rank_corr_kernel(const float* __
   const int it = static_cast<int>(v[7]), is = static_cast<int>(v[8]);
   const float sx = s[it];
   long long rank = 0;
-  for (int j = tid; j < C; j += NT) rank += (s[j] > sx || (s[j] == sx && j < it)) ? 1 : 0;
-  rank = wave_sum_i64(rank);
+  for (int j = tid; j < C; j += NT) rank += rr_precedes(s[j], j, sx, it) ? 1 : 0;
+  rank = rr_wave_sum(rank);
   if constexpr (NW > 1) {
     if ((tid & (RR_WAVE - 1)) == 0) red2[tid / RR_WAVE] = rank;
     __syncthreads();
@@ -171,37 +154,20 @@ __global__ void __launch_bounds__(NW * RR_WAVE) rank_corr_kernel(const float* __
   }
 }
 
-template <int NW>
-int rank_corr_launch(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
-                     double* stats, hipStream_t s) {
-  const int L = max_len > 4 ? (max_len + 3) & ~3 : 4;              // float4 reads
-  const size_t lds = static_cast<size_t>(L) * 2 * sizeof(float) + kScratch;
-  if (set_lds(rank_corr_kernel<NW>, lds) != RR_OK) return RR_ERR_LAUNCH;
-  rank_corr_kernel<NW><<<Q, NW * RR_WAVE, lds, s>>>(score, score_stride, targets, seg_off, L, stats);
-  return rr_launch_status();
-}
-
 }  // namespace
 
 extern "C" {
 
-int rr_rank_correlation_waves(void) { return g_waves; }
-
-int rr_rank_correlation_set_waves(int waves) {
-  RR_CHECK_ARG(waves == 0 || waves == 1 || waves == 4);
-  g_waves = waves;
-  return RR_OK;
-}
+int rr_rank_correlation_waves(void) { return g_knob.waves; }
+int rr_rank_correlation_set_waves(int waves) { return g_knob.set(waves); }
 
 int rr_rank_correlation_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                             int max_len, double* stats, rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && score_stride >= 1 && stats);
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (Q == 0) return RR_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int waves = g_waves != 0 ? g_waves : (max_len <= RR_WAVE ? 1 : 4);
-  return waves == 1 ? rank_corr_launch<1>(score, score_stride, targets, seg_off, Q, max_len, stats, s)
-                    : rank_corr_launch<4>(score, score_stride, targets, seg_off, Q, max_len, stats, s);
+  const int L = list_words4(max_len);
+  return launch_waves(rank_corr_kernel<1>, rank_corr_kernel<4>, g_knob.pick(max_len), Q, L * 2 * sizeof(float) + kScratch,
+                      static_cast<hipStream_t>(stream), score, score_stride, targets, seg_off, L, stats);
 }
 
 }  // extern "C"

@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(RS_NT) rs_kernel(const RsParams p) {
       }
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
-        acc[c] = wave_sum_f64(acc[c]);
+        acc[c] = rr_wave_sum(acc[c]);
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) n[c] += __shfl_xor(n[c], off, 64);
       }

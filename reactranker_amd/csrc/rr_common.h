@@ -1,8 +1,11 @@
-// Shared host/device helpers for the gfx950 kernels behind include/reactranker_hip.h.
+// Shared host/device helpers for the gfx950 kernels behind include/reactranker_hip.h: status and grid helpers, the magnitude
+// slots, the counter-based random streams, and on the device the wave64 reductions, the ordering rule of every ranking kernel
+// (rr_precedes) and the first maximum built on it.
 #pragma once
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
-#else            // host-only translation unit (the AddressSanitizer build of pack.cpp: `make asan`, plain g++)
+#include <type_traits>
+#else           // host-only translation unit (the AddressSanitizer build of pack.cpp: `make asan`, plain g++)
 #define __host__
 #define __device__
 #endif
@@ -129,15 +132,49 @@ __device__ static inline float rr_softplus(float x) { return x > 20.0f ? x : log
 __device__ static inline float rr_softplus_grad(float x) { return x > 20.0f ? 1.0f : 1.0f / (1.0f + expf(-x)); }
 
 // ---- wave64 reductions / scans (all 64 lanes must be active) ---------------------------
-__device__ static inline float rr_wave_sum(float v) {
+// The xor butterfly 32, 16, ..., 1 with v = op(v, shuffled), the one copy of that loop: every lane ends with the same value, and
+// a given op gives the same bits wherever it is used.  T is float, double, int, unsigned or long long.
+template <typename T, typename Op>
+__device__ __forceinline__ T rr_wave_reduce(T v, Op op) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_xor(v, off, RR_WAVE));
   return v;
 }
-__device__ static inline float rr_wave_max(float v) {
+template <typename T>
+__device__ __forceinline__ T rr_wave_sum(T v) {
+  return rr_wave_reduce(v, [](T a, T b) { return a + b; });
+}
+template <typename T>
+__device__ __forceinline__ T rr_wave_min(T v) {
+  return rr_wave_reduce(v, [](T a, T b) { return b < a ? b : a; });
+}
+// float and double: fmaxf / fmax, so a NaN loses against a number
+template <typename T>
+__device__ __forceinline__ T rr_wave_max(T v) {
+  return rr_wave_reduce(v, [](T a, T b) {
+    if constexpr (std::is_floating_point<T>::value) return fmax(a, b);
+    else return b > a ? b : a;
+  });
+}
+
+// THE order of the library - every rank, every `order`, every tie-break: candidate j (value xj) comes before candidate i (value
+// xi) in the stable descending order, ties by list position.  A comparison with a NaN is false, so a NaN precedes nothing and
+// nothing precedes it.
+__device__ __forceinline__ bool rr_precedes(float xj, int j, float xi, int i) { return xj > xi || (xj == xi && j < i); }
+
+// The first maximum - rank 0 of that order - kept as a running (value, position) pair, position -1 = none yet: does (ov, oi)
+// replace (v, i)?  Written out, not built on rr_precedes: that form costs the top-1 kernels 25 instructions each.
+__device__ __forceinline__ bool rr_first_max_replaces(float ov, int oi, float v, int i) {
+  return oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i));
+}
+// (value, position) of the first maximum across the wave, valid in every lane; position -1 = this lane saw no candidate
+__device__ __forceinline__ void rr_wave_first_max(float& v, int& i) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  return v;
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off, RR_WAVE);
+    const int oi = __shfl_xor(i, off, RR_WAVE);
+    if (rr_first_max_replaces(ov, oi, v, i)) { v = ov; i = oi; }
+  }
 }
 // inclusive prefix sum across lanes (lane 0 .. lane 63)
 __device__ static inline float rr_wave_incl_scan(float v, int lane) {

@@ -26,16 +26,6 @@ namespace {
 constexpr int kCalBlock = RR_UQ_CAL_BLOCK;
 static_assert(kCalBlock % RR_WAVE == 0, "the calibration block is whole wavefronts");
 
-// (value, position) of the first maximum across the wave; position -1 = this lane saw no candidate
-__device__ inline void wave_first_max(float& v, int& i) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off, 64);
-    const int oi = __shfl_xor(i, off, 64);
-    if (oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i))) { v = ov; i = oi; }
-  }
-}
-
 __global__ void __launch_bounds__(RR_WAVE) mc_stats_kernel(const float* __restrict__ samples, int64_t sstride, int T,
                                                            const float* __restrict__ targets,
                                                            const int32_t* __restrict__ seg_off, int L,
@@ -64,10 +54,7 @@ __global__ void __launch_bounds__(RR_WAVE) mc_stats_kernel(const float* __restri
     for (int i = lane; i < C; i += RR_WAVE) {                 // stable descending rank (ranking_metrics_kernel's rule)
       const float si = s[i];
       int r = 0;
-      for (int j = 0; j < C; ++j) {
-        const float sj = s[j];
-        r += (sj > si || (sj == si && j < i)) ? 1 : 0;
-      }
+      for (int j = 0; j < C; ++j) r += rr_precedes(s[j], j, si, i) ? 1 : 0;
       rsum[i] += static_cast<uint32_t>(r);
       top1[i] += r == 0 ? 1u : 0u;
     }
@@ -100,10 +87,10 @@ __global__ void __launch_bounds__(RR_WAVE) mc_stats_kernel(const float* __restri
     const float ti = targets[off + i];
     if (bti < 0 || ti > bt) { bt = ti; bti = i; }
   }
-  ent = wave_sum_f64(ent);
-  sdsum = wave_sum_f64(sdsum);
-  wave_first_max(bm, bmi);
-  wave_first_max(bt, bti);
+  ent = rr_wave_sum(ent);
+  sdsum = rr_wave_sum(sdsum);
+  rr_wave_first_max(bm, bmi);
+  rr_wave_first_max(bt, bti);
   if (lane == 0) {
     qs[0] = ent;
     qs[1] = static_cast<double>(top1[bti]) / Td;
@@ -257,11 +244,11 @@ __global__ void __launch_bounds__(RR_WAVE) analytic_qstats_kernel(const float* _
     if (bmi < 0 || mf > bm) { bm = mf; bmi = i; }
     if (bti < 0 || ti > bt) { bt = ti; bti = i; }
   }
-  ent = wave_sum_f64(ent);
-  sdsum = wave_sum_f64(sdsum);
-  psum = wave_sum_f64(psum);
-  wave_first_max(bm, bmi);
-  wave_first_max(bt, bti);
+  ent = rr_wave_sum(ent);
+  sdsum = rr_wave_sum(sdsum);
+  psum = rr_wave_sum(psum);
+  rr_wave_first_max(bm, bmi);
+  rr_wave_first_max(bt, bti);
   if (lane == 0) {
     qs[0] = ent;
     qs[1] = static_cast<double>(p_top1[off + bti]);
@@ -313,7 +300,7 @@ __device__ inline int64_t removed_rows(double f, int64_t n) {       // k = floor
 // sum of v over the block in a fixed order (wave trees, then the waves in order); the result is valid in thread 0
 __device__ inline double block_sum(double v, double* red) {
   const int lane = threadIdx.x & (RR_WAVE - 1), w = threadIdx.x / RR_WAVE;
-  v = wave_sum_f64(v);
+  v = rr_wave_sum(v);
   if (lane == 0) red[w] = v;
   __syncthreads();
   double s = 0.0;
@@ -419,7 +406,7 @@ int rr_analytic_rank_stats_f32(const float* out, int64_t ld, int kind, const flo
   RR_CHECK_ARG(ld >= (kind == RR_MOMENT_NIG ? 4 : 2));
   if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   if (Q == 0) return RR_OK;
-  const int L = max_len > 0 ? (max_len + 3) & ~3 : 4;
+  const int L = list_words4(max_len);
   const size_t lds = static_cast<size_t>(L) * 3 * sizeof(float);
   if (set_lds(analytic_rank_kernel, lds) != RR_OK) return RR_ERR_LAUNCH;
   hipStream_t s = static_cast<hipStream_t>(stream);

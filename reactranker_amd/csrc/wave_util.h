@@ -1,7 +1,9 @@
-// Helpers of the one-wavefront-per-list kernels (loss.hip, task_loss.hip, pairwise.hip, uq.hip): the list-length cap,
-// wave-level synchronisation, the f64 wave sum, and on the host side the dynamic-LDS opt-in, the argument check and the one
-// launch of a "one workgroup per query" kernel (launch_per_query).  Everything lives in an unnamed namespace: each
-// translation unit gets its own copy.
+// Helpers of the per-list kernels - one wavefront per list (loss.hip, task_loss.hip, pairwise.hip, lambdarank.hip, uq.hip) or one
+// workgroup of one or four (approx_ndcg.hip, rank_corr.hip, calibration.hip): the list-length cap and wave-level synchronisation;
+// on the host side the dynamic-LDS opt-in, the argument check, the words per staged array (list_words, list_words4), the wave
+// knob of the one-or-four-wave kernels (WaveKnob) and the one launch of a "one workgroup per query" kernel (launch_per_query,
+// launch_per_query_bytes, launch_waves).  The wave reductions and the ordering rule are in rr_common.h.  Everything lives in an
+// unnamed namespace: each translation unit gets its own copy.
 #pragma once
 #include <atomic>
 
@@ -22,12 +24,6 @@ __device__ inline void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 template <typename Kern>
 int set_lds(Kern k, size_t bytes) {
   if (bytes > 65536) {
@@ -46,16 +42,43 @@ inline bool list_args_ok(const void* a, const void* t, const int32_t* seg, int Q
 // words per staged array of a window whose longest list has max_len candidates (a window of empty lists still gets one)
 inline int list_words(int max_len) { return max_len > 0 ? max_len : 1; }
 
-// The launch of a "one workgroup per query" kernel: Q workgroups of `threads` threads, each with L * bytes_per_cand bytes of
-// dynamic LDS.  L is the kernel's words per staged array - list_words(max_len) unless the kernel pads its arrays - and the
-// caller passes it among `args` as well, wherever the kernel takes it.  Q == 0 launches nothing and is no error.
+// the same rounded up to whole float4s, for the kernels that walk a list four candidates at a time (16-byte LDS reads)
+inline int list_words4(int max_len) { return max_len > 4 ? (max_len + 3) & ~3 : 4; }
+
+// The wave count of a kernel that gives a query one wavefront while the window's longest list has at most 64 candidates and
+// four above: 0 = by max_len, 1 or 4 = pinned.  One instance per entry-point family, a plain process-wide word that every
+// launch reads: set() is for the bench tools and the tests, and is not safe against launches or setters on other threads.
+struct WaveKnob {
+  int waves = 0;
+  int set(int w) {
+    RR_CHECK_ARG(w == 0 || w == 1 || w == 4);
+    waves = w;
+    return RR_OK;
+  }
+  int pick(int max_len) const { return waves != 0 ? waves : (max_len <= RR_WAVE ? 1 : 4); }
+};
+
+// The launch of a "one workgroup per query" kernel: Q workgroups of `threads` threads, each with `lds` bytes of dynamic LDS.
+// Q == 0 launches nothing and is no error.
 template <typename Kern, typename... Args>
-int launch_per_query(Kern kern, int Q, int L, size_t bytes_per_cand, int threads, hipStream_t s, Args... args) {
+int launch_per_query_bytes(Kern kern, int Q, size_t lds, int threads, hipStream_t s, Args... args) {
   if (Q == 0) return RR_OK;
-  const size_t lds = static_cast<size_t>(L) * bytes_per_cand;
   if (set_lds(kern, lds) != RR_OK) return RR_ERR_LAUNCH;
   kern<<<Q, threads, lds, s>>>(args...);
   return rr_launch_status();
+}
+
+// The same with L * bytes_per_cand bytes.  L is the kernel's words per staged array - list_words(max_len) unless the kernel
+// pads its arrays - and the caller passes it among `args` as well, wherever the kernel takes it.
+template <typename Kern, typename... Args>
+int launch_per_query(Kern kern, int Q, int L, size_t bytes_per_cand, int threads, hipStream_t s, Args... args) {
+  return launch_per_query_bytes(kern, Q, static_cast<size_t>(L) * bytes_per_cand, threads, s, args...);
+}
+
+// The one-wave or the four-wave instantiation of a kernel, `waves` (1 or 4) wavefronts per query
+template <typename Kern, typename... Args>
+int launch_waves(Kern kern1, Kern kern4, int waves, int Q, size_t lds, hipStream_t s, Args... args) {
+  return launch_per_query_bytes(waves == 1 ? kern1 : kern4, Q, lds, waves * RR_WAVE, s, args...);
 }
 
 }  // namespace
