@@ -38,6 +38,14 @@ for every candidate of the first validation query, its K nearest training reacti
 them to compute next (neighbors.acquire: greedy k-center from the bank of training embeddings, weighted by the head's own
 predictive std where it has one), with the pool's coverage radius before and after.
 
+--mahalanobis [--neighbors K] (listwise task types, one process) logs the applicability calibration with both distances side
+by side: the mean distance to the K (default 8) nearest training reactions and the Mahalanobis distance to the Gaussian of the
+training embeddings (latent_gaussian.EmbeddingGaussian, neighbors.evaluate_applicability(method='mahalanobis')).
+
+--embedding-map N (listwise task types, one process) logs the explained variance of the first N principal components of the
+training embeddings and writes the validation reactions' scores on them next to the checkpoint (<checkpoint>.embedding_map.pt:
+scores [M, N], targets, scope, explained_variance_ratio).
+
 --bootstrap N (listwise task types, one process) prints the validation metrics of the restored best checkpoint with their 95 %
 bootstrap intervals over the validation queries (significance.metric_intervals, N resamples), and the paired comparison of that
 checkpoint against the last epoch's weights on the same queries: the difference per metric, its interval and the two-sided
@@ -54,7 +62,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import attribution, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
+from reactranker_amd import attribution, latent_gaussian, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -128,6 +136,35 @@ def nearest_training_reactions(model, train_b, val_b, checkpoint, k, gpu, log):
     for c in range(n0):
         near = ", ".join(f"#{int(i)} (d {float(d):.4f}, target {float(t):+.3f})" for d, i, t in zip(dist[c], idx[c], tgt[c]))
         log.info("  query 0 candidate %2d (target %+.3f): %s", c, float(b["targets"][c]), near)
+
+
+def both_distances(model, train_b, val_b, checkpoint, k, gpu, log):
+    """The applicability calibration with the k-nearest-neighbour distance and the Mahalanobis distance side by side."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], b["targets"], b["add"])          # noqa: E731
+    bank = neighbors.ReactionBank.from_batches(model, [as_tuple(b) for b in train_b], gpu)
+    gauss = latent_gaussian.EmbeddingGaussian.from_bank(bank)
+    log.info("embedding Gaussian of %d training reactions: %d of %d directions kept", gauss.n_, gauss.rank_, bank.vectors.shape[1])
+    for method, kw in (("knn", dict(k=k)), ("mahalanobis", dict(gaussian=gauss))):
+        res = neighbors.evaluate_applicability(model, bank, val_b, checkpoint, gpu, target_name=None, method=method, **kw)
+        cal = res["calibration"]
+        log.info("applicability, %-11s: Spearman(error, distance) %.3f; mean distance %.4f; mae after removing the most distant "
+                 "rows: %s", method, cal["spearman"], float(res["distance"].mean()),
+                 ", ".join(f"{f:.1f}: {m:.4f}" for f, m in zip(cal["fractions"][::3], cal["mae"][::3])))
+
+
+def embedding_map(model, train_b, val_b, checkpoint, n, gpu, log):
+    """PCA of the training embeddings: the explained variance of the first n components, the validation set's scores on them."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], b["targets"], b["add"])          # noqa: E731
+    gauss = latent_gaussian.EmbeddingGaussian.fit(neighbors.reaction_vectors(model, [as_tuple(b) for b in train_b], gpu))
+    n = min(n, gauss.rank_)
+    evr = gauss.explained_variance_ratio_[:n]
+    log.info("embedding map: %d components explain %.1f %% of the variance (%s)", n, 100 * float(evr.sum()),
+             ", ".join(f"{100 * float(v):.1f}" for v in evr))
+    scores = gauss.project(neighbors.reaction_vectors(model, [as_tuple(b) for b in val_b], gpu), n)
+    path = checkpoint + ".embedding_map.pt"
+    torch.save(dict(scores=scores.cpu(), targets=torch.cat([torch.as_tensor(b["targets"]).reshape(-1) for b in val_b]),
+                    scope=[int(c) for b in val_b for c in b["scope"]], explained_variance_ratio=evr), path)
+    log.info("  scores of %d validation reactions written to %s", scores.shape[0], path)
 
 
 def reactions_to_compute_next(model, train_b, val_b, n, gpu, log):
@@ -209,6 +246,10 @@ def main():
                     "and bonds moved the score of the first validation query's predicted top candidate")
     ap.add_argument("--neighbors", type=int, default=0, metavar="K", help="listwise task types: after training, the applicability "
                     "calibration of the distance to the K nearest training reactions, and the first validation query's neighbours")
+    ap.add_argument("--mahalanobis", action="store_true", help="listwise task types: after training, the applicability calibration "
+                    "with the k-nearest-neighbour distance (k = --neighbors or 8) and the Mahalanobis distance side by side")
+    ap.add_argument("--embedding-map", type=int, default=0, metavar="N", help="listwise task types: after training, the explained "
+                    "variance of the first N principal components of the training embeddings; the validation scores are written out")
     ap.add_argument("--acquire", type=int, default=0, metavar="N", help="listwise task types: after training, which N validation "
                     "reactions to compute next (greedy k-center from the training embeddings) and the coverage radius before and after")
     ap.add_argument("--bootstrap", type=int, default=0, metavar="N", help="listwise task types: after training, the validation metrics "
@@ -299,6 +340,10 @@ def main():
         explain_top_candidate(model, val_b[0], args.attribute, args.ig_steps, args.gpu, log)
     if world == 1 and args.neighbors:
         nearest_training_reactions(model, train_b, val_b, args.checkpoint, args.neighbors, args.gpu, log)
+    if world == 1 and args.mahalanobis:
+        both_distances(model, train_b, val_b, args.checkpoint, args.neighbors or 8, args.gpu, log)
+    if world == 1 and args.embedding_map:
+        embedding_map(model, train_b, val_b, args.checkpoint, args.embedding_map, args.gpu, log)
     if world == 1 and args.acquire:
         reactions_to_compute_next(model, train_b, val_b, args.acquire, args.gpu, log)
     if world == 1 and args.bootstrap:

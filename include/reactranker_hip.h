@@ -1125,6 +1125,76 @@ int rr_resample_blocks(void);
 int rr_resample_set_blocks(int blocks);
 uint32_t rr_resample_draw_host(uint64_t seed, uint64_t j);
 
+/* A Gaussian model of the embedding space: second moments of the rows of a matrix, and the centred projection with a fused row
+ * norm that Mahalanobis distances, whitening and PCA scores are (additive: six new symbols, the ABI revision stays 8).  This
+ * library's own definition.
+ *
+ * rr_col_moments_f64.  x [N,H] (ld >= H) is f32 device memory.  Row n is USED when every one of its H values is finite; a row
+ * that holds a NaN or an infinity takes part in nothing below and is not counted.
+ *   n_used     = the number of used rows (one int64 on the device)
+ *   mean [H]   = column sums of the used rows / n_used, f64;  all +0.0 when n_used == 0
+ *   scatter [H,H] = sum over the used rows of c_n c_n^T, c_n[h] = (double)x[n,h] - mean[h] (one rounding), f64, row-major, dense.
+ * The caller divides by n_used - ddof.  Every element of the three outputs is written; N == 0 or no used row gives n_used = 0,
+ * mean and scatter all +0.0.  scatter is EXACTLY symmetric: only j <= i is computed, scatter[j][i] is a copy.
+ * Chunks: the rows are cut into C contiguous chunks of L = ceil(N / C) rows (chunk c = rows c L .. min(N, (c+1) L) - 1) with
+ *   C = max(1, min(64, ceil(N / 1024), floor(2^28 / (8 Hp^2)))),  Hp = H rounded up to a multiple of 64
+ * (a slab of Hp^2 doubles per chunk, 256 MiB of slabs at most) - a function of N and H only (rr_moments_chunks).
+ * The mean's chain, all f64, every addition rounded on its own: inside chunk c, row lane q = 0..15 owns the rows c L + q,
+ * c L + q + 16, ... and walks them ascending, acc = +0.0, acc = acc + (double)x[n,h] for a used row (+ 0.0 for another); the 16
+ * sums are added in ascending q starting from lane 0's; the chunks' sums are added to +0.0 in ascending c; one division by n_used.
+ * The scatter's chain, all f64: inside chunk c the rows are taken four at a time in ascending order (c L .. c L + 3, ...; a row
+ * that is not used, or past the chunk's end, enters as exact zeros, which change no bit of a sum), one
+ * v_mfma_f64_16x16x4_f64 per group of four rows and 16 x 16 tile, accumulating from +0.0: the matrix core adds the four products
+ * c_n[i] c_n[j], n ascending, to the running sum.  The instruction's internal rounding (the ISA documents a fused multiply-add
+ * per product, i.e. one rounding per term) was not held against a software chain on the card; tests/test_gpu_moments.py bounds
+ * the result for either reading.  The chunks' tiles are added to +0.0 in ascending c.
+ * So the bits depend on x's values, N and H only: not on ld, the pointer's alignment, the grid or the blocks setting.  No
+ * atomics, nothing depends on an order of arrival: run-to-run identical.  Five launches on `stream` (four when N == 0), no host
+ * synchronisation.  16-byte loads where x and ld allow, 4-byte loads otherwise - same values; the bytes between H and ld never
+ * reach a result.
+ * Limits: H <= RR_MOMENTS_MAX_H and N <= 2^31 - 1 (RR_ERR_UNSUPPORTED above).
+ *   rr_moments_workspace_bytes   bytes of caller-owned scratch: one byte per row, the chunks' column sums and row counts and the
+ *                                chunks' slabs; it does not depend on the blocks setting; nothing is retained after the call's work
+ *   rr_moments_chunks            C of the formula above (0 for arguments the call would refuse)
+ *   rr_moments_blocks / rr_moments_set_blocks   workgroups of the grid-strided launches (the row flags, the mean, the finish, and
+ *                                rr_center_project_f32's row tiles): 0 = automatic (four per CU at most), 1 .. 4096 fixed.  The
+ *                                result is the same bits for every value; a process-wide word, NOT thread-safe, for the bench
+ *                                tool and the tests.
+ * Status, all before any launch: RR_ERR_ARG for a null x / mean / scatter / n_used / workspace / bytes, a negative N, H < 1,
+ * ld < H or blocks outside [0, 4096]; RR_ERR_UNSUPPORTED as above; RR_ERR_WORKSPACE for a workspace below
+ * rr_moments_workspace_bytes.
+ *
+ * rr_center_project_f32.  y[n,r] = sum_h (x[n,h] - center[h]) * W[h,r] and sq[n] = sum_r y[n,r]^2, all f32.  x [N,H] (ld >= H),
+ * center [H] or NULL (= zeros), W [H,R] row-major and dense, 1 <= R <= H; y [N,R] dense or NULL, sq [N] or NULL, at least one
+ * given.  With y == NULL the [N,R] product is never written: four bytes per row leave the kernel.
+ * Arithmetic: t = x[n,h] - center[h] rounded in f32; the dot on v_mfma_f32_16x16x4_f32 by rr_knn_f32's chain over h (tiles of 16
+ * ascending, inside a tile h = 16 t + 4 c + j with j = 0..3 outer, one instruction each, and c = 0..3 inside the instruction;
+ * the columns from H to the next multiple of 16 enter as zeros).  sq: four chains q = 0..3, chain q owns the columns r with
+ * (r mod 16) div 4 == q and walks them ascending, acc = 0.0f, acc = acc + y * y (the square rounded, then added);
+ * sq = (chain 0 + chain 2) + (chain 1 + chain 3).  sq is computed from the very y that is written.  So the bits of row n depend
+ * on row n of x, center, W, H and R only: not on N, the row's position, ld, the pointer's alignment, the grid or the blocks
+ * setting.  A non-finite value in a row propagates by plain IEEE arithmetic: a NaN gives NaN in y and sq; an infinity gives NaN
+ * wherever it meets a zero or an infinity of the other sign (a dense W: sq is NaN), else an infinity.  Nothing is special-cased.
+ * One launch on `stream` (none when N == 0), no workspace, no atomics.
+ * Status, all before any launch: RR_ERR_ARG for a null x or W, y and sq both null, a negative N, H < 1, ld < H or R outside
+ * [1, H]; RR_ERR_UNSUPPORTED for N > 2^31 - 1. */
+#define RR_MOMENTS_MAX_H 1024
+int rr_moments_workspace_bytes(int64_t N, int H, size_t* bytes);
+int rr_moments_chunks(int64_t N, int H);
+int rr_col_moments_f64(const float* x, int64_t ld, int64_t N, int H,
+                       double* mean,        /* [H]    */
+                       double* scatter,     /* [H, H] */
+                       int64_t* n_used,     /* one value, device */
+                       void* workspace, size_t workspace_bytes, rr_stream_t stream);
+int rr_moments_blocks(void);
+int rr_moments_set_blocks(int blocks);
+int rr_center_project_f32(const float* x, int64_t ld, int64_t N, int H,
+                          const float* center,   /* [H] or NULL */
+                          const float* W, int R, /* [H, R] */
+                          float* y,              /* [N, R] or NULL */
+                          float* sq,             /* [N] or NULL */
+                          rr_stream_t stream);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

@@ -318,6 +318,12 @@ _SIGS = {
     "rr_resample_blocks": (i32, []),
     "rr_resample_set_blocks": (i32, [i32]),
     "rr_resample_draw_host": (C.c_uint32, [u64, u64]),
+    "rr_moments_workspace_bytes": (i32, [i64, i32, C.POINTER(C.c_size_t)]),
+    "rr_moments_chunks": (i32, [i64, i32]),
+    "rr_col_moments_f64": (i32, [c_f32p, i64, i64, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, c_stream]),
+    "rr_moments_blocks": (i32, []),
+    "rr_moments_set_blocks": (i32, [i32]),
+    "rr_center_project_f32": (i32, [c_f32p, i64, i64, i32, c_f32p, c_f32p, i32, c_f32p, c_f32p, c_stream]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
@@ -362,6 +368,7 @@ RR_KCENTER_MAX_PICKS = 65536
 RR_RESAMPLE_MAX_COLS = 32
 RR_RESAMPLE_MAX_ROWS = 1 << 20
 RR_RESAMPLE_BOOTSTRAP, RR_RESAMPLE_SIGNFLIP = 0, 1
+RR_MOMENTS_MAX_H = 1024
 ABI_VERSION = 8
 (RR_SAVED_R_MSG, RR_SAVED_R_H, RR_SAVED_P_MSG, RR_SAVED_P_H, RR_SAVED_D_MSG, RR_SAVED_D_HID, RR_SAVED_VECS, RR_SAVED_FFN_H,
  RR_SAVED_R_MSG0_U, RR_SAVED_R_Z1_U) = range(10)

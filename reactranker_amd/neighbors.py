@@ -8,7 +8,8 @@ the [M, N] distance matrix is never written.  On top of it:
   knn                     (dist [M, k] float32, idx [M, k] int64) of query rows against bank rows, with optional group exclusion
   ReactionBank            vectors + squared norms + targets + query index per row of a set of reactions; save / load / query
   latent_distance         mean distance to the k nearest bank rows: a one-forward uncertainty for every task type
-  evaluate_applicability  that distance against the model's error on a test set (uncertainty.uncertainty_calibration)
+  evaluate_applicability  that distance - or the Mahalanobis distance to the bank's Gaussian (latent_gaussian, DESIGN.md section
+                          4j) - against the model's error on a test set (uncertainty.uncertainty_calibration)
   split_overlap           test rows that have a (near-)duplicate in the bank
   kcenter_greedy          greedy k-center selection (rr_kcenter_f32): n rows of a pool, each the farthest
                           (optionally times a weight) from a labelled set and from the rows taken before it
@@ -35,6 +36,7 @@ MAX_K = _lib.RR_KNN_MAX_K
 MAX_PICKS = _lib.RR_KCENTER_MAX_PICKS
 KCENTER_ROWS_PER_WORKGROUP = 4                             # one wavefront per row, 256 threads (csrc/kcenter.hip)
 METRICS = ("sqeuclidean", "cosine")
+APPLICABILITY_METHODS = ("knn", "mahalanobis")
 
 
 def geometry() -> Tuple[int, int, int]:
@@ -253,16 +255,23 @@ def latent_distance(bank: ReactionBank, vectors: torch.Tensor, k: int, group=Non
 
 
 def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dict], path_checkpoints, gpu: int, k: int = 8,
-                           target_name: str = "ea", fractions=U.DEFAULT_FRACTIONS) -> dict:
+                           target_name: str = "ea", fractions=U.DEFAULT_FRACTIONS, method: str = "knn", gaussian=None) -> dict:
     """Applicability domain of a trained model: the latent distance of every test candidate to `bank` against its error.
     `test_batches` are the dicts main.test takes (r, p, scope, targets, add); the checkpoint is loaded and the targets are
     standardised as evaluate_uncertainty does.  One eval-mode forward per batch gives both the scores (column 0) and the
     reaction vectors.  Returns dict(distance [n], pred [n], targets [n] (standardised), scope, calibration =
     uncertainty_calibration(pred, targets, distance, fractions) - Spearman rho of error and distance plus the
     error-confidence curve -, qstats [Q, 12] = eval.ranking_stats per query, query_distance [Q] = mean distance per query).
-    A bank without rows gives +inf distances, which the calibration sorts like any other value."""
+    A bank without rows gives +inf distances, which the calibration sorts like any other value.
+    method 'mahalanobis'  puts sqrt(d^2), d^2 the squared Mahalanobis distance to the bank's Gaussian,
+    where the latent distance goes; `gaussian` is a fitted latent_gaussian.EmbeddingGaussian (None: fitted from the bank's
+    vectors with its defaults) and k is not used.  Everything else is the same."""
     if not isinstance(path_checkpoints, (str, bytes)) and hasattr(path_checkpoints, "__len__"):
         raise ValueError("evaluate_applicability takes one checkpoint path")
+    if method not in APPLICABILITY_METHODS:
+        raise ValueError(f"evaluate_applicability: method must be one of {APPLICABILITY_METHODS} (got {method!r})")
+    if gaussian is not None and method != "mahalanobis":
+        raise ValueError("evaluate_applicability: `gaussian` belongs to method 'mahalanobis'")
     U._check_fractions(fractions)
     f = U._standardizer(U._scaler_of(path_checkpoints), target_name)
     batches = []
@@ -278,6 +287,9 @@ def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dic
     H = int(model.encoder.hidden_size)
     if bank.vectors.shape[1] != H:
         raise ValueError(f"the bank holds vectors of width {bank.vectors.shape[1]}, the model's are {H}")
+    if method == "mahalanobis" and gaussian is None:
+        from .latent_gaussian import EmbeddingGaussian
+        gaussian = EmbeddingGaussian.from_bank(bank)
     preds, dists, stats = [], [], []
     try:
         model.eval()
@@ -288,7 +300,7 @@ def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dic
                 vec = vec[:, :H]
                 pred = U._first_column(out)
                 preds.append(pred)
-                dists.append(latent_distance(bank, vec, k))
+                dists.append(latent_distance(bank, vec, k) if method == "knn" else gaussian.mahalanobis(vec).sqrt())
                 stats.append(E.ranking_stats(pred, scope, targets, gpu, 0.25)[0])
     finally:
         StepPlan.keep_last, StepPlan.last = old_keep, old_last
