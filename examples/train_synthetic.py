@@ -46,6 +46,11 @@ training embeddings (latent_gaussian.EmbeddingGaussian, neighbors.evaluate_appli
 training embeddings and writes the validation reactions' scores on them next to the checkpoint (<checkpoint>.embedding_map.pt:
 scores [M, N], targets, scope, explained_variance_ratio).
 
+--cluster-split RADIUS (listwise task types, one process) clusters the mean embedding of every query, training and validation
+together, by sphere exclusion (clusters.sphere_exclusion; RADIUS 0: clusters.suggest_radius picks one), prints the cluster count
+and sizes, sends whole clusters to train / validation / test folds (clusters.cluster_split) and prints, per held-out fold, the
+quantiles of the distance to the nearest training query (clusters.split_report) next to a random split of the same fold sizes.
+
 --bootstrap N (listwise task types, one process) prints the validation metrics of the restored best checkpoint with their 95 %
 bootstrap intervals over the validation queries (significance.metric_intervals, N resamples), and the paired comparison of that
 checkpoint against the last epoch's weights on the same queries: the difference per metric, its interval and the two-sided
@@ -62,7 +67,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import attribution, latent_gaussian, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
+from reactranker_amd import attribution, clusters, latent_gaussian, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -182,6 +187,30 @@ def reactions_to_compute_next(model, train_b, val_b, n, gpu, log):
                      t, row, bt, q, c, gain, int((res["assign"] == t).sum()))
 
 
+def cluster_held_out_split(model, train_b, val_b, radius, gpu, log):
+    """A cluster-held-out split of all queries next to a random split of the same fold sizes (clusters.sphere_exclusion on the
+    mean reaction vector per query, clusters.cluster_split, clusters.split_report)."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], b["targets"], b["add"])          # noqa: E731
+    bank = neighbors.ReactionBank.from_batches(model, [as_tuple(b) for b in list(train_b) + list(val_b)], gpu)
+    qv = clusters.query_vectors(bank.vectors, bank.group)
+    if radius <= 0:
+        radius = clusters.suggest_radius(qv, k=min(8, max(1, qv.shape[0] - 1)), quantile=0.5)
+    res = clusters.sphere_exclusion(qv, radius)
+    sizes = res["sizes"].cpu().tolist()
+    log.info("cluster split: %d queries, radius %.4f -> %d clusters; sizes %s%s; %d singletons", qv.shape[0], radius, len(sizes),
+             sizes[:12], " ..." if len(sizes) > 12 else "", sum(1 for s in sizes if s == 1))
+    folds = clusters.cluster_split(res["labels"], (0.8, 0.1, 0.1), seed=0)
+    counts = torch.bincount(folds, minlength=3).cpu().tolist()
+    log.info("  folds by cluster (train / validation / test): %s queries", counts)
+    g = torch.Generator().manual_seed(0)
+    random_folds = torch.repeat_interleave(torch.arange(3), torch.tensor(counts))[torch.randperm(sum(counts), generator=g)].to(folds.device)
+    for name, f in (("cluster", folds), ("random ", random_folds)):
+        rep = clusters.split_report(qv, f, k=1)
+        for fold, n, q in zip(rep["folds"], rep["n"], rep["quantiles"].tolist()):
+            log.info("  %s split, fold %d (%3d queries): distance to the nearest training query, quantiles %s = %s", name, fold, n,
+                     "/".join(f"{lv:g}" for lv in rep["levels"]), " ".join(f"{v:.4f}" for v in q))
+
+
 def intervals_and_comparison(model, val_b, last_table, n, gpu, log):
     """What the validation means are worth: their bootstrap intervals, and whether the best checkpoint really beats the last epoch."""
     val = [(b["r"], b["p"], b["scope"], b["targets"], b["add"]) for b in val_b]
@@ -252,6 +281,9 @@ def main():
                     "variance of the first N principal components of the training embeddings; the validation scores are written out")
     ap.add_argument("--acquire", type=int, default=0, metavar="N", help="listwise task types: after training, which N validation "
                     "reactions to compute next (greedy k-center from the training embeddings) and the coverage radius before and after")
+    ap.add_argument("--cluster-split", type=float, default=None, metavar="RADIUS", help="listwise task types: after training, sphere-"
+                    "exclusion clusters of all queries' mean embeddings (0: a radius from clusters.suggest_radius), the folds of a "
+                    "cluster-held-out split and their distance to the training fold next to a random split of the same sizes")
     ap.add_argument("--bootstrap", type=int, default=0, metavar="N", help="listwise task types: after training, the validation metrics "
                     "with 95 %% bootstrap intervals (N resamples of the queries) and the paired test of the best checkpoint against the last epoch")
     ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
@@ -346,6 +378,8 @@ def main():
         embedding_map(model, train_b, val_b, args.checkpoint, args.embedding_map, args.gpu, log)
     if world == 1 and args.acquire:
         reactions_to_compute_next(model, train_b, val_b, args.acquire, args.gpu, log)
+    if world == 1 and args.cluster_split is not None:
+        cluster_held_out_split(model, train_b, val_b, args.cluster_split, args.gpu, log)
     if world == 1 and args.bootstrap:
         intervals_and_comparison(model, val_b, last_table, args.bootstrap, args.gpu, log)
     if world > 1:

@@ -1080,6 +1080,74 @@ int rr_kcenter_f32(const float* x, int64_t ld, int64_t P, int H, int n_pick,
 int rr_kcenter_blocks(void);
 int rr_kcenter_set_blocks(int blocks);
 
+/* Neighbours within a radius (additive: two new symbols, the ABI revision stays 8).  This library's own definition.  For query
+ * rows q [M,H] (ld_q) and bank rows bank [N,H] (ld_b), f32 device memory:
+ *   count[m] = #{ n : (m,n) not excluded and d(m,n) <= r2 }                                    int32 [M], every element written
+ * d(m,n) is rr_knn_f32's distance, bit for bit - max(0, (qn[m] + bn[n]) - 2 * dot(m,n)) with the same chains on
+ * v_mfma_f32_16x16x4_f32 - and the exclusion is rr_knn_f32's: q_group[m] == b_group[n] >= 0 (both arrays or neither), or a NaN
+ * distance.  A row compared with itself is counted like any other pair (knn's form leaves a rounding residue there, so at a
+ * very small r2 a row may not count itself; give every row its own group id to leave it out for certain).  At r2 = +inf a
+ * distance that overflowed to +inf counts and a NaN (inf - inf, a row that holds an infinity) does not.  The tile walk is
+ * rr_knn_f32's (one copy of it in csrc/knn.hip); instead of a sorted list every lane compares the distances it holds against r2
+ * and keeps integers, summed over the workgroup at the end of the walk.  With more than one bank split the partial counts [M,S]
+ * go to the workspace and a second kernel sums them in split order.  No atomics; the same counts for every split count
+ * (rr_knn_set_splits governs this entry too), pitch, alignment and position of the rows.
+ *   rr_radius_count_workspace_bytes   the query norms, the bank norms and the partial counts UNDER THE CURRENT SPLIT SETTING
+ *   rr_radius_count_f32               bank_sqnorm [N] may be NULL, as in rr_knn_f32.  M == 0 returns RR_OK without a launch;
+ *                                     N == 0 writes zeros.
+ * Status, all before any launch: RR_ERR_ARG for a null q / bank / count / workspace / bytes, one group array without the other,
+ * a negative M or N, H < 1, a pitch below H, or an r2 that is a NaN or negative (+inf is allowed); RR_ERR_UNSUPPORTED for M or N
+ * above 2^31 - 1; RR_ERR_WORKSPACE for a workspace below rr_radius_count_workspace_bytes. */
+int rr_radius_count_workspace_bytes(int64_t M, int64_t N, size_t* bytes);
+int rr_radius_count_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, float r2,
+                        const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, int32_t* count,
+                        void* workspace, size_t workspace_bytes, rr_stream_t stream);
+
+/* Sphere-exclusion clustering (Taylor-Butina with a density key, the leader algorithm without one) over reaction embeddings
+ * (additive: four new symbols, the ABI revision stays 8).  This library's own definition.  For pool rows x [P,H] (ld), f32
+ * device memory, a squared radius r2 >= 0 (+inf allowed) and an optional int32 key per row:
+ * Distance: d(i,c) is rr_kcenter_f32's difference chain, bit for bit (one copy of it, csrc/row_chain.h) - NOT knn's distance:
+ * the difference form gives d(c,c) = 0, so a centre always joins its own cluster and every non-padding round assigns at least
+ * one row.
+ * State: labels[i] = -2 for a row that holds any non-finite value (never eligible, never a member), every other row starts at -1.
+ * Round t takes the row c with labels == -1 that is largest under the total order (key descending, then index ascending;
+ * key == NULL: every key equal, so index order): centres[t - first_round] = c, and every row i with labels[i] == -1 and
+ * d(i,c) <= r2 gets labels[i] = t.  With no row at -1 left centres[t - first_round] = -1 and nothing else changes.  The keys are
+ * read as given and never updated (Butina uses the initial neighbour counts).
+ * What holds afterwards: every member lies within r2 of its centre, and two centres lie farther than r2 apart (both in this
+ * chain's f32 arithmetic).  What does NOT: two members of different clusters may lie within r2 of each other.
+ * How it runs: launches of one kernel back to back on `stream`, nothing else - no host synchronisation, no copy to the host, no
+ * atomics, no workgroup that waits for or signals another.  first_round == 0: one initial launch writes the state (the one extra
+ * read of the pool: it finds the non-finite rows) and leaves every workgroup's best (key, index) pair in the workspace; then one
+ * launch per round reads the pairs of the launch before it (two arrays, used alternately), reduces them to the winner in every
+ * workgroup alike (workgroup 0 writes the centre), keeps the centre's columns in registers (H <= 1024; wider rows re-read them)
+ * and streams only the rows still at -1 - the label is read first, then the row: one wavefront per row, rows grid-strided,
+ * four rows per workgroup and grid pass (256 threads).  16-byte loads where x and ld allow, 4-byte loads otherwise - same
+ * values; the bytes between H and ld never reach a result.
+ * first_round > 0 CONTINUES: labels and the workspace must be what the previous call on the same x / ld / P / H / r2 / key left
+ * (rounds 0 .. first_round-1 done), so that a caller can run rounds in batches and look at the last centre in between.  The
+ * blocks setting may differ between such calls.
+ * Results are the same bits for every blocks setting, row pitch, pointer alignment and position of the rows in a larger pool.
+ * Limits: n_rounds <= RR_SPHERE_EXCLUSION_MAX_ROUNDS per call, P <= 2^31 - 1 and first_round + n_rounds <= 2^31 - 1
+ * (RR_ERR_UNSUPPORTED above); H >= 1 is any value.  P == 0 writes the padding of centres; n_rounds == 0 with first_round == 0
+ * still writes labels.
+ *   rr_sphere_exclusion_workspace_bytes   the pairs of two launches at the largest grid; independent of the blocks setting
+ *   rr_sphere_exclusion_blocks / rr_sphere_exclusion_set_blocks   workgroups per launch: 0 = automatic (rr_kcenter_f32's rule),
+ *                                1 .. 4096 fixed; a process-wide word, NOT thread-safe, for the bench tool and the tests.
+ * Status, all before any launch: RR_ERR_ARG for a null x / labels / centres / workspace / bytes, a negative P, first_round or
+ * n_rounds, H < 1, ld < H, an r2 that is a NaN or negative, or blocks outside [0, 4096]; RR_ERR_UNSUPPORTED as above;
+ * RR_ERR_WORKSPACE for a workspace below rr_sphere_exclusion_workspace_bytes. */
+#define RR_SPHERE_EXCLUSION_MAX_ROUNDS 65536
+int rr_sphere_exclusion_workspace_bytes(int64_t P, size_t* bytes);
+int rr_sphere_exclusion_f32(const float* x, int64_t ld, int64_t P, int H, float r2,
+                            const int32_t* key,        /* [P] or NULL (= equal keys: index order) */
+                            int first_round, int n_rounds,
+                            int32_t* labels,           /* [P] state and result */
+                            int32_t* centres,          /* [n_rounds]: rounds first_round .. first_round+n_rounds-1 */
+                            void* workspace, size_t workspace_bytes, rr_stream_t stream);
+int rr_sphere_exclusion_blocks(void);
+int rr_sphere_exclusion_set_blocks(int blocks);
+
 /* Resampled column means of a per-query table: bootstrap intervals and paired sign-flip tests (additive: four new symbols, the
  * ABI revision stays 8).  This library's own definition.  x [Q,M] (ld >= M) is f64 device memory, one row per query, one column
  * per statistic (the tables of rr_ranking_metrics_f32 / rr_rank_correlation_f32, or differences of two such tables).

@@ -314,6 +314,14 @@ _SIGS = {
                              C.c_size_t, c_stream]),
     "rr_kcenter_blocks": (i32, []),
     "rr_kcenter_set_blocks": (i32, [i32]),
+    "rr_radius_count_workspace_bytes": (i32, [i64, i64, C.POINTER(C.c_size_t)]),
+    "rr_radius_count_f32": (i32, [c_f32p, i64, i64, c_f32p, i64, i64, i32, f32, c_i32p, c_i32p, c_f32p, c_i32p, C.c_void_p,
+                                  C.c_size_t, c_stream]),
+    "rr_sphere_exclusion_workspace_bytes": (i32, [i64, C.POINTER(C.c_size_t)]),
+    "rr_sphere_exclusion_f32": (i32, [c_f32p, i64, i64, i32, f32, c_i32p, i32, i32, c_i32p, c_i32p, C.c_void_p, C.c_size_t,
+                                      c_stream]),
+    "rr_sphere_exclusion_blocks": (i32, []),
+    "rr_sphere_exclusion_set_blocks": (i32, [i32]),
     "rr_resample_means_f64": (i32, [C.c_void_p, i64, i64, i32, i32, u64, i64, i64, C.c_void_p, c_i32p, c_stream]),
     "rr_resample_blocks": (i32, []),
     "rr_resample_set_blocks": (i32, [i32]),
@@ -365,6 +373,7 @@ RR_AMAX_LANES, RR_AMAX_STRIDE = 16, 32
 RR_AMAX_FLOATS = RR_AMAX_LANES * RR_AMAX_STRIDE
 RR_KNN_MAX_K = 64
 RR_KCENTER_MAX_PICKS = 65536
+RR_SPHERE_EXCLUSION_MAX_ROUNDS = 65536
 RR_RESAMPLE_MAX_COLS = 32
 RR_RESAMPLE_MAX_ROWS = 1 << 20
 RR_RESAMPLE_BOOTSTRAP, RR_RESAMPLE_SIGNFLIP = 0, 1

@@ -3,7 +3,7 @@
 //
 //   d(i, c) = sum_h (x[i,h] - x[c,h])^2 in f32 by the fixed chain: columns in groups of four, lane l of the wave owns the groups
 //   g with g % 64 == l (ascending, columns inside a group ascending), acc = acc + t * t with t = x[i,h] - x[c,h], the 64 chains
-//   joined by the butterfly xor 32, 16, 8, 4, 2, 1.
+//   joined by the butterfly xor 32, 16, 8, 4, 2, 1.  The chain and the row loads live in row_chain.h (csrc/cluster.hip shares them).
 //
 // kc_pass_kernel<NG, VEC> is the only kernel of a selection; n_pick + 1 launches of it run back to back on the caller's stream:
 //   launch 0       writes min_dist / assign / the eligibility bytes (the one extra read of the pool: it finds the rows that hold
@@ -17,6 +17,7 @@
 // NG = groups a lane owns (1 .. 4: H <= 1024, the centre in 4 NG registers); NG == 0 is the loop for wider rows, which re-reads
 // the centre's columns (L1 / L2 hits).  VEC: 16-byte loads (pointer 16-byte aligned and ld % 4 == 0), else 4-byte loads.
 #include "rr_common.h"
+#include "row_chain.h"
 
 #include <atomic>
 
@@ -41,87 +42,6 @@ struct KcParams {
   int t;                                          // the round this launch scores; 0: the initial pass
   int last;                                       // launch n_pick: nothing is scored
 };
-
-typedef const __attribute__((address_space(1))) f32x4* kc_gptr4;
-
-// columns c .. c + 3 of a row (c % 4 == 0, c < H); elements at or past H hold anything and are masked where they are used
-template <bool VEC>
-__device__ __forceinline__ f32x4 kc_load4(const float* row, int c, int H) {
-  f32x4 v;
-  if (VEC) {
-    v = *(kc_gptr4)(row + c);                     // (VEC: ld % 4 == 0, so the group lies inside the row's pitch)
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[c + e < H ? c + e : c];
-  }
-  return v;
-}
-
-template <int NG, bool VEC>
-__device__ __forceinline__ void kc_load_row(const float* row, int lane, int H, f32x4 (&v)[NG]) {
-#pragma unroll
-  for (int j = 0; j < NG; ++j) {
-    const int c = 4 * (lane + 64 * j);
-    v[j] = c < H ? kc_load4<VEC>(row, c, H) : f32x4(0.f);
-  }
-}
-
-__device__ __forceinline__ float kc_step(float acc, float a, float b, bool on) {
-  float t = a - b;
-  t = on ? t : 0.f;                               // (acc >= 0, so acc + 0 is acc: a masked column is a skipped one)
-  return acc + t * t;
-}
-
-template <int NG>
-__device__ __forceinline__ float kc_dist(const f32x4 (&a)[NG], const f32x4 (&b)[NG], int lane, int H) {
-  float acc = 0.f;
-#pragma unroll
-  for (int j = 0; j < NG; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = kc_step(acc, a[j][e], b[j][e], 4 * (lane + 64 * j) + e < H);
-  return rr_wave_sum(acc);
-}
-
-// any width: the same chain with both rows read group by group
-template <bool VEC>
-__device__ __forceinline__ float kc_dist_any(const float* row, const float* centre, int lane, int H) {
-  float acc = 0.f;
-  for (int g0 = 0; 4 * g0 < H; g0 += 64) {        // (uniform)
-    const int c = 4 * (g0 + lane);
-    if (c < H) {
-      const f32x4 a = kc_load4<VEC>(row, c, H), b = kc_load4<VEC>(centre, c, H);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc = kc_step(acc, a[e], b[e], c + e < H);
-    }
-  }
-  return rr_wave_sum(acc);
-}
-
-__device__ __forceinline__ bool kc_finite(float v) { return fabsf(v) < __builtin_inff(); }
-
-template <int NG>
-__device__ __forceinline__ bool kc_row_finite(const f32x4 (&a)[NG], int lane, int H) {
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < NG; ++j)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ok = ok && (4 * (lane + 64 * j) + e >= H || kc_finite(a[j][e]));
-  return __all(ok);
-}
-
-template <bool VEC>
-__device__ __forceinline__ bool kc_row_finite_any(const float* row, int lane, int H) {
-  bool ok = true;
-  for (int g0 = 0; 4 * g0 < H; g0 += 64) {
-    const int c = 4 * (g0 + lane);
-    if (c < H) {
-      const f32x4 a = kc_load4<VEC>(row, c, H);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) ok = ok && (c + e >= H || kc_finite(a[e]));
-    }
-  }
-  return __all(ok);
-}
 
 template <int NG, bool VEC>
 __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {

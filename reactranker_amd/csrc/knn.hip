@@ -21,6 +21,10 @@
 // row) merges them under the same order; with one split the lists are the result.  The order is total (n is unique), so the
 // result does not depend on the order of insertion: no atomics, run-to-run identical, the same bits for every split count.
 //
+// kn_walk is the one copy of that walk (staging, chunking, the k-tile skip, the split of the bank); knn_tile_kernel gives it the
+// list epilogue above, knn_count_kernel (rr_radius_count_f32, DESIGN section 4k: neighbours within a radius) a counting one
+// that needs neither the LDS distance tile nor a list.  Both form the distance through kn_dist.
+//
 // row_sqnorm_kernel: one wave per row; lane l sums x[h]^2 over h = l, l + 64, ... ascending (product rounded, then added), the
 // 64 partial sums are joined by the butterfly xor 32, 16, 8, 4, 2, 1.  4-byte loads only (a wave reads 256 contiguous bytes).
 #include "rr_common.h"
@@ -44,14 +48,25 @@ constexpr int KN_PAD = 0x7fffffff;                // index of an empty slot insi
 
 std::atomic<int> g_splits{0};
 
-struct KnnParams {
+// what the tile walk reads, and what both epilogues need next to it
+struct KnWalk {
   const float* q; int64_t ld_q; int64_t M;
   const float* b; int64_t ld_b; int64_t N;
-  int H, k, S;
+  int H, S;
   const int32_t* qg; const int32_t* bg;
   const float* qn; const float* bn;
+};
+
+struct KnnParams : KnWalk {
+  int k;
   float* out_d; int32_t* out_i;                   // S == 1: the result
   float* part_d; int32_t* part_i;                 // S > 1: [M, S, k]
+};
+
+struct KnCountParams : KnWalk {
+  float r2;
+  int32_t* out;                                   // S == 1: the result
+  int32_t* part;                                  // S > 1: [M, S]
 };
 
 typedef const __attribute__((address_space(1))) f32x4* kn_gptr4;
@@ -106,41 +121,23 @@ __device__ __forceinline__ void kn_offer(float& ld, int& li, float d, int n, boo
   }
 }
 
-template <bool QV, bool BV>
-__global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
-  __shared__ __attribute__((aligned(16))) float smem[KN_LDS];
+// The tile walk, the one copy of it: the workgroup's 64 query rows against its contiguous range of bank tiles, both operands
+// staged through `smem` (KN_STAGE floats) chunk by chunk.  tile_begin(n0) runs at a tile's first chunk (what the epilogue wants
+// loaded early), tile_end(acc, n0) after its last MFMA with the dot products of the tile that starts at bank row n0; the walk
+// passes a barrier before it touches `smem` again, so tile_end may use it between barriers of its own.
+template <bool QV, bool BV, class Begin, class End>
+__device__ __forceinline__ void kn_walk(const KnWalk& P, float* smem, Begin tile_begin, End tile_end) {
   float* const qs = smem;
   float* const bs = smem + KN_ROWS * KN_SP;
-  float* const dt = smem;                         // between a tile's last MFMA and the next tile's first chunk
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, qd = lane >> 4;
-  const int H = P.H, km1 = P.k - 1;
+  const int H = P.H;
   const int64_t m0 = static_cast<int64_t>(blockIdx.x) * KN_ROWS;
   const int64_t T = (P.N + KN_BANK - 1) / KN_BANK;
   const int64_t t0 = static_cast<int64_t>(blockIdx.y) * T / P.S, t1 = (static_cast<int64_t>(blockIdx.y) + 1) * T / P.S;
   const int nch = (H + KN_KC - 1) / KN_KC;
   const int64_t total = (t1 - t0) * nch;
-
-  // the lists of this wave's 16 query rows
-  float ld[16];
-  int li[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    ld[r] = __builtin_inff();
-    li[r] = KN_PAD;
-  }
-  float qnv[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    const int64_t m = m0 + 16 * b + l15;
-    qnv[b] = P.qn[m < P.M ? m : 0];
-  }
-  int qgv = -1;                                   // lane r < 16: the group of query row 16 wave + r
-  if (P.qg != nullptr) {
-    const int64_t m = m0 + 16 * wave + l15;
-    qgv = P.qg[m < P.M ? m : 0];
-  }
 
   // staging: thread -> (row, 4 columns) of the chunk; KN_QU pieces of q and KN_BU of the bank per thread
   const int srow = tid / (KN_KC / 4), sc4 = (tid % (KN_KC / 4)) * 4;
@@ -164,9 +161,6 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
   };
 
   f32x4 acc[2][4];
-  float bnv[2][4];                                // this lane's bank norms and the candidates' groups of the tile in flight,
-  int cn[2], cg[2];                               // loaded at the tile's first chunk, used after its last
-  bool cin[2];
   if (total > 0) fetch(0);
   int ch = 0;
   int64_t n0 = t0 * KN_BANK;
@@ -183,20 +177,7 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = f32x4(0.f);
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int64_t n = n0 + 32 * wave + 16 * a + 4 * qd + e;
-          bnv[a][e] = P.bn[n < P.N ? n : 0];
-        }
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int64_t n = n0 + lane + 64 * h;
-        cin[h] = n < P.N;
-        cn[h] = static_cast<int>(cin[h] ? n : 0);
-        cg[h] = (P.bg != nullptr) ? P.bg[cn[h]] : -1;
-      }
+      tile_begin(n0);
     }
     const int nt = (H - ch * KN_KC + 15) / 16;    // k-tiles of this chunk that hold anything (uniform)
 #pragma unroll
@@ -216,7 +197,72 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
     }
     if (++ch < nch) continue;
     ch = 0;
+    tile_end(acc, n0);
+    n0 += KN_BANK;
+  }
+}
 
+// this lane's bank norms of the tile that starts at n0: bank rows 32 w + 16 a + 4 (lane >> 4) + e
+__device__ __forceinline__ void kn_tile_norms(const KnWalk& P, int64_t n0, int wave, int qd, float (&bnv)[2][4]) {
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int64_t n = n0 + 32 * wave + 16 * a + 4 * qd + e;
+      bnv[a][e] = P.bn[n < P.N ? n : 0];
+    }
+}
+
+// THE distance of the search and of the count, from a finished dot product (a NaN stays a NaN: it is excluded by the caller)
+__device__ __forceinline__ float kn_dist(float qn, float bn, float dot) {
+  const float v = (qn + bn) - 2.0f * dot;
+  return v < 0.f ? 0.f : v;
+}
+
+template <bool QV, bool BV>
+__global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
+  __shared__ __attribute__((aligned(16))) float smem[KN_LDS];
+  float* const dt = smem;                         // between a tile's last MFMA and the next tile's first chunk
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, qd = lane >> 4;
+  const int km1 = P.k - 1;
+  const int64_t m0 = static_cast<int64_t>(blockIdx.x) * KN_ROWS;
+
+  // the lists of this wave's 16 query rows
+  float ld[16];
+  int li[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    ld[r] = __builtin_inff();
+    li[r] = KN_PAD;
+  }
+  float qnv[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int64_t m = m0 + 16 * b + l15;
+    qnv[b] = P.qn[m < P.M ? m : 0];
+  }
+  int qgv = -1;                                   // lane r < 16: the group of query row 16 wave + r
+  if (P.qg != nullptr) {
+    const int64_t m = m0 + 16 * wave + l15;
+    qgv = P.qg[m < P.M ? m : 0];
+  }
+  float bnv[2][4];                                // this lane's bank norms and the candidates' groups of the tile in flight,
+  int cn[2], cg[2];                               // loaded at the tile's first chunk, used after its last
+  bool cin[2];
+
+  auto tile_begin = [&](int64_t n0) {
+    kn_tile_norms(P, n0, wave, qd, bnv);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int64_t n = n0 + lane + 64 * h;
+      cin[h] = n < P.N;
+      cn[h] = static_cast<int>(cin[h] ? n : 0);
+      cg[h] = (P.bg != nullptr) ? P.bg[cn[h]] : -1;
+    }
+  };
+  auto tile_end = [&](const f32x4 (&acc)[2][4], int64_t) {
     // ---- the tile is complete: distances -> LDS (over the staging buffers, once every wave has read its last operands)
     __syncthreads();
 #pragma unroll
@@ -226,10 +272,7 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
       for (int b = 0; b < 4; ++b) {
         f32x4 d;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float v = (qnv[b] + bnv[a][e]) - 2.0f * acc[a][b][e];
-          d[e] = v < 0.f ? 0.f : v;               // (a NaN stays a NaN: it is excluded below)
-        }
+        for (int e = 0; e < 4; ++e) d[e] = kn_dist(qnv[b], bnv[a][e], acc[a][b][e]);
         *reinterpret_cast<f32x4*>(dt + (16 * b + l15) * KN_DP + col) = d;
       }
     }
@@ -246,8 +289,8 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
         kn_offer(ld[r], li[r], d, cn[h], valid, km1, lane);
       }
     }
-    n0 += KN_BANK;
-  }
+  };
+  kn_walk<QV, BV>(P, smem, tile_begin, tile_end);
 
   // ---- the lists: the result (one split) or this split's partial lists
 #pragma unroll
@@ -264,6 +307,84 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_tile_kernel(const KnnParams P) {
       }
     }
   }
+}
+
+// Neighbours within a radius: the same walk with a cheaper epilogue - no LDS distance tile, no list.  A lane compares the 32
+// distances it holds after a tile (bank rows 32 w + 16 a + 4 (lane >> 4) + e of query row 16 b + (lane & 15)) against r2 and keeps
+// one integer per b; after the walk the four lane >> 4 groups are summed by two shuffles and the four waves through LDS, in wave
+// order.  One split: the counts are the result; more: this split's column of the partial counts [M, S].
+template <bool QV, bool BV>
+__global__ void __launch_bounds__(KN_NT, 2) knn_count_kernel(const KnCountParams P) {
+  __shared__ __attribute__((aligned(16))) float smem[KN_STAGE];
+  __shared__ int s_cnt[KN_NT / 64][KN_ROWS];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, qd = lane >> 4;
+  const int64_t m0 = static_cast<int64_t>(blockIdx.x) * KN_ROWS;
+  const float r2 = P.r2;
+
+  float qnv[4];
+  int qgv[4], cnt[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int64_t m = m0 + 16 * b + l15;
+    qnv[b] = P.qn[m < P.M ? m : 0];
+    qgv[b] = (P.qg != nullptr) ? P.qg[m < P.M ? m : 0] : -1;
+    cnt[b] = 0;
+  }
+  float bnv[2][4];                                // this lane's bank norms, groups and row bounds of the tile in flight
+  int bgv[2][4];
+  bool bin[2][4];
+
+  auto tile_begin = [&](int64_t n0) {
+    kn_tile_norms(P, n0, wave, qd, bnv);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int64_t n = n0 + 32 * wave + 16 * a + 4 * qd + e;
+        bin[a][e] = n < P.N;
+        bgv[a][e] = (P.bg != nullptr) ? P.bg[bin[a][e] ? n : 0] : -1;
+      }
+  };
+  auto tile_end = [&](const f32x4 (&acc)[2][4], int64_t) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float d = kn_dist(qnv[b], bnv[a][e], acc[a][b][e]);
+          const bool in = bin[a][e] && d <= r2 && !(qgv[b] >= 0 && qgv[b] == bgv[a][e]);   // (d <= r2 is false for a NaN)
+          cnt[b] += in ? 1 : 0;
+        }
+  };
+  kn_walk<QV, BV>(P, smem, tile_begin, tile_end);
+
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    cnt[b] += __shfl_xor(cnt[b], 16, 64);
+    cnt[b] += __shfl_xor(cnt[b], 32, 64);
+    if (qd == 0) s_cnt[wave][16 * b + l15] = cnt[b];
+  }
+  __syncthreads();
+  const int64_t m = m0 + tid;
+  if (tid < KN_ROWS && m < P.M) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < KN_NT / 64; ++w) c += s_cnt[w][tid];
+    if (P.S == 1) P.out[m] = c;
+    else P.part[m * P.S + blockIdx.y] = c;
+  }
+}
+
+// one thread per row: the S partial counts of a row, in split order (S == 0: zeros)
+__global__ void __launch_bounds__(KN_NT) knn_count_merge_kernel(const int32_t* part, int64_t M, int S, int32_t* out) {
+  const int64_t m = static_cast<int64_t>(blockIdx.x) * KN_NT + threadIdx.x;
+  if (m >= M) return;
+  int c = 0;
+  for (int s = 0; s < S; ++s) c += part[m * S + s];
+  out[m] = c;
 }
 
 // one wave per row: the S partial lists of a row -> the row's result (S == 0: all padding)
@@ -339,6 +460,36 @@ int sqnorm_launch(const float* x, int64_t ld, int64_t rows, int H, float* out, h
   return rr_launch_status();
 }
 
+// the walk's operands, with the norms both entries need: the query norms go to `qn`, the bank norms to `bn` unless the caller has them
+int kn_prepare(KnWalk& W, const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, int S,
+               const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, float* qn, float* bn, hipStream_t s) {
+  W.q = q; W.ld_q = ld_q; W.M = M;
+  W.b = bank; W.ld_b = ld_b; W.N = N;
+  W.H = H; W.S = S;
+  W.qg = q_group; W.bg = b_group;
+  int st = sqnorm_launch(q, ld_q, M, H, qn, s);
+  if (st != RR_OK) return st;
+  W.qn = qn;
+  W.bn = bank_sqnorm;
+  if (!bank_sqnorm) {
+    st = sqnorm_launch(bank, ld_b, N, H, bn, s);
+    W.bn = bn;
+  }
+  return st;
+}
+
+// the workspace of a count: the norms as in KnLayout, then the partial counts [M, S]
+struct KnCountLayout { size_t qn, bn, part, total; };
+KnCountLayout kn_count_layout(int64_t M, int64_t N, int S) {
+  KnCountLayout L;
+  size_t o = 0;
+  L.qn = o; o += kn_round(static_cast<size_t>(M) * 4);
+  L.bn = o; o += kn_round(static_cast<size_t>(N) * 4);
+  L.part = o; o += S > 1 ? kn_round(static_cast<size_t>(M) * S * 4) : 0;
+  L.total = o > 256 ? o : 256;
+  return L;
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,22 +541,10 @@ int rr_knn_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64
     return rr_launch_status();
   }
   KnnParams P;
-  P.q = q; P.ld_q = ld_q; P.M = M;
-  P.b = bank; P.ld_b = ld_b; P.N = N;
-  P.H = H; P.k = k; P.S = S;
-  P.qg = q_group; P.bg = b_group;
-  float* qn = reinterpret_cast<float*>(ws + L.qn);
-  int st = sqnorm_launch(q, ld_q, M, H, qn, s);
+  P.k = k;
+  int st = kn_prepare(P, q, ld_q, M, bank, ld_b, N, H, S, q_group, b_group, bank_sqnorm, reinterpret_cast<float*>(ws + L.qn),
+                      reinterpret_cast<float*>(ws + L.bn), s);
   if (st != RR_OK) return st;
-  P.qn = qn;
-  if (bank_sqnorm) {
-    P.bn = bank_sqnorm;
-  } else {
-    float* bn = reinterpret_cast<float*>(ws + L.bn);
-    st = sqnorm_launch(bank, ld_b, N, H, bn, s);
-    if (st != RR_OK) return st;
-    P.bn = bn;
-  }
   P.out_d = dist; P.out_i = idx;
   P.part_d = reinterpret_cast<float*>(ws + L.part_d);
   P.part_i = reinterpret_cast<int32_t*>(ws + L.part_i);
@@ -418,6 +557,51 @@ int rr_knn_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64
   st = rr_launch_status();
   if (st != RR_OK || S == 1) return st;
   knn_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(P.part_d, P.part_i, M, S, k, dist, idx);
+  return rr_launch_status();
+}
+
+int rr_radius_count_workspace_bytes(int64_t M, int64_t N, size_t* bytes) {
+  RR_CHECK_ARG(bytes && M >= 0 && N >= 0);
+  if (M > 0x7fffffffLL || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  *bytes = kn_count_layout(M, N, kn_splits(M, N)).total;
+  return RR_OK;
+}
+
+int rr_radius_count_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, float r2,
+                        const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, int32_t* count,
+                        void* workspace, size_t workspace_bytes, rr_stream_t stream) {
+  RR_CHECK_ARG(q && bank && count && workspace);
+  RR_CHECK_ARG((q_group == nullptr) == (b_group == nullptr));
+  RR_CHECK_ARG(M >= 0 && N >= 0 && H >= 1 && ld_q >= H && ld_b >= H);
+  RR_CHECK_ARG(r2 >= 0.f);                        // (false for a NaN)
+  if (M > 0x7fffffffLL || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  const int S = kn_splits(M, N);
+  const KnCountLayout L = kn_count_layout(M, N, S);
+  if (workspace_bytes < L.total) return RR_ERR_WORKSPACE;
+  if (M == 0) return RR_OK;
+  const int64_t row_tiles = (M + KN_ROWS - 1) / KN_ROWS, merge_blocks = (M + KN_NT - 1) / KN_NT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* ws = static_cast<char*>(workspace);
+  if (N == 0) {                                   // nothing to count: the sum of zero partial counts
+    knn_count_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(nullptr, M, 0, count);
+    return rr_launch_status();
+  }
+  KnCountParams P;
+  P.r2 = r2;
+  int st = kn_prepare(P, q, ld_q, M, bank, ld_b, N, H, S, q_group, b_group, bank_sqnorm, reinterpret_cast<float*>(ws + L.qn),
+                      reinterpret_cast<float*>(ws + L.bn), s);
+  if (st != RR_OK) return st;
+  P.out = count;
+  P.part = reinterpret_cast<int32_t*>(ws + L.part);
+  const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(S));
+  const bool qv = kn_vec_ok(q, ld_q), bv = kn_vec_ok(bank, ld_b);
+  if (qv && bv) knn_count_kernel<true, true><<<grid, KN_NT, 0, s>>>(P);
+  else if (qv) knn_count_kernel<true, false><<<grid, KN_NT, 0, s>>>(P);
+  else if (bv) knn_count_kernel<false, true><<<grid, KN_NT, 0, s>>>(P);
+  else knn_count_kernel<false, false><<<grid, KN_NT, 0, s>>>(P);
+  st = rr_launch_status();
+  if (st != RR_OK || S == 1) return st;
+  knn_count_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(P.part, M, S, count);
   return rr_launch_status();
 }
 
