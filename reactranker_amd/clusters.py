@@ -22,9 +22,9 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _embed, _lib
 from ._lib import check, lib, ptr, stream
-from .neighbors import _group, _matrix, _rows, knn
+from .neighbors import knn
 
 MAX_ROUNDS = _lib.RR_SPHERE_EXCLUSION_MAX_ROUNDS
 ROWS_PER_WORKGROUP = 4                                     # one wavefront per row, 256 threads (csrc/cluster.hip)
@@ -54,14 +54,15 @@ def radius_count(queries: torch.Tensor, bank: torch.Tensor, radius, q_group=None
     Scratch comes from torch's allocator on the current stream, and the call is ordered on that stream.
     ValueError - before any launch - for CPU tensors, widths that differ or are 0, one group array without the other, or a
     radius that is negative or a NaN."""
-    _matrix(queries, "queries")
-    _matrix(bank, "bank")
+    who = "radius_count"
+    _embed.matrix(queries, "queries", who)
+    _embed.matrix(bank, "bank", who)
     r2 = radius_squared(radius)
     if queries.shape[1] != bank.shape[1] or queries.shape[1] < 1:
         raise ValueError(f"radius_count: queries have width {queries.shape[1]}, the bank {bank.shape[1]} (equal and >= 1 required)")
     if (q_group is None) != (b_group is None):
         raise ValueError("radius_count: q_group and b_group go together (both or neither)")
-    q, b = _rows(queries, "queries"), _rows(bank, "bank")
+    q, b = _embed.rows(queries, "queries", who), _embed.rows(bank, "bank", who)
     if q.device != b.device:
         raise ValueError(f"radius_count: queries on {q.device}, bank on {b.device}")
     M, N, H, dev = q.shape[0], b.shape[0], q.shape[1], q.device
@@ -69,26 +70,17 @@ def radius_count(queries: torch.Tensor, bank: torch.Tensor, radius, q_group=None
         raise ValueError(f"radius_count: {max(M, N)} rows (at most 2^31 - 1)")
     qg = bg = None
     if q_group is not None:
-        qg, bg = _group(q_group, M, dev, "q_group"), _group(b_group, N, dev, "b_group")
-    bn = None
-    if bank_sqnorm is not None:
-        bn = torch.as_tensor(bank_sqnorm)
-        if not bn.is_cuda or bn.dtype != torch.float32 or bn.numel() != N:
-            raise ValueError(f"radius_count: bank_sqnorm must be {N} float32 values on the GPU")
-        bn = bn.reshape(-1).contiguous()
+        qg, bg = _embed.group(q_group, M, dev, "q_group", who), _embed.group(b_group, N, dev, "b_group", who)
+    bn = None if bank_sqnorm is None else _embed.per_row(bank_sqnorm, N, None, "bank_sqnorm", who)
     count = torch.empty(M, dtype=torch.int32, device=dev)
     if M == 0:
         return count.to(torch.int64)
     if N == 0:                                             # (the C entry wants a bank pointer even when it holds no row)
-        b = torch.zeros(1, H, dtype=torch.float32, device=dev)
-        bg = None if bg is None else torch.full((1,), -1, dtype=torch.int32, device=dev)
+        b, bg = _embed.empty_bank(H, dev, bg is not None)
     with torch.cuda.device(dev):
-        nbytes = C.c_size_t()
-        check(lib().rr_radius_count_workspace_bytes(M, N, C.byref(nbytes)), "rr_radius_count_workspace_bytes")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        check(lib().rr_radius_count_f32(ptr(q), q.stride(0) if M > 1 else H, M, ptr(b), b.stride(0) if N > 1 else H, N, H,
-                                        C.c_float(r2), ptr(qg), ptr(bg), ptr(bn), ptr(count), ptr(ws),
-                                        C.c_size_t(nbytes.value), stream()), "rr_radius_count_f32")
+        ws, nbytes = _embed.scratch("rr_radius_count_workspace_bytes", dev, M, N)
+        check(lib().rr_radius_count_f32(ptr(q), _embed.pitch(q), M, ptr(b), _embed.pitch(b), N, H, C.c_float(r2),
+                                        ptr(qg), ptr(bg), ptr(bn), ptr(count), ptr(ws), nbytes, stream()), "rr_radius_count_f32")
     return count.to(torch.int64)
 
 
@@ -112,7 +104,7 @@ def sphere_exclusion(vectors: torch.Tensor, radius, order: str = "density", key=
     and every call is ordered on that stream.
     ValueError - before any launch - for CPU tensors, width 0, an unknown order, a radius that is negative or a NaN, a key that
     is not P integers, or max_clusters outside [0, 65536]."""
-    _matrix(vectors, "vectors")
+    _embed.matrix(vectors, "vectors", "sphere_exclusion")
     if order not in ORDERS:
         raise ValueError(f"sphere_exclusion: order must be one of {ORDERS} (got {order!r})")
     r2 = radius_squared(radius)
@@ -123,28 +115,26 @@ def sphere_exclusion(vectors: torch.Tensor, radius, order: str = "density", key=
             raise ValueError(f"sphere_exclusion: max_clusters must be an integer in [0, {MAX_ROUNDS}] (got {max_clusters!r})")
     if vectors.shape[1] < 1:
         raise ValueError("sphere_exclusion: rows of width 0")
-    x = _rows(vectors, "vectors")
+    x = _embed.rows(vectors, "vectors", "sphere_exclusion")
     P, H, dev = x.shape[0], x.shape[1], x.device
     if P > 2 ** 31 - 1:
         raise ValueError(f"sphere_exclusion: {P} rows (at most 2^31 - 1)")
     if key is not None:
-        k32 = _group(key, P, dev, "key")
+        k32 = _embed.group(key, P, dev, "key", "sphere_exclusion")
     elif order == "density" and P > 0:
         k32 = radius_count(x, x, radius).to(torch.int32)
     else:
         k32 = None
     labels = torch.empty(P, dtype=torch.int32, device=dev)
-    one = torch.empty(1, dtype=torch.int32, device=dev)            # (the C entry wants non-null pointers for empty arrays)
+    one = _embed.placeholder(dev, torch.int32)
     with torch.cuda.device(dev):
-        nbytes = C.c_size_t()
-        check(lib().rr_sphere_exclusion_workspace_bytes(P, C.byref(nbytes)), "rr_sphere_exclusion_workspace_bytes")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        ws, nbytes = _embed.scratch("rr_sphere_exclusion_workspace_bytes", dev, P)
 
         def rounds(first, count, out):
-            check(lib().rr_sphere_exclusion_f32(ptr(x) if P > 0 else ptr(one), x.stride(0) if P > 1 else H, P, H, C.c_float(r2),
-                                                ptr(k32), first, count, ptr(labels) if P > 0 else ptr(one),
-                                                ptr(out) if count > 0 else ptr(one), ptr(ws), C.c_size_t(nbytes.value),
-                                                stream()), "rr_sphere_exclusion_f32")
+            check(lib().rr_sphere_exclusion_f32(ptr(x) if P > 0 else ptr(one), _embed.pitch(x), P, H, C.c_float(r2), ptr(k32),
+                                                first, count, ptr(labels) if P > 0 else ptr(one),
+                                                ptr(out) if count > 0 else ptr(one), ptr(ws), nbytes, stream()),
+                  "rr_sphere_exclusion_f32")
         if n is not None:
             centres = torch.empty(n, dtype=torch.int32, device=dev)
             rounds(0, n, centres)
@@ -178,7 +168,7 @@ def suggest_radius(vectors: torch.Tensor, k: int = 8, quantile: float = 0.5) -> 
     non-finite values, are left out).  A Python float; ValueError when no row has k neighbours."""
     if not 0.0 <= float(quantile) <= 1.0:
         raise ValueError(f"suggest_radius: quantile must lie in [0, 1] (got {quantile!r})")
-    x = _rows(vectors, "vectors")
+    x = _embed.rows(vectors, "vectors", "suggest_radius")
     g = torch.arange(x.shape[0], dtype=torch.int32, device=x.device)
     dist, _ = knn(x, x, k, q_group=g, b_group=g)
     d = dist[:, int(k) - 1]
@@ -191,8 +181,8 @@ def suggest_radius(vectors: torch.Tensor, k: int = 8, quantile: float = 0.5) -> 
 def query_vectors(vectors: torch.Tensor, group) -> torch.Tensor:
     """The mean reaction vector of every query: [Q, H] float32 for `vectors` [N, H] and `group` [N], the running index of the
     query a row belongs to (ReactionBank.group's numbering: 0 .. Q - 1, every query with at least one row).  Sums in float64."""
-    x = _rows(vectors, "vectors")
-    g = _group(group, x.shape[0], x.device, "group").to(torch.int64)
+    x = _embed.rows(vectors, "vectors", "query_vectors")
+    g = _embed.group(group, x.shape[0], x.device, "group", "query_vectors").to(torch.int64)
     if x.shape[0] == 0:
         return torch.zeros(0, x.shape[1], dtype=torch.float32, device=x.device)
     lo, hi = int(g.min()), int(g.max())
@@ -258,8 +248,8 @@ def split_report(vectors: torch.Tensor, folds, k: int = 1) -> dict:
     rows to their k-th nearest row of fold 0.  One knn call with the folds as groups: the bank is every row, and every row
     outside fold 0 shares one group id with the queries, so only fold 0 can be found.  A held-out row without k such
     neighbours counts as +inf.  Rows with a negative fold are in neither side."""
-    x = _rows(vectors, "vectors")
-    f = _group(folds, x.shape[0], x.device, "folds").to(torch.int64)
+    x = _embed.rows(vectors, "vectors", "split_report")
+    f = _embed.group(folds, x.shape[0], x.device, "folds", "split_report").to(torch.int64)
     held = (f >= 1).nonzero().reshape(-1)
     ids = sorted(set(f[held].cpu().tolist()))
     out = torch.full((len(ids), len(REPORT_LEVELS)), float("nan"), dtype=torch.float64)

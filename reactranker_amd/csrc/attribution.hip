@@ -312,8 +312,6 @@ __global__ void __launch_bounds__(RR_WAVE) attribution_reduce_kernel(const Reduc
   if (lane == 0) P.mol_total[mol] = total;
 }
 
-inline bool at_vec_ok(const float* p, int64_t ld) { return p && rr_aligned16(p) && (ld % 4 == 0); }
-
 }  // namespace
 
 extern "C" {
@@ -355,8 +353,8 @@ int rr_input_attribution_f32(const float* dz, int64_t ld_dz, const float* w, int
   P.alpha = alpha; P.accumulate = accumulate;
   P.attr = attr; P.ld_attr = ld_attr;
   P.dx = dx; P.ld_dx = ld_dx;
-  P.dz_vec = at_vec_ok(dz, ld_dz) ? 1 : 0;
-  P.x_vec = at_vec_ok(P.x, ld_x) ? 1 : 0;
+  P.dz_vec = rr_vec4_ok(dz, ld_dz) ? 1 : 0;
+  P.x_vec = (P.x && rr_vec4_ok(P.x, ld_x)) ? 1 : 0;    // (no attributions: x is not read)
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int kt = (K + 15) / 16;
   if (kt <= 1) return launch_attr<1>(P, s);

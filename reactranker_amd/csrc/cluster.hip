@@ -19,22 +19,13 @@
 // workgroup, and there are no atomics.
 // One wave per row, rows grid-strided as in kcenter.hip.  A wave first reads the labels of its next 64 rows (one per lane),
 // then visits only those still at -1, two rows in flight: a row that is assigned already costs four bytes, not its columns.
-#include "rr_common.h"
 #include "row_chain.h"
-
-#include <atomic>
 
 namespace {
 
-constexpr int SE_NT = 256;                        // threads (4 waves: 4 rows per workgroup and grid pass)
-constexpr int SE_WAVES = SE_NT / 64;
-constexpr int SE_MAX_BLOCKS = 4096;
-constexpr int SE_MAX_NG = 4;                      // register path up to H = 256 * SE_MAX_NG
-constexpr int SE_AUTO_BLOCKS = RR_NUM_CU * 4;     // kcenter.hip's grid: the same stream
+BlocksKnob g_blocks;
 
-std::atomic<int> g_blocks{0};
-
-struct __attribute__((aligned(8))) SePair { int32_t k; int32_t i; };   // i < 0: no row at -1; slot 0 of an array: k = pairs that follow
+typedef RowPair<int32_t> SePair;                  // (key, index); slot 0 of an array: k = pairs that follow
 
 struct SeParams {
   const float* x; int64_t ld; int64_t P; int H;
@@ -46,14 +37,9 @@ struct SeParams {
   int t;                                          // the round this launch assigns; the initial launch assigns none
 };
 
-// does candidate (ok, oi) replace (k, i) as the first maximum?  i < 0 = none yet
-__device__ __forceinline__ bool se_replaces(int ok, int oi, int k, int i) {
-  return oi >= 0 && (i < 0 || ok > k || (ok == k && oi < i));
-}
-
 template <int NG, bool VEC>
-__global__ void __launch_bounds__(SE_NT) se_pass_kernel(const SeParams p) {
-  __shared__ SePair s_prev[SE_WAVES], s_out[SE_WAVES];
+__global__ void __launch_bounds__(RC_NT) se_pass_kernel(const SeParams p) {
+  __shared__ SePair s_prev[RC_WAVES], s_out[RC_WAVES];
   constexpr int NR = NG > 0 ? NG : 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -65,25 +51,18 @@ __global__ void __launch_bounds__(SE_NT) se_pass_kernel(const SeParams p) {
   f32x4 cv[NR];
   const float* crow = p.x;
   if (!init) {
+    // The scan stays here, as in kc_pass_kernel: inside one helper with the join it moves the registers of the NG == 0 kernels
+    // (profiles/embedding_shared_ab.txt).
     int bk = 0, bi = -1;
     // (a workspace that no launch of this entry wrote - a call with first_round > 0 on fresh memory - must not become an
     // address: the count is held to the array and an index past the pool counts as none)
-    const int n_prev = min(max(p.prev[0].k, 0), SE_MAX_BLOCKS);
-    for (int k = tid; k < n_prev; k += SE_NT) {
+    const int n_prev = min(max(p.prev[0].k, 0), RC_MAX_BLOCKS);
+    for (int k = tid; k < n_prev; k += RC_NT) {
       const SePair q = p.prev[1 + k];
-      if (q.i < p.P && se_replaces(q.k, q.i, bk, bi)) { bk = q.k; bi = q.i; }
+      if (q.i < p.P && rr_first_max_replaces(q.k, q.i, bk, bi)) { bk = q.k; bi = q.i; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const int ok = __shfl_xor(bk, off, RR_WAVE), oi = __shfl_xor(bi, off, RR_WAVE);
-      if (se_replaces(ok, oi, bk, bi)) { bk = ok; bi = oi; }
-    }
-    if (lane == 0) { s_prev[wave].k = bk; s_prev[wave].i = bi; }
-    __syncthreads();
-    bk = s_prev[0].k; bi = s_prev[0].i;
-#pragma unroll
-    for (int w = 1; w < SE_WAVES; ++w)
-      if (se_replaces(s_prev[w].k, s_prev[w].i, bk, bi)) { bk = s_prev[w].k; bi = s_prev[w].i; }
+    rr_wave_first_max(bk, bi);
+    rc_join_waves(bk, bi, wave, s_prev);
     c = __builtin_amdgcn_readfirstlane(bi);
     if (blockIdx.x == 0 && tid == 0) *p.centre = c;
     if (c < 0) {                                  // no row is at -1, so none will be: nothing changes, no candidate
@@ -98,8 +77,8 @@ __global__ void __launch_bounds__(SE_NT) se_pass_kernel(const SeParams p) {
   }
 
   int best_k = 0, best_i = -1;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * SE_WAVES;
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * SE_WAVES + wave;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * RC_WAVES;
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * RC_WAVES + wave;
 
   // one row that is at -1 (or, in the initial launch, any row): `a` holds its columns (NG > 0); uniform per wave
   auto row_pass = [&](int64_t r, const f32x4 (&a)[NR], int k) {
@@ -113,7 +92,7 @@ __global__ void __launch_bounds__(SE_NT) se_pass_kernel(const SeParams p) {
       stays = !(d <= p.r2);
       if (!stays && lane == 0) p.labels[r] = p.t;
     }
-    if (stays && se_replaces(k, static_cast<int>(r), best_k, best_i)) { best_k = k; best_i = static_cast<int>(r); }
+    if (stays && rr_first_max_replaces(k, static_cast<int>(r), best_k, best_i)) { best_k = k; best_i = static_cast<int>(r); }
   };
 
   for (int64_t base = first; base < p.P; base += 64 * stride) {   // (uniform per wave)
@@ -138,56 +117,24 @@ __global__ void __launch_bounds__(SE_NT) se_pass_kernel(const SeParams p) {
     }
   }
 
-  if (lane == 0) { s_out[wave].k = best_k; s_out[wave].i = best_i; }
-  __syncthreads();
-  if (tid == 0) {
-    int bk = s_out[0].k, bi = s_out[0].i;
-#pragma unroll
-    for (int w = 1; w < SE_WAVES; ++w)
-      if (se_replaces(s_out[w].k, s_out[w].i, bk, bi)) { bk = s_out[w].k; bi = s_out[w].i; }
+  rc_block_best(best_k, best_i, wave, s_out, [&](int bk, int bi) {
     p.out[1 + blockIdx.x].k = bk;
     p.out[1 + blockIdx.x].i = bi;
     if (blockIdx.x == 0) { p.out[0].k = static_cast<int32_t>(gridDim.x); p.out[0].i = 0; }
-  }
-}
-
-// P == 0: every slot of centres is padding
-__global__ void __launch_bounds__(SE_NT) se_pad_kernel(int32_t* centres, int n) {
-  for (int k = blockIdx.x * SE_NT + threadIdx.x; k < n; k += gridDim.x * SE_NT) centres[k] = -1;
+  });
 }
 
 // the workspace: two pair arrays sized for the largest grid (so the size does not depend on the blocks setting), each behind
 // its count slot
-constexpr size_t SE_PAIRS_BYTES = static_cast<size_t>(SE_MAX_BLOCKS + 1) * sizeof(SePair);
+constexpr size_t SE_PAIRS_BYTES = static_cast<size_t>(RC_MAX_BLOCKS + 1) * sizeof(SePair);
 constexpr size_t SE_WORKSPACE = 2 * SE_PAIRS_BYTES;
-
-int se_grid(int64_t P) {
-  int64_t b = g_blocks.load(std::memory_order_relaxed);
-  if (b == 0) {                                   // automatic: two rows per wave and launch at least, 16 waves per CU at most
-    b = (P + 2 * SE_WAVES - 1) / (2 * SE_WAVES);
-    if (b > SE_AUTO_BLOCKS) b = SE_AUTO_BLOCKS;
-    if (b < 1) b = 1;
-  }
-  return static_cast<int>(b);
-}
-
-template <int NG>
-void se_launch(bool vec, int grid, hipStream_t s, const SeParams& p) {
-  if (vec) se_pass_kernel<NG, true><<<grid, SE_NT, 0, s>>>(p);
-  else se_pass_kernel<NG, false><<<grid, SE_NT, 0, s>>>(p);
-}
 
 }  // namespace
 
 extern "C" {
 
-int rr_sphere_exclusion_blocks(void) { return g_blocks.load(std::memory_order_relaxed); }
-
-int rr_sphere_exclusion_set_blocks(int blocks) {
-  RR_CHECK_ARG(blocks >= 0 && blocks <= SE_MAX_BLOCKS);
-  g_blocks.store(blocks, std::memory_order_relaxed);
-  return RR_OK;
-}
+int rr_sphere_exclusion_blocks(void) { return g_blocks.get(); }
+int rr_sphere_exclusion_set_blocks(int blocks) { return g_blocks.set(blocks, RC_MAX_BLOCKS); }
 
 int rr_sphere_exclusion_workspace_bytes(int64_t P, size_t* bytes) {
   RR_CHECK_ARG(bytes && P >= 0);
@@ -207,16 +154,14 @@ int rr_sphere_exclusion_f32(const float* x, int64_t ld, int64_t P, int H, float 
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (P == 0) {
     if (n_rounds == 0) return RR_OK;
-    se_pad_kernel<<<rr_grid_for(n_rounds, SE_NT, 64), SE_NT, 0, s>>>(centres, n_rounds);
+    rc_pad_kernel<false><<<rr_grid_for(n_rounds, RC_NT, 64), RC_NT, 0, s>>>(centres, nullptr, n_rounds);
     return rr_launch_status();
   }
   char* ws = static_cast<char*>(workspace);
   SePair* pairs[2] = {reinterpret_cast<SePair*>(ws), reinterpret_cast<SePair*>(ws + SE_PAIRS_BYTES)};
   SeParams p;
   p.x = x; p.ld = ld; p.P = P; p.H = H; p.r2 = r2; p.key = key; p.labels = labels;
-  const int grid = se_grid(P);
-  const bool vec = rr_aligned16(x) && (ld % 4 == 0);
-  const int groups = (H + 3) / 4, ng = (groups + 63) / 64;
+  const int grid = rc_grid(g_blocks.get(), P);
   // launch j = -1 is the initial one; the launch of round t reads pairs[t & 1] and writes pairs[(t + 1) & 1]
   for (int j = first_round == 0 ? -1 : 0; j < n_rounds; ++j) {
     const int t = first_round + (j < 0 ? 0 : j);
@@ -224,13 +169,9 @@ int rr_sphere_exclusion_f32(const float* x, int64_t ld, int64_t P, int H, float 
     p.centre = j < 0 ? nullptr : centres + j;
     p.prev = pairs[t & 1];
     p.out = j < 0 ? pairs[0] : pairs[(t + 1) & 1];
-    switch (ng <= SE_MAX_NG ? ng : 0) {
-      case 1: se_launch<1>(vec, grid, s, p); break;
-      case 2: se_launch<2>(vec, grid, s, p); break;
-      case 3: se_launch<3>(vec, grid, s, p); break;
-      case 4: se_launch<4>(vec, grid, s, p); break;
-      default: se_launch<0>(vec, grid, s, p); break;
-    }
+    rc_dispatch(H, x, ld, [&](auto ng, auto vec) {
+      se_pass_kernel<decltype(ng)::value, decltype(vec)::value><<<grid, RC_NT, 0, s>>>(p);
+    });
     const int st = rr_launch_status();
     if (st != RR_OK) return st;
   }

@@ -3,7 +3,8 @@
 //
 //   d(i, c) = sum_h (x[i,h] - x[c,h])^2 in f32 by the fixed chain: columns in groups of four, lane l of the wave owns the groups
 //   g with g % 64 == l (ascending, columns inside a group ascending), acc = acc + t * t with t = x[i,h] - x[c,h], the 64 chains
-//   joined by the butterfly xor 32, 16, 8, 4, 2, 1.  The chain and the row loads live in row_chain.h (csrc/cluster.hip shares them).
+//   joined by the butterfly xor 32, 16, 8, 4, 2, 1.  The chain, the row loads and the round scaffold (the join of the four
+//   waves, the workgroup's best pair, the grid rule, the NG / VEC dispatch) live in row_chain.h (csrc/cluster.hip shares them).
 //
 // kc_pass_kernel<NG, VEC> is the only kernel of a selection; n_pick + 1 launches of it run back to back on the caller's stream:
 //   launch 0       writes min_dist / assign / the eligibility bytes (the one extra read of the pool: it finds the rows that hold
@@ -16,22 +17,13 @@
 // signals another workgroup, and there are no atomics.  One wave per row, rows grid-strided, two rows in flight per wave.
 // NG = groups a lane owns (1 .. 4: H <= 1024, the centre in 4 NG registers); NG == 0 is the loop for wider rows, which re-reads
 // the centre's columns (L1 / L2 hits).  VEC: 16-byte loads (pointer 16-byte aligned and ld % 4 == 0), else 4-byte loads.
-#include "rr_common.h"
 #include "row_chain.h"
-
-#include <atomic>
 
 namespace {
 
-constexpr int KC_NT = 256;                        // threads (4 waves: 4 rows per workgroup and grid pass)
-constexpr int KC_WAVES = KC_NT / 64;
-constexpr int KC_MAX_BLOCKS = 4096;
-constexpr int KC_MAX_NG = 4;                      // register path up to H = 256 * KC_MAX_NG
-constexpr int KC_AUTO_BLOCKS = RR_NUM_CU * 4;     // 16 waves per CU: measured best or within 4 % of it from P = 10^4 to 10^6
+BlocksKnob g_blocks;
 
-std::atomic<int> g_blocks{0};
-
-struct __attribute__((aligned(8))) KcPair { float s; int32_t i; };   // i < 0: no eligible row
+typedef RowPair<float> KcPair;                    // (score, index)
 
 struct KcParams {
   const float* x; int64_t ld; int64_t P; int H;
@@ -44,8 +36,8 @@ struct KcParams {
 };
 
 template <int NG, bool VEC>
-__global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
-  __shared__ KcPair s_prev[KC_WAVES], s_out[KC_WAVES];
+__global__ void __launch_bounds__(RC_NT) kc_pass_kernel(const KcParams p) {
+  __shared__ KcPair s_prev[RC_WAVES], s_out[RC_WAVES];
   constexpr int NR = NG > 0 ? NG : 1;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -56,26 +48,24 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
   f32x4 cv[NR];
   const float* crow = p.x;
   if (t > 0) {
+    // The scan over the grid's pairs stays here (and in se_pass_kernel, which adds its count slot and index guard): as one
+    // helper with the join it cost the NG == 3 kernels, at the SGPR cap, up to 38 instructions and measured 0.4 - 1.5 % on
+    // weighted picks at H = 600 (profiles/embedding_shared_ab.txt).
     float bs = 0.f;
     int bi = -1;
-    for (int k = tid; k < static_cast<int>(gridDim.x); k += KC_NT) {
+    for (int k = tid; k < static_cast<int>(gridDim.x); k += RC_NT) {
       const KcPair q = p.prev[k];
-      if (rr_first_max_replaces(q.s, q.i, bs, bi)) { bs = q.s; bi = q.i; }
+      if (rr_first_max_replaces(q.k, q.i, bs, bi)) { bs = q.k; bi = q.i; }
     }
     rr_wave_first_max(bs, bi);
-    if (lane == 0) { s_prev[wave].s = bs; s_prev[wave].i = bi; }
-    __syncthreads();
-    bs = s_prev[0].s; bi = s_prev[0].i;
-#pragma unroll
-    for (int w = 1; w < KC_WAVES; ++w)
-      if (rr_first_max_replaces(s_prev[w].s, s_prev[w].i, bs, bi)) { bs = s_prev[w].s; bi = s_prev[w].i; }
+    rc_join_waves(bs, bi, wave, s_prev);
     c = __builtin_amdgcn_readfirstlane(bi);
     if (blockIdx.x == 0 && tid == 0) {
       p.picks[t - 1] = c;
       p.gain[t - 1] = c >= 0 ? bs : -1.0f;
     }
     if (c < 0) {                                  // nothing was eligible, so nothing will be: no update, no candidate
-      if (tid == 0 && !p.last) { p.out[blockIdx.x].s = 0.f; p.out[blockIdx.x].i = -1; }
+      if (tid == 0 && !p.last) { p.out[blockIdx.x].k = 0.f; p.out[blockIdx.x].i = -1; }
       return;
     }
     crow = p.x + static_cast<int64_t>(c) * p.ld;
@@ -84,8 +74,8 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
 
   float best_s = 0.f;
   int best_i = -1;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * KC_WAVES;
-  const int64_t first = static_cast<int64_t>(blockIdx.x) * KC_WAVES + wave;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * RC_WAVES;
+  const int64_t first = static_cast<int64_t>(blockIdx.x) * RC_WAVES + wave;
 
   // one row: `a` holds its columns (NG > 0); every lane leaves with the same values
   auto row_pass = [&](int64_t r, const f32x4 (&a)[NR], float md_in, float w, int e_in) {
@@ -149,60 +139,22 @@ __global__ void __launch_bounds__(KC_NT) kc_pass_kernel(const KcParams p) {
   }
 
   if (p.last) return;
-  if (lane == 0) { s_out[wave].s = best_s; s_out[wave].i = best_i; }
-  __syncthreads();
-  if (tid == 0) {
-    float bs = s_out[0].s;
-    int bi = s_out[0].i;
-#pragma unroll
-    for (int w = 1; w < KC_WAVES; ++w)
-      if (rr_first_max_replaces(s_out[w].s, s_out[w].i, bs, bi)) { bs = s_out[w].s; bi = s_out[w].i; }
-    p.out[blockIdx.x].s = bs;
+  rc_block_best(best_s, best_i, wave, s_out, [&](float bs, int bi) {
+    p.out[blockIdx.x].k = bs;
     p.out[blockIdx.x].i = bi;
-  }
+  });
 }
-
-// P == 0: every slot of picks / gain is padding
-__global__ void __launch_bounds__(KC_NT) kc_pad_kernel(int32_t* picks, float* gain, int n) {
-  for (int k = blockIdx.x * KC_NT + threadIdx.x; k < n; k += gridDim.x * KC_NT) {
-    picks[k] = -1;
-    gain[k] = -1.0f;
-  }
-}
-
-inline size_t kc_round(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
 // the workspace: two pair arrays sized for the largest grid (so the size does not depend on the blocks setting), then elig [P]
-constexpr size_t KC_PAIRS_BYTES = static_cast<size_t>(KC_MAX_BLOCKS) * sizeof(KcPair);
-inline size_t kc_workspace(int64_t P) { return 2 * KC_PAIRS_BYTES + kc_round(static_cast<size_t>(P)); }
-
-int kc_grid(int64_t P) {
-  int64_t b = g_blocks.load(std::memory_order_relaxed);
-  if (b == 0) {                                   // automatic: two rows per wave and launch at least, 16 waves per CU at most
-    b = (P + 2 * KC_WAVES - 1) / (2 * KC_WAVES);
-    if (b > KC_AUTO_BLOCKS) b = KC_AUTO_BLOCKS;
-    if (b < 1) b = 1;
-  }
-  return static_cast<int>(b);
-}
-
-template <int NG>
-void kc_launch(bool vec, int grid, hipStream_t s, const KcParams& p) {
-  if (vec) kc_pass_kernel<NG, true><<<grid, KC_NT, 0, s>>>(p);
-  else kc_pass_kernel<NG, false><<<grid, KC_NT, 0, s>>>(p);
-}
+constexpr size_t KC_PAIRS_BYTES = static_cast<size_t>(RC_MAX_BLOCKS) * sizeof(KcPair);
+inline size_t kc_workspace(int64_t P) { return 2 * KC_PAIRS_BYTES + rr_round256(static_cast<size_t>(P)); }
 
 }  // namespace
 
 extern "C" {
 
-int rr_kcenter_blocks(void) { return g_blocks.load(std::memory_order_relaxed); }
-
-int rr_kcenter_set_blocks(int blocks) {
-  RR_CHECK_ARG(blocks >= 0 && blocks <= KC_MAX_BLOCKS);
-  g_blocks.store(blocks, std::memory_order_relaxed);
-  return RR_OK;
-}
+int rr_kcenter_blocks(void) { return g_blocks.get(); }
+int rr_kcenter_set_blocks(int blocks) { return g_blocks.set(blocks, RC_MAX_BLOCKS); }
 
 int rr_kcenter_workspace_bytes(int64_t P, int n_pick, size_t* bytes) {
   RR_CHECK_ARG(bytes && P >= 0 && n_pick >= 0);
@@ -221,7 +173,7 @@ int rr_kcenter_f32(const float* x, int64_t ld, int64_t P, int H, int n_pick, con
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (P == 0) {
     if (n_pick == 0) return RR_OK;
-    kc_pad_kernel<<<rr_grid_for(n_pick, KC_NT, 64), KC_NT, 0, s>>>(picks, gain, n_pick);
+    rc_pad_kernel<true><<<rr_grid_for(n_pick, RC_NT, 64), RC_NT, 0, s>>>(picks, gain, n_pick);
     return rr_launch_status();
   }
   char* ws = static_cast<char*>(workspace);
@@ -231,21 +183,15 @@ int rr_kcenter_f32(const float* x, int64_t ld, int64_t P, int H, int n_pick, con
   p.init_dist = init_dist; p.weight = weight;
   p.picks = picks; p.gain = gain; p.min_dist = min_dist; p.assign = assign;
   p.elig = reinterpret_cast<uint8_t*>(ws + 2 * KC_PAIRS_BYTES);
-  const int grid = kc_grid(P);
-  const bool vec = rr_aligned16(x) && (ld % 4 == 0);
-  const int groups = (H + 3) / 4, ng = (groups + 63) / 64;
+  const int grid = rc_grid(g_blocks.get(), P);
   for (int t = 0; t <= n_pick; ++t) {
     p.t = t;
     p.last = t == n_pick;
     p.prev = pairs[(t + 1) & 1];
     p.out = pairs[t & 1];
-    switch (ng <= KC_MAX_NG ? ng : 0) {
-      case 1: kc_launch<1>(vec, grid, s, p); break;
-      case 2: kc_launch<2>(vec, grid, s, p); break;
-      case 3: kc_launch<3>(vec, grid, s, p); break;
-      case 4: kc_launch<4>(vec, grid, s, p); break;
-      default: kc_launch<0>(vec, grid, s, p); break;
-    }
+    rc_dispatch(H, x, ld, [&](auto ng, auto vec) {
+      kc_pass_kernel<decltype(ng)::value, decltype(vec)::value><<<grid, RC_NT, 0, s>>>(p);
+    });
     const int st = rr_launch_status();
     if (st != RR_OK) return st;
   }

@@ -24,12 +24,11 @@
 // kn_walk is the one copy of that walk (staging, chunking, the k-tile skip, the split of the bank); knn_tile_kernel gives it the
 // list epilogue above, knn_count_kernel (rr_radius_count_f32, DESIGN section 4k: neighbours within a radius) a counting one
 // that needs neither the LDS distance tile nor a list.  Both form the distance through kn_dist.
+// kn_run is the one copy of the host side of both entries (checks, splits, workspace, the empty bank, norms, tile launch, merge).
 //
 // row_sqnorm_kernel: one wave per row; lane l sums x[h]^2 over h = l, l + 64, ... ascending (product rounded, then added), the
 // 64 partial sums are joined by the butterfly xor 32, 16, 8, 4, 2, 1.  4-byte loads only (a wave reads 256 contiguous bytes).
-#include "rr_common.h"
-
-#include <atomic>
+#include "row_chain.h"
 
 namespace {
 
@@ -69,19 +68,11 @@ struct KnCountParams : KnWalk {
   int32_t* part;                                  // S > 1: [M, S]
 };
 
-typedef const __attribute__((address_space(1))) f32x4* kn_gptr4;
-
-// four consecutive elements of a row from column c (c % 4 == 0), every load unconditional; elements at or past `width`, and
-// rows that do not exist, read as 0 (the address is clamped to a valid one and the value replaced)
+// four consecutive elements of a row from column c (c % 4 == 0): row_chain.h's load with elements at or past `width`, and rows
+// that do not exist, replaced by 0
 template <bool VEC>
 __device__ __forceinline__ f32x4 kn_load4(const float* row, int c, int width, bool row_ok) {
-  f32x4 v;
-  if (VEC) {
-    v = *(kn_gptr4)(row + (c < width ? c : 0));   // (VEC: ld % 4 == 0, so the chunk lies inside the row's pitch)
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[c + e < width ? c + e : 0];
-  }
+  f32x4 v = rr_load4<VEC>(row, c, width);
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = (row_ok && c + e < width) ? v[e] : 0.f;
   return v;
@@ -421,9 +412,6 @@ __global__ void __launch_bounds__(KN_NT) row_sqnorm_kernel(const float* x, int64
   if (lane == 0) out[r] = s;
 }
 
-inline bool kn_vec_ok(const float* p, int64_t ld) { return rr_aligned16(p) && (ld % 4 == 0); }
-inline size_t kn_round(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
 // the split count a search of this shape runs with
 int kn_splits(int64_t M, int64_t N) {
   const int64_t T = (N + KN_BANK - 1) / KN_BANK;
@@ -440,18 +428,19 @@ int kn_splits(int64_t M, int64_t N) {
   return static_cast<int>(S);
 }
 
-struct KnLayout { size_t qn, bn, part_d, part_i, total; };
-KnLayout kn_layout(int64_t M, int64_t N, int k, int S) {
+// the workspace of both entries: the norms, then the caller's partial-result area
+struct KnLayout { size_t qn, bn, part, total; };
+KnLayout kn_layout(int64_t M, int64_t N, size_t part_bytes) {
   KnLayout L;
   size_t o = 0;
-  L.qn = o; o += kn_round(static_cast<size_t>(M) * 4);
-  L.bn = o; o += kn_round(static_cast<size_t>(N) * 4);
-  const size_t part = S > 1 ? kn_round(static_cast<size_t>(M) * S * k * 4) : 0;
-  L.part_d = o; o += part;
-  L.part_i = o; o += part;
+  L.qn = o; o += rr_round256(static_cast<size_t>(M) * 4);
+  L.bn = o; o += rr_round256(static_cast<size_t>(N) * 4);
+  L.part = o; o += part_bytes;
   L.total = o > 256 ? o : 256;
   return L;
 }
+// one partial-result array [M, S, words] of 4-byte values; a single split writes the result itself
+inline size_t kn_part(int64_t M, int S, int words) { return S > 1 ? rr_round256(static_cast<size_t>(M) * S * words * 4) : 0; }
 
 int sqnorm_launch(const float* x, int64_t ld, int64_t rows, int H, float* out, hipStream_t s) {
   const int64_t blocks = (rows + KN_NT / 64 - 1) / (KN_NT / 64);
@@ -460,34 +449,71 @@ int sqnorm_launch(const float* x, int64_t ld, int64_t rows, int H, float* out, h
   return rr_launch_status();
 }
 
+// what both entries take from the C ABI, as given
+struct KnArgs {
+  const float* q; int64_t ld_q; int64_t M;
+  const float* bank; int64_t ld_b; int64_t N;
+  int H;
+  const int32_t* q_group; const int32_t* b_group; const float* bank_sqnorm;
+  void* workspace; size_t workspace_bytes;
+  hipStream_t s;
+};
+
+// what an entry adds: its checks of what only it takes, and its partial results - `arrays` arrays of [M, S, words] (kn_part)
+// behind the norms, merged by a kernel with merge_rows rows per workgroup
+struct KnEntry {
+  bool args_ok, supported;
+  int arrays, words, merge_rows;
+};
+
 // the walk's operands, with the norms both entries need: the query norms go to `qn`, the bank norms to `bn` unless the caller has them
-int kn_prepare(KnWalk& W, const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, int S,
-               const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, float* qn, float* bn, hipStream_t s) {
-  W.q = q; W.ld_q = ld_q; W.M = M;
-  W.b = bank; W.ld_b = ld_b; W.N = N;
-  W.H = H; W.S = S;
-  W.qg = q_group; W.bg = b_group;
-  int st = sqnorm_launch(q, ld_q, M, H, qn, s);
+int kn_prepare(KnWalk& W, const KnArgs& a, int S, float* qn, float* bn) {
+  W.q = a.q; W.ld_q = a.ld_q; W.M = a.M;
+  W.b = a.bank; W.ld_b = a.ld_b; W.N = a.N;
+  W.H = a.H; W.S = S;
+  W.qg = a.q_group; W.bg = a.b_group;
+  int st = sqnorm_launch(a.q, a.ld_q, a.M, a.H, qn, a.s);
   if (st != RR_OK) return st;
   W.qn = qn;
-  W.bn = bank_sqnorm;
-  if (!bank_sqnorm) {
-    st = sqnorm_launch(bank, ld_b, N, H, bn, s);
+  W.bn = a.bank_sqnorm;
+  if (!a.bank_sqnorm) {
+    st = sqnorm_launch(a.bank, a.ld_b, a.N, a.H, bn, a.s);
     W.bn = bn;
   }
   return st;
 }
 
-// the workspace of a count: the norms as in KnLayout, then the partial counts [M, S]
-struct KnCountLayout { size_t qn, bn, part, total; };
-KnCountLayout kn_count_layout(int64_t M, int64_t N, int S) {
-  KnCountLayout L;
-  size_t o = 0;
-  L.qn = o; o += kn_round(static_cast<size_t>(M) * 4);
-  L.bn = o; o += kn_round(static_cast<size_t>(N) * 4);
-  L.part = o; o += S > 1 ? kn_round(static_cast<size_t>(M) * S * 4) : 0;
-  L.total = o > 256 ? o : 256;
-  return L;
+// The host side of both entries.  tile(QV, BV, grid, part, each) launches the entry's tile kernel - `part` the first of its
+// partial-result arrays, `each` the bytes of one -, merge(part, each, S, blocks) its merge kernel; S == 0 (and no arrays) when the
+// bank is empty: the merge of nothing writes the padding.
+template <class Params, class Tile, class Merge>
+int kn_run(Params& P, const KnArgs& a, const KnEntry& e, Tile tile, Merge merge) {
+  RR_CHECK_ARG(e.args_ok && a.q && a.bank && a.workspace);
+  RR_CHECK_ARG((a.q_group == nullptr) == (a.b_group == nullptr));
+  RR_CHECK_ARG(a.M >= 0 && a.N >= 0 && a.H >= 1 && a.ld_q >= a.H && a.ld_b >= a.H);
+  if (!e.supported) return RR_ERR_UNSUPPORTED;
+  const int S = kn_splits(a.M, a.N);
+  const size_t each = kn_part(a.M, S, e.words);
+  const KnLayout L = kn_layout(a.M, a.N, e.arrays * each);
+  if (a.workspace_bytes < L.total) return RR_ERR_WORKSPACE;
+  if (a.M == 0) return RR_OK;
+  const int64_t row_tiles = (a.M + KN_ROWS - 1) / KN_ROWS, merge_blocks = (a.M + e.merge_rows - 1) / e.merge_rows;
+  if (merge_blocks > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
+  if (a.N == 0) {
+    merge(nullptr, 0, 0, static_cast<unsigned>(merge_blocks));
+    return rr_launch_status();
+  }
+  char* ws = static_cast<char*>(a.workspace);
+  int st = kn_prepare(P, a, S, reinterpret_cast<float*>(ws + L.qn), reinterpret_cast<float*>(ws + L.bn));
+  if (st != RR_OK) return st;
+  const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(S));
+  rr_vec_dispatch(rr_vec4_ok(a.q, a.ld_q), [&](auto qv) {
+    rr_vec_dispatch(rr_vec4_ok(a.bank, a.ld_b), [&](auto bv) { tile(qv, bv, grid, ws + L.part, each); });
+  });
+  st = rr_launch_status();
+  if (st != RR_OK || S == 1) return st;
+  merge(ws + L.part, each, S, static_cast<unsigned>(merge_blocks));
+  return rr_launch_status();
 }
 
 }  // namespace
@@ -517,92 +543,65 @@ int rr_row_sqnorm_f32(const float* x, int64_t ld, int64_t rows, int H, float* ou
 int rr_knn_workspace_bytes(int64_t M, int64_t N, int k, size_t* bytes) {
   RR_CHECK_ARG(bytes && M >= 0 && N >= 0 && k >= 1);
   if (k > RR_KNN_MAX_K || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
-  *bytes = kn_layout(M, N, k, kn_splits(M, N)).total;
+  *bytes = kn_layout(M, N, 2 * kn_part(M, kn_splits(M, N), k)).total;
   return RR_OK;
 }
 
 int rr_knn_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, int k,
                const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, float* dist, int32_t* idx,
                void* workspace, size_t workspace_bytes, rr_stream_t stream) {
-  RR_CHECK_ARG(q && bank && dist && idx && workspace);
-  RR_CHECK_ARG((q_group == nullptr) == (b_group == nullptr));
-  RR_CHECK_ARG(M >= 0 && N >= 0 && H >= 1 && k >= 1 && ld_q >= H && ld_b >= H);
-  if (k > RR_KNN_MAX_K || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
-  const int S = kn_splits(M, N);
-  const KnLayout L = kn_layout(M, N, k, S);
-  if (workspace_bytes < L.total) return RR_ERR_WORKSPACE;
-  if (M == 0) return RR_OK;
-  const int64_t row_tiles = (M + KN_ROWS - 1) / KN_ROWS, merge_blocks = (M + KN_NT / 64 - 1) / (KN_NT / 64);
-  if (merge_blocks > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
-  if (N == 0) {                                   // nothing to search: the merge of zero lists writes the padding
-    knn_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(nullptr, nullptr, M, 0, k, dist, idx);
-    return rr_launch_status();
-  }
+  const KnArgs a{q, ld_q, M, bank, ld_b, N, H, q_group, b_group, bank_sqnorm, workspace, workspace_bytes, s};
+  KnEntry e;
+  e.args_ok = dist && idx && k >= 1;
+  e.supported = k <= RR_KNN_MAX_K && N <= 0x7fffffffLL;
+  e.arrays = 2; e.words = k;                      // the lists: distances, then indices
+  e.merge_rows = KN_NT / 64;                      // one wave per row
   KnnParams P;
   P.k = k;
-  int st = kn_prepare(P, q, ld_q, M, bank, ld_b, N, H, S, q_group, b_group, bank_sqnorm, reinterpret_cast<float*>(ws + L.qn),
-                      reinterpret_cast<float*>(ws + L.bn), s);
-  if (st != RR_OK) return st;
   P.out_d = dist; P.out_i = idx;
-  P.part_d = reinterpret_cast<float*>(ws + L.part_d);
-  P.part_i = reinterpret_cast<int32_t*>(ws + L.part_i);
-  const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(S));
-  const bool qv = kn_vec_ok(q, ld_q), bv = kn_vec_ok(bank, ld_b);
-  if (qv && bv) knn_tile_kernel<true, true><<<grid, KN_NT, 0, s>>>(P);
-  else if (qv) knn_tile_kernel<true, false><<<grid, KN_NT, 0, s>>>(P);
-  else if (bv) knn_tile_kernel<false, true><<<grid, KN_NT, 0, s>>>(P);
-  else knn_tile_kernel<false, false><<<grid, KN_NT, 0, s>>>(P);
-  st = rr_launch_status();
-  if (st != RR_OK || S == 1) return st;
-  knn_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(P.part_d, P.part_i, M, S, k, dist, idx);
-  return rr_launch_status();
+  return kn_run(
+      P, a, e,
+      [&](auto qv, auto bv, dim3 grid, char* part, size_t each) {
+        P.part_d = reinterpret_cast<float*>(part);
+        P.part_i = reinterpret_cast<int32_t*>(part + each);
+        knn_tile_kernel<decltype(qv)::value, decltype(bv)::value><<<grid, KN_NT, 0, s>>>(P);
+      },
+      [&](const char* part, size_t each, int S, unsigned blocks) {
+        knn_merge_kernel<<<blocks, KN_NT, 0, s>>>(reinterpret_cast<const float*>(part), reinterpret_cast<const int32_t*>(part + each),
+                                                  M, S, k, dist, idx);
+      });
 }
 
 int rr_radius_count_workspace_bytes(int64_t M, int64_t N, size_t* bytes) {
   RR_CHECK_ARG(bytes && M >= 0 && N >= 0);
   if (M > 0x7fffffffLL || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
-  *bytes = kn_count_layout(M, N, kn_splits(M, N)).total;
+  *bytes = kn_layout(M, N, kn_part(M, kn_splits(M, N), 1)).total;
   return RR_OK;
 }
 
 int rr_radius_count_f32(const float* q, int64_t ld_q, int64_t M, const float* bank, int64_t ld_b, int64_t N, int H, float r2,
                         const int32_t* q_group, const int32_t* b_group, const float* bank_sqnorm, int32_t* count,
                         void* workspace, size_t workspace_bytes, rr_stream_t stream) {
-  RR_CHECK_ARG(q && bank && count && workspace);
-  RR_CHECK_ARG((q_group == nullptr) == (b_group == nullptr));
-  RR_CHECK_ARG(M >= 0 && N >= 0 && H >= 1 && ld_q >= H && ld_b >= H);
-  RR_CHECK_ARG(r2 >= 0.f);                        // (false for a NaN)
-  if (M > 0x7fffffffLL || N > 0x7fffffffLL) return RR_ERR_UNSUPPORTED;
-  const int S = kn_splits(M, N);
-  const KnCountLayout L = kn_count_layout(M, N, S);
-  if (workspace_bytes < L.total) return RR_ERR_WORKSPACE;
-  if (M == 0) return RR_OK;
-  const int64_t row_tiles = (M + KN_ROWS - 1) / KN_ROWS, merge_blocks = (M + KN_NT - 1) / KN_NT;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  char* ws = static_cast<char*>(workspace);
-  if (N == 0) {                                   // nothing to count: the sum of zero partial counts
-    knn_count_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(nullptr, M, 0, count);
-    return rr_launch_status();
-  }
+  const KnArgs a{q, ld_q, M, bank, ld_b, N, H, q_group, b_group, bank_sqnorm, workspace, workspace_bytes, s};
+  KnEntry e;
+  e.args_ok = count && r2 >= 0.f;                 // (false for a NaN)
+  e.supported = M <= 0x7fffffffLL && N <= 0x7fffffffLL;
+  e.arrays = 1; e.words = 1;                      // one count per row and split
+  e.merge_rows = KN_NT;                           // one thread per row
   KnCountParams P;
   P.r2 = r2;
-  int st = kn_prepare(P, q, ld_q, M, bank, ld_b, N, H, S, q_group, b_group, bank_sqnorm, reinterpret_cast<float*>(ws + L.qn),
-                      reinterpret_cast<float*>(ws + L.bn), s);
-  if (st != RR_OK) return st;
   P.out = count;
-  P.part = reinterpret_cast<int32_t*>(ws + L.part);
-  const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(S));
-  const bool qv = kn_vec_ok(q, ld_q), bv = kn_vec_ok(bank, ld_b);
-  if (qv && bv) knn_count_kernel<true, true><<<grid, KN_NT, 0, s>>>(P);
-  else if (qv) knn_count_kernel<true, false><<<grid, KN_NT, 0, s>>>(P);
-  else if (bv) knn_count_kernel<false, true><<<grid, KN_NT, 0, s>>>(P);
-  else knn_count_kernel<false, false><<<grid, KN_NT, 0, s>>>(P);
-  st = rr_launch_status();
-  if (st != RR_OK || S == 1) return st;
-  knn_count_merge_kernel<<<static_cast<unsigned>(merge_blocks), KN_NT, 0, s>>>(P.part, M, S, count);
-  return rr_launch_status();
+  return kn_run(
+      P, a, e,
+      [&](auto qv, auto bv, dim3 grid, char* part, size_t) {
+        P.part = reinterpret_cast<int32_t*>(part);
+        knn_count_kernel<decltype(qv)::value, decltype(bv)::value><<<grid, KN_NT, 0, s>>>(P);
+      },
+      [&](const char* part, size_t, int S, unsigned blocks) {
+        knn_count_merge_kernel<<<blocks, KN_NT, 0, s>>>(reinterpret_cast<const int32_t*>(part), M, S, count);
+      });
 }
 
 }  // extern "C"

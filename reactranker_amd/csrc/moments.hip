@@ -3,7 +3,9 @@
 // a port; include/reactranker_hip.h states both.
 //
 // rr_col_moments_f64: five launches on the caller's stream, no atomics, nothing that depends on an order of arrival.
-//   mo_flag_kernel     one wavefront per row (rows grid-strided): flags[n] = 1 when every value of row n is finite, else 0
+//   mo_flag_kernel     one wavefront per row (rows grid-strided): flags[n] = 1 when every value of row n is finite, else 0 (the
+//                      finite rule and the row load are row_chain.h's, shared with kcenter.hip and cluster.hip; the loop
+//                      over the row is written out here, see the kernel)
 //   mo_colsum_kernel   grid = 64-column blocks x chunks.  A thread owns four columns and the rows q, q + 16, ... of its chunk
 //                      (q = 0..15); the 16 partial sums of a column are added in ascending q.  Block 0 also counts the chunk's rows.
 //   mo_mean_kernel     mean[h] = (0.0 + chunk sums ascending) / n_used, n_used = the chunks' row counts added up
@@ -25,9 +27,7 @@
 //   C / D      lane holds columns r0 + 16 b + 4 (lane >> 4) + e, e = 0..3, of row n0 + 16 w + (lane & 15)
 // - knn's chain over h.  A lane keeps the running sum of y^2 over its columns (r ascending); the four lanes of a row are joined
 // by the butterfly xor 32, 16.
-#include "rr_common.h"
-
-#include <atomic>
+#include "row_chain.h"
 
 namespace {
 
@@ -48,9 +48,8 @@ constexpr int CP_KC = 64;                         // columns of x / rows of W st
 constexpr int CP_RC = 64;                         // columns of W per group
 constexpr int CP_SP = CP_KC + 4;                  // pitch of the staged operands (knn.hip: KN_SP)
 
-std::atomic<int> g_blocks{0};
+BlocksKnob g_blocks;
 
-typedef const __attribute__((address_space(1))) f32x4* mo_gptr4;
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
@@ -68,51 +67,36 @@ inline int mo_chunks(int64_t N, int H) {
 }
 inline int64_t mo_chunk_rows(int64_t N, int chunks) { return (N + chunks - 1) / chunks; }
 
-inline size_t mo_round(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
 struct MoLayout { size_t flags, cnt, colsum, slabs, total; };
 inline MoLayout mo_layout(int64_t N, int H) {
   const int chunks = mo_chunks(N, H);
   const size_t hp = static_cast<size_t>(mo_hp(H));
   MoLayout L;
   size_t o = 0;
-  L.flags = o; o += mo_round(static_cast<size_t>(N));
-  L.cnt = o; o += mo_round(static_cast<size_t>(chunks) * sizeof(long long));
-  L.colsum = o; o += mo_round(static_cast<size_t>(chunks) * hp * sizeof(double));
-  L.slabs = o; o += mo_round(static_cast<size_t>(chunks) * hp * hp * sizeof(double));
+  L.flags = o; o += rr_round256(static_cast<size_t>(N));
+  L.cnt = o; o += rr_round256(static_cast<size_t>(chunks) * sizeof(long long));
+  L.colsum = o; o += rr_round256(static_cast<size_t>(chunks) * hp * sizeof(double));
+  L.slabs = o; o += rr_round256(static_cast<size_t>(chunks) * hp * hp * sizeof(double));
   L.total = o;
   return L;
 }
-
-// columns c .. c + 3 of a row (c % 4 == 0), every load unconditional: the address of a column at or past `width` is clamped to a
-// valid one; what it holds is masked where it is used
-template <bool VEC>
-__device__ __forceinline__ f32x4 mo_load4(const float* row, int c, int width) {
-  f32x4 v;
-  if (VEC) {
-    v = *(mo_gptr4)(row + (c < width ? c : 0));   // (VEC: ld % 4 == 0, so the group lies inside the row's pitch)
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = row[c + e < width ? c + e : 0];
-  }
-  return v;
-}
-
-__device__ __forceinline__ bool mo_finite(float v) { return fabsf(v) < __builtin_inff(); }
 
 template <bool VEC>
 __global__ void __launch_bounds__(MO_NT) mo_flag_kernel(const float* x, int64_t ld, int64_t N, int H, uint8_t* flags) {
   const int lane = threadIdx.x & 63;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * MO_WAVES;
   for (int64_t r = static_cast<int64_t>(blockIdx.x) * MO_WAVES + (threadIdx.x >> 6); r < N; r += stride) {   // (uniform per wave)
+    // row_chain.h's kc_row_finite_any(row, lane, H), written out: as a call it changes this kernel's registers (next_free_vgpr
+    // 15 -> 16 without VEC, next_free_sgpr 36 -> 32 with it) and measured 2.6 % on the moments of 10^5 x 600
+    // (profiles/embedding_shared_ab.txt).  The load and the rule are the shared ones.
     const float* row = x + r * ld;
     bool ok = true;
     for (int g0 = 0; 4 * g0 < H; g0 += 64) {
       const int c = 4 * (g0 + lane);
       if (c < H) {
-        const f32x4 v = mo_load4<VEC>(row, c, H);
+        const f32x4 v = rr_load4<VEC>(row, c, H);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) ok = ok && (c + e >= H || mo_finite(v[e]));
+        for (int e = 0; e < 4; ++e) ok = ok && (c + e >= H || rr_finite(v[e]));
       }
     }
     ok = __all(ok);
@@ -134,7 +118,7 @@ __global__ void __launch_bounds__(MO_NT) mo_colsum_kernel(const float* x, int64_
   long long n = 0;
   for (int64_t r = r0 + q; r < r1; r += MO_QL) {
     const bool on = flags[r] != 0;
-    const f32x4 v = mo_load4<VEC>(x + r * ld, col, H);
+    const f32x4 v = rr_load4<VEC>(x + r * ld, col, H);
 #pragma unroll
     for (int e = 0; e < 4; ++e) s[e] = s[e] + ((on && col + e < H) ? static_cast<double>(v[e]) : 0.0);
     n += on ? 1 : 0;
@@ -207,7 +191,7 @@ __global__ void __launch_bounds__(MO_NT) mo_scatter_kernel(const float* x, int64
     for (int u = 0; u < MO_ROWS / 8; ++u) {
       const int64_t row = r + srow + 8 * u;
       const bool ok = row < r1 && flags[row < r1 ? row : r0] != 0;
-      const f32x4 v = mo_load4<VEC>(x + (row < r1 ? row : r0) * ld, gcol, H);
+      const f32x4 v = rr_load4<VEC>(x + (row < r1 ? row : r0) * ld, gcol, H);
       double c[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) c[e] = (ok && gcol + e < H) ? static_cast<double>(v[e]) - m4[e] : 0.0;
@@ -293,7 +277,7 @@ __global__ void __launch_bounds__(MO_NT) cp_kernel(const CpParams P) {
         for (int u = 0; u < CP_ROWS / 16; ++u) {
           const int64_t m = n0 + xrow + 16 * u;
           const bool ok = m < P.N;
-          f32x4 v = mo_load4<VEC>(P.x + (ok ? m : 0) * P.ld, c, H);
+          f32x4 v = rr_load4<VEC>(P.x + (ok ? m : 0) * P.ld, c, H);
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = (ok && c + e < H) ? v[e] - ce[e] : 0.f;
           *reinterpret_cast<f32x4*>(xs + (xrow + 16 * u) * CP_SP + xc4) = v;
@@ -339,11 +323,9 @@ __global__ void __launch_bounds__(MO_NT) cp_kernel(const CpParams P) {
   }
 }
 
-inline bool mo_vec_ok(const float* p, int64_t ld) { return rr_aligned16(p) && (ld % 4 == 0); }
-
 // workgroups of a grid-strided launch over `items` workgroups' worth of work
 inline int mo_grid(int64_t items) {
-  int64_t b = g_blocks.load(std::memory_order_relaxed);
+  int64_t b = g_blocks.get();
   if (b == 0) b = items < MO_AUTO_BLOCKS ? items : MO_AUTO_BLOCKS;
   if (b < 1) b = 1;
   return static_cast<int>(b);
@@ -353,13 +335,8 @@ inline int mo_grid(int64_t items) {
 
 extern "C" {
 
-int rr_moments_blocks(void) { return g_blocks.load(std::memory_order_relaxed); }
-
-int rr_moments_set_blocks(int blocks) {
-  RR_CHECK_ARG(blocks >= 0 && blocks <= MO_MAX_BLOCKS);
-  g_blocks.store(blocks, std::memory_order_relaxed);
-  return RR_OK;
-}
+int rr_moments_blocks(void) { return g_blocks.get(); }
+int rr_moments_set_blocks(int blocks) { return g_blocks.set(blocks, MO_MAX_BLOCKS); }
 
 int rr_moments_chunks(int64_t N, int H) {
   if (N < 0 || H < 1 || H > RR_MOMENTS_MAX_H) return 0;
@@ -388,23 +365,20 @@ int rr_col_moments_f64(const float* x, int64_t ld, int64_t N, int H, double* mea
   double* slabs = reinterpret_cast<double*>(ws + L.slabs);
   const int chunks = mo_chunks(N, H), hp = mo_hp(H), T = hp / MO_TILE;
   const int64_t rpc = mo_chunk_rows(N, chunks);
-  const bool vec = mo_vec_ok(x, ld);
+  const bool vec = rr_vec4_ok(x, ld);
   int st;
   if (N > 0) {
     const int grid = mo_grid((N + MO_WAVES - 1) / MO_WAVES);
-    if (vec) mo_flag_kernel<true><<<grid, MO_NT, 0, s>>>(x, ld, N, H, flags);
-    else mo_flag_kernel<false><<<grid, MO_NT, 0, s>>>(x, ld, N, H, flags);
+    rr_vec_dispatch(vec, [&](auto v) { mo_flag_kernel<decltype(v)::value><<<grid, MO_NT, 0, s>>>(x, ld, N, H, flags); });
     if ((st = rr_launch_status()) != RR_OK) return st;
   }
   const dim3 gsum(static_cast<unsigned>(T), static_cast<unsigned>(chunks));
-  if (vec) mo_colsum_kernel<true><<<gsum, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, sums, cnt);
-  else mo_colsum_kernel<false><<<gsum, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, sums, cnt);
+  rr_vec_dispatch(vec, [&](auto v) { mo_colsum_kernel<decltype(v)::value><<<gsum, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, sums, cnt); });
   if ((st = rr_launch_status()) != RR_OK) return st;
   mo_mean_kernel<<<mo_grid((H + MO_NT - 1) / MO_NT), MO_NT, 0, s>>>(sums, cnt, chunks, H, hp, mean, reinterpret_cast<long long*>(n_used));
   if ((st = rr_launch_status()) != RR_OK) return st;
   const dim3 gsc(static_cast<unsigned>(T * (T + 1) / 2), static_cast<unsigned>(chunks));
-  if (vec) mo_scatter_kernel<true><<<gsc, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, mean, slabs);
-  else mo_scatter_kernel<false><<<gsc, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, mean, slabs);
+  rr_vec_dispatch(vec, [&](auto v) { mo_scatter_kernel<decltype(v)::value><<<gsc, MO_NT, 0, s>>>(x, ld, N, H, hp, rpc, flags, mean, slabs); });
   if ((st = rr_launch_status()) != RR_OK) return st;
   mo_finish_kernel<<<mo_grid((static_cast<int64_t>(H) * H + MO_NT - 1) / MO_NT), MO_NT, 0, s>>>(slabs, chunks, H, hp, scatter);
   return rr_launch_status();
@@ -421,8 +395,7 @@ int rr_center_project_f32(const float* x, int64_t ld, int64_t N, int H, const fl
   P.center = center; P.W = W; P.y = y; P.sq = sq;
   const int grid = mo_grid((N + CP_ROWS - 1) / CP_ROWS);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mo_vec_ok(x, ld)) cp_kernel<true><<<grid, MO_NT, 0, s>>>(P);
-  else cp_kernel<false><<<grid, MO_NT, 0, s>>>(P);
+  rr_vec_dispatch(rr_vec4_ok(x, ld), [&](auto v) { cp_kernel<decltype(v)::value><<<grid, MO_NT, 0, s>>>(P); });
   return rr_launch_status();
 }
 

@@ -25,7 +25,7 @@ constexpr int RS_MAX_BLOCKS = 4096;
 constexpr int64_t RS_MAX_Q = 1 << 20;             // row() = (draw * Q) >> 32 is uniform to 2.4e-4 relative up to here (header)
 constexpr int RS_MAX_NC = 16;
 
-std::atomic<int> g_blocks{0};
+BlocksKnob g_blocks;                             // (wave_util.h: the storage only; rs_grid is this file's own rule)
 
 struct RsParams {
   const double* x; int64_t ld; int64_t Q; int M;
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(RS_NT) rs_kernel(const RsParams p) {
 // per CU beyond (33 against 46 ms at 10^5 x 20); the sign flip, which walks the rows in order, takes three workgroups per two
 // CUs there (22.9 against 24.6 ms).
 int rs_grid(int64_t B, int64_t table_bytes, int mode) {
-  int64_t b = g_blocks.load(std::memory_order_relaxed);
+  int64_t b = g_blocks.get();
   if (b == 0) {
     const int64_t beyond_l2 = mode == RR_RESAMPLE_SIGNFLIP ? 3 * RR_NUM_CU / 2 : RR_NUM_CU;
     const int64_t cap = table_bytes <= (32 << 10) ? RS_MAX_BLOCKS : table_bytes <= (4 << 20) ? 2 * RR_NUM_CU : beyond_l2;
@@ -166,13 +166,8 @@ void rs_launch(bool vec, int mode, int grid, hipStream_t s, const RsParams& p) {
 
 extern "C" {
 
-int rr_resample_blocks(void) { return g_blocks.load(std::memory_order_relaxed); }
-
-int rr_resample_set_blocks(int blocks) {
-  RR_CHECK_ARG(blocks >= 0 && blocks <= RS_MAX_BLOCKS);
-  g_blocks.store(blocks, std::memory_order_relaxed);
-  return RR_OK;
-}
+int rr_resample_blocks(void) { return g_blocks.get(); }
+int rr_resample_set_blocks(int blocks) { return g_blocks.set(blocks, RS_MAX_BLOCKS); }
 
 uint32_t rr_resample_draw_host(uint64_t seed, uint64_t j) { return rr_resample_draw(seed, j); }
 

@@ -9,6 +9,7 @@
 #define __host__
 #define __device__
 #endif
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/reactranker_hip.h"
@@ -50,6 +51,10 @@ __device__ __forceinline__ void rr_amax_put(float* slot, float m) {       // one
 #endif
 
 static inline bool rr_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// may the rows of a float matrix be read in 16-byte groups?  (a null pointer passes: the caller says what null means)
+static inline bool rr_vec4_ok(const void* p, int64_t ld) { return rr_aligned16(p) && (ld % 4 == 0); }
+// a workspace section's size: whole 256-byte lines
+static inline size_t rr_round256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
 // Grid cap of the grid-stride streaming kernels.  Every pass of such a loop ends in a store and starts with
 // a load whose s_waitcnt also retires that store (vmcnt counts loads and stores in issue order), so a thread
@@ -163,15 +168,18 @@ __device__ __forceinline__ T rr_wave_max(T v) {
 __device__ __forceinline__ bool rr_precedes(float xj, int j, float xi, int i) { return xj > xi || (xj == xi && j < i); }
 
 // The first maximum - rank 0 of that order - kept as a running (value, position) pair, position -1 = none yet: does (ov, oi)
-// replace (v, i)?  Written out, not built on rr_precedes: that form costs the top-1 kernels 25 instructions each.
-__device__ __forceinline__ bool rr_first_max_replaces(float ov, int oi, float v, int i) {
+// replace (v, i)?  Written out, not built on rr_precedes: that form costs the top-1 kernels 25 instructions each.  T is float
+// (a score) or int (a key).
+template <typename T>
+__device__ __forceinline__ bool rr_first_max_replaces(T ov, int oi, T v, int i) {
   return oi >= 0 && (i < 0 || ov > v || (ov == v && oi < i));
 }
 // (value, position) of the first maximum across the wave, valid in every lane; position -1 = this lane saw no candidate
-__device__ __forceinline__ void rr_wave_first_max(float& v, int& i) {
+template <typename T>
+__device__ __forceinline__ void rr_wave_first_max(T& v, int& i) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
-    const float ov = __shfl_xor(v, off, RR_WAVE);
+    const T ov = __shfl_xor(v, off, RR_WAVE);
     const int oi = __shfl_xor(i, off, RR_WAVE);
     if (rr_first_max_replaces(ov, oi, v, i)) { v = ov; i = oi; }
   }

@@ -1,9 +1,9 @@
 // Helpers of the per-list kernels - one wavefront per list (loss.hip, task_loss.hip, pairwise.hip, lambdarank.hip, uq.hip) or one
 // workgroup of one or four (approx_ndcg.hip, rank_corr.hip, calibration.hip): the list-length cap and wave-level synchronisation;
 // on the host side the dynamic-LDS opt-in, the argument check, the words per staged array (list_words, list_words4), the wave
-// knob of the one-or-four-wave kernels (WaveKnob) and the one launch of a "one workgroup per query" kernel (launch_per_query,
-// launch_per_query_bytes, launch_waves).  The wave reductions and the ordering rule are in rr_common.h.  Everything lives in an
-// unnamed namespace: each translation unit gets its own copy.
+// knob of the one-or-four-wave kernels (WaveKnob), the blocks knob of the grid-strided embedding kernels (BlocksKnob) and the one
+// launch of a "one workgroup per query" kernel (launch_per_query, launch_per_query_bytes, launch_waves).  The wave reductions and
+// the ordering rule are in rr_common.h.  Everything lives in an unnamed namespace: each translation unit gets its own copy.
 #pragma once
 #include <atomic>
 
@@ -56,6 +56,18 @@ struct WaveKnob {
     return RR_OK;
   }
   int pick(int max_len) const { return waves != 0 ? waves : (max_len <= RR_WAVE ? 1 : 4); }
+};
+
+// The workgroup count of a grid-strided entry-point family (kcenter, cluster, moments, resample): 0 = automatic by the file's own
+// grid rule, else pinned.  A process-wide word that every launch reads (relaxed); set() is for the bench tools and the tests.
+struct BlocksKnob {
+  std::atomic<int> blocks{0};
+  int get() const { return blocks.load(std::memory_order_relaxed); }
+  int set(int b, int max) {
+    RR_CHECK_ARG(b >= 0 && b <= max);
+    blocks.store(b, std::memory_order_relaxed);
+    return RR_OK;
+  }
 };
 
 // The launch of a "one workgroup per query" kernel: Q workgroups of `threads` threads, each with `lds` bytes of dynamic LDS.

@@ -12,36 +12,14 @@ Euclidean neighbors.knn / kcenter_greedy on whiten()-ed rows are the Mahalanobis
 There is no CPU path: tensors on the CPU raise."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _embed, _lib
 from ._lib import check, lib, ptr, stream
 
 MAX_H = _lib.RR_MOMENTS_MAX_H
-
-
-def _rows(t, name: str, who: str) -> torch.Tensor:
-    """a float32 GPU matrix whose rows are contiguous (any row pitch is taken as it is)"""
-    if not torch.is_tensor(t) or t.dim() != 2:
-        raise ValueError(f"{who}: `{name}` must be a matrix [rows, H] (got {type(t).__name__}"
-                         + (f" of shape {tuple(t.shape)})" if torch.is_tensor(t) else ")"))
-    if t.dtype != torch.float32:
-        raise ValueError(f"{who}: `{name}` must be float32 (got {t.dtype})")
-    if t.shape[1] < 1:
-        raise ValueError(f"{who}: `{name}` has rows of width 0")
-    if not t.is_cuda:
-        raise ValueError(f"{who}: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
-    t = t.detach()
-    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _pitch(x: torch.Tensor) -> int:
-    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
 
 
 def chunks(n_rows: int, width: int) -> int:
@@ -52,7 +30,7 @@ def chunks(n_rows: int, width: int) -> int:
 def scatter(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(mean f64 [H], scatter f64 [H, H], n_used int64 0-dim), all on the device and without a host synchronisation:
     rr_col_moments_f64 as include/reactranker_hip.h states it.  scatter = sum over the used rows of (x - mean)(x - mean)^T."""
-    x = _rows(x, "x", "moments")
+    x = _embed.rows(x, "x", "moments", min_width=1)
     N, H, dev = x.shape[0], x.shape[1], x.device
     if H > MAX_H:
         raise ValueError(f"moments: rows of width {H} (at most {MAX_H})")
@@ -62,12 +40,10 @@ def scatter(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     sc = torch.empty(H, H, dtype=torch.float64, device=dev)
     n_used = torch.empty((), dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        nbytes = C.c_size_t()
-        check(lib().rr_moments_workspace_bytes(N, H, C.byref(nbytes)), "rr_moments_workspace_bytes")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        src = x if N > 0 else torch.empty(1, dtype=torch.float32, device=dev)   # (the C entry wants a pointer even for no rows)
-        check(lib().rr_col_moments_f64(ptr(src), _pitch(x), N, H, ptr(mean), ptr(sc), ptr(n_used), ptr(ws),
-                                       C.c_size_t(nbytes.value), stream()), "rr_col_moments_f64")
+        ws, nbytes = _embed.scratch("rr_moments_workspace_bytes", dev, N, H)
+        src = x if N > 0 else _embed.placeholder(dev)
+        check(lib().rr_col_moments_f64(ptr(src), _embed.pitch(x), N, H, ptr(mean), ptr(sc), ptr(n_used), ptr(ws), nbytes,
+                                       stream()), "rr_col_moments_f64")
     return mean, sc, n_used
 
 
@@ -90,7 +66,7 @@ def center_project(x: torch.Tensor, center: Optional[torch.Tensor], W: torch.Ten
     (include/reactranker_hip.h states the chains).  center [H] float32 or None (zeros); W [H, R] float32, 1 <= R <= H.  With
     want_y False the product is never written.  Ordered on the current stream, no scratch."""
     who = "center_project"
-    x = _rows(x, "x", who)
+    x = _embed.rows(x, "x", who, min_width=1)
     N, H, dev = x.shape[0], x.shape[1], x.device
     if not torch.is_tensor(W) or W.dim() != 2 or W.dtype != torch.float32 or W.device != dev:
         raise ValueError(f"{who}: `W` must be a float32 matrix [H, R] on {dev}")
@@ -110,7 +86,7 @@ def center_project(x: torch.Tensor, center: Optional[torch.Tensor], W: torch.Ten
     sq = torch.empty(N, dtype=torch.float32, device=dev) if want_sq else None
     if N > 0:
         with torch.cuda.device(dev):
-            check(lib().rr_center_project_f32(ptr(x), _pitch(x), N, H, ptr(center), ptr(W), R, ptr(y), ptr(sq), stream()),
+            check(lib().rr_center_project_f32(ptr(x), _embed.pitch(x), N, H, ptr(center), ptr(W), R, ptr(y), ptr(sq), stream()),
                   "rr_center_project_f32")
     return y, sq
 
@@ -175,7 +151,7 @@ class EmbeddingGaussian:
         """moments(vectors, ddof=1), then torch.linalg.eigh of the covariance in float64 on the CPU (eigen_model says what
         happens to the eigenvalues and signs).  Directions whose eigenvalue is at most eig_floor (default H 2^-24, the f32 noise
         floor of the inputs) times the largest are dropped from the whitening; rank = r keeps at most the top r."""
-        x = _rows(vectors, "vectors", "EmbeddingGaussian.fit")
+        x = _embed.rows(vectors, "vectors", "EmbeddingGaussian.fit", min_width=1)
         mean, cov, n = moments(x, ddof=1)
         if n < 2:
             raise ValueError(f"EmbeddingGaussian.fit: {n} usable rows (at least 2 needed)")
@@ -187,7 +163,7 @@ class EmbeddingGaussian:
         return cls.fit(bank.vectors, **kw)
 
     def _check(self, vectors, who):
-        x = _rows(vectors, "vectors", who)
+        x = _embed.rows(vectors, "vectors", who, min_width=1)
         if x.shape[1] != self.center_.numel():
             raise ValueError(f"{who}: vectors of width {x.shape[1]}, the model was fitted on width {self.center_.numel()}")
         if x.device != self.center_.device:

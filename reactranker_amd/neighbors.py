@@ -19,13 +19,14 @@ the [M, N] distance matrix is never written.  On top of it:
 There is no CPU path: tensors on the CPU raise."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _embed, _lib
 from . import eval as E
 from . import uncertainty as U
 from ._lib import check, lib, ptr, stream
@@ -46,45 +47,16 @@ def geometry() -> Tuple[int, int, int]:
     return a.value, b.value, c.value
 
 
-def _matrix(t, name: str) -> None:
-    if not torch.is_tensor(t) or t.dim() != 2:
-        raise ValueError(f"knn: `{name}` must be a matrix [rows, H] (got {type(t).__name__}"
-                         + (f" of shape {tuple(t.shape)})" if torch.is_tensor(t) else ")"))
-    if t.dtype != torch.float32:
-        raise ValueError(f"knn: `{name}` must be float32 (got {t.dtype})")
-
-
-def _rows(t, name: str) -> torch.Tensor:
-    """a float32 GPU matrix whose rows are contiguous (any row pitch is taken as it is)"""
-    _matrix(t, name)
-    if not t.is_cuda:
-        raise ValueError(f"knn: `{name}` must live on the GPU (got {t.device}); there is no CPU path")
-    t = t.detach()
-    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
-
-
-def _group(g, rows: int, dev, name: str) -> torch.Tensor:
-    g = torch.as_tensor(g)
-    if g.numel() != rows:
-        raise ValueError(f"knn: `{name}` has {g.numel()} entries for {rows} rows")
-    if g.is_floating_point():
-        raise ValueError(f"knn: `{name}` must hold integers")
-    return g.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-
-
 def row_sqnorm(x: torch.Tensor) -> torch.Tensor:
     """sum_h x[r, h]^2 per row by the library's fixed f32 chain (rr_row_sqnorm_f32): what knn() takes as `bank_sqnorm`"""
-    x = _rows(x, "x")
+    x = _embed.rows(x, "x", "row_sqnorm")
     if x.shape[1] < 1:
         raise ValueError("row_sqnorm: rows of width 0")
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     if x.shape[0] == 0:
         return out
     with torch.cuda.device(x.device):
-        check(lib().rr_row_sqnorm_f32(ptr(x), x.stride(0) if x.shape[0] > 1 else x.shape[1], x.shape[0], x.shape[1], ptr(out),
-                                      stream()), "rr_row_sqnorm_f32")
+        check(lib().rr_row_sqnorm_f32(ptr(x), _embed.pitch(x), x.shape[0], x.shape[1], ptr(out), stream()), "rr_row_sqnorm_f32")
     return out
 
 
@@ -108,8 +80,8 @@ def knn(queries: torch.Tensor, bank: torch.Tensor, k: int, q_group=None, b_group
     without the other."""
     if metric not in METRICS:
         raise ValueError(f"knn: metric must be one of {METRICS} (got {metric!r})")
-    _matrix(queries, "queries")
-    _matrix(bank, "bank")
+    _embed.matrix(queries, "queries", "knn")
+    _embed.matrix(bank, "bank", "knn")
     kk = int(k)
     if kk != k or not (1 <= kk <= MAX_K):
         raise ValueError(f"knn: k must be an integer in [1, {MAX_K}] (got {k!r})")
@@ -117,37 +89,31 @@ def knn(queries: torch.Tensor, bank: torch.Tensor, k: int, q_group=None, b_group
         raise ValueError(f"knn: queries have width {queries.shape[1]}, the bank {bank.shape[1]} (equal and >= 1 required)")
     if (q_group is None) != (b_group is None):
         raise ValueError("knn: q_group and b_group go together (both or neither)")
-    q, b = _rows(queries, "queries"), _rows(bank, "bank")
+    q, b = _embed.rows(queries, "queries", "knn"), _embed.rows(bank, "bank", "knn")
     if q.device != b.device:
         raise ValueError(f"knn: queries on {q.device}, bank on {b.device}")
     M, N, H = q.shape[0], b.shape[0], q.shape[1]
     dev = q.device
     qg = bg = None
     if q_group is not None:
-        qg, bg = _group(q_group, M, dev, "q_group"), _group(b_group, N, dev, "b_group")
+        qg, bg = _embed.group(q_group, M, dev, "q_group", "knn"), _embed.group(b_group, N, dev, "b_group", "knn")
     bn = None
     if metric == "cosine":
         if bank_sqnorm is not None:
             raise ValueError("knn: bank_sqnorm belongs to metric 'sqeuclidean' (cosine normalises the rows first)")
         q, b = _unit_rows(q), _unit_rows(b)
     elif bank_sqnorm is not None:
-        bn = torch.as_tensor(bank_sqnorm)
-        if not bn.is_cuda or bn.dtype != torch.float32 or bn.numel() != N:
-            raise ValueError(f"knn: bank_sqnorm must be {N} float32 values on the GPU")
-        bn = bn.reshape(-1).contiguous()
+        bn = _embed.per_row(bank_sqnorm, N, None, "bank_sqnorm", "knn")
     dist = torch.empty(M, kk, dtype=torch.float32, device=dev)
     idx = torch.empty(M, kk, dtype=torch.int32, device=dev)
     if M == 0:
         return dist, idx.to(torch.int64)
     if N == 0:                                             # (the C entry wants a bank pointer even when it holds no row)
-        b = torch.zeros(1, H, dtype=torch.float32, device=dev)
-        bg = None if bg is None else torch.full((1,), -1, dtype=torch.int32, device=dev)
+        b, bg = _embed.empty_bank(H, dev, bg is not None)
     with torch.cuda.device(dev):
-        nbytes = C.c_size_t()
-        check(lib().rr_knn_workspace_bytes(M, N, kk, C.byref(nbytes)), "rr_knn_workspace_bytes")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        check(lib().rr_knn_f32(ptr(q), q.stride(0) if M > 1 else H, M, ptr(b), b.stride(0) if N > 1 else H, N, H, kk, ptr(qg),
-                               ptr(bg), ptr(bn), ptr(dist), ptr(idx), ptr(ws), C.c_size_t(nbytes.value), stream()), "rr_knn_f32")
+        ws, nbytes = _embed.scratch("rr_knn_workspace_bytes", dev, M, N, kk)
+        check(lib().rr_knn_f32(ptr(q), _embed.pitch(q), M, ptr(b), _embed.pitch(b), N, H, kk, ptr(qg), ptr(bg),
+                               ptr(bn), ptr(dist), ptr(idx), ptr(ws), nbytes, stream()), "rr_knn_f32")
     if metric == "cosine":
         dist = dist * 0.5
     return dist, idx.to(torch.int64)
@@ -169,27 +135,35 @@ def _forward_with_vectors(model, r_batch, p_batch, add_features, gpu):
     return out, model.diff_encoder(p_h - r_h, p_batch, gpu, features_batch=add_features).clone()
 
 
+@contextlib.contextmanager
+def _eval_keeping_vectors(model):
+    """eval mode, no_grad and StepPlan.keep_last for the forwards inside; model.training, StepPlan.keep_last and StepPlan.last
+    are left as found"""
+    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
+    try:
+        model.eval()
+        StepPlan.keep_last = True
+        with torch.no_grad():
+            yield
+    finally:
+        StepPlan.keep_last, StepPlan.last = old_keep, old_last
+        model.train(was_training)
+
+
 def reaction_vectors(model, batches: Iterable, gpu, include_features: bool = False) -> torch.Tensor:
     """The model's reaction vector of every candidate of `batches` ((r, p, scope, targets, add_features) tuples, the form
     the evaluators take; batches without queries are skipped): one eval-mode forward per batch under no_grad (on the step-plan
     path; _forward_with_vectors says what happens without one), the first H columns of RR_SAVED_VECS (all of them - the additional features behind the H readout columns - with
     include_features) copied out of the step's workspace before another step can reuse it.  [sum M, H] float32 on the device.
     model.training, StepPlan.keep_last and StepPlan.last are left as found."""
-    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
     H = int(model.encoder.hidden_size)
     out = []
-    try:
-        model.eval()
-        StepPlan.keep_last = True
-        with torch.no_grad():
-            for r_batch, p_batch, scope, _targets, add_features in batches:
-                if len(scope) == 0:
-                    continue
-                _, v = _forward_with_vectors(model, r_batch, p_batch, add_features, gpu)
-                out.append(v if include_features else v[:, :H].contiguous())
-    finally:
-        StepPlan.keep_last, StepPlan.last = old_keep, old_last
-        model.train(was_training)
+    with _eval_keeping_vectors(model):
+        for r_batch, p_batch, scope, _targets, add_features in batches:
+            if len(scope) == 0:
+                continue
+            _, v = _forward_with_vectors(model, r_batch, p_batch, add_features, gpu)
+            out.append(v if include_features else v[:, :H].contiguous())
     if not out:
         dev = torch.device("cuda", torch.cuda.current_device() if gpu is None else gpu)
         return torch.zeros(0, H, dtype=torch.float32, device=dev)
@@ -202,12 +176,12 @@ class ReactionBank:
     OTHER queries" and leave-one-query-out of the bank against itself are one knn call)."""
 
     def __init__(self, vectors: torch.Tensor, targets, group, sqnorm: Optional[torch.Tensor] = None):
-        self.vectors = _rows(vectors, "vectors").contiguous()
+        self.vectors = _embed.rows(vectors, "vectors", "ReactionBank").contiguous()
         dev, N = self.vectors.device, self.vectors.shape[0]
         self.targets = torch.as_tensor(targets).reshape(-1).to(device=dev, dtype=torch.float32)
         if self.targets.numel() != N:
             raise ValueError(f"ReactionBank: {self.targets.numel()} targets for {N} rows")
-        self.group = _group(group, N, dev, "group")
+        self.group = _embed.group(group, N, dev, "group", "ReactionBank")
         self.sqnorm = row_sqnorm(self.vectors) if sqnorm is None else sqnorm.to(device=dev, dtype=torch.float32).reshape(-1)
         if self.sqnorm.numel() != N:
             raise ValueError(f"ReactionBank: {self.sqnorm.numel()} norms for {N} rows")
@@ -283,7 +257,6 @@ def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dic
         raise ValueError("no queries to evaluate")
     model = model.cuda(gpu)
     load_checkpoint(path_checkpoints, model, map_location="cpu")
-    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
     H = int(model.encoder.hidden_size)
     if bank.vectors.shape[1] != H:
         raise ValueError(f"the bank holds vectors of width {bank.vectors.shape[1]}, the model's are {H}")
@@ -291,20 +264,14 @@ def evaluate_applicability(model, bank: ReactionBank, test_batches: Sequence[dic
         from .latent_gaussian import EmbeddingGaussian
         gaussian = EmbeddingGaussian.from_bank(bank)
     preds, dists, stats = [], [], []
-    try:
-        model.eval()
-        StepPlan.keep_last = True
-        with torch.no_grad():
-            for r_batch, p_batch, scope, targets, add in batches:
-                out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
-                vec = vec[:, :H]
-                pred = U._first_column(out)
-                preds.append(pred)
-                dists.append(latent_distance(bank, vec, k) if method == "knn" else gaussian.mahalanobis(vec).sqrt())
-                stats.append(E.ranking_stats(pred, scope, targets, gpu, 0.25)[0])
-    finally:
-        StepPlan.keep_last, StepPlan.last = old_keep, old_last
-        model.train(was_training)
+    with _eval_keeping_vectors(model):
+        for r_batch, p_batch, scope, targets, add in batches:
+            out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
+            vec = vec[:, :H]
+            pred = U._first_column(out)
+            preds.append(pred)
+            dists.append(latent_distance(bank, vec, k) if method == "knn" else gaussian.mahalanobis(vec).sqrt())
+            stats.append(E.ranking_stats(pred, scope, targets, gpu, 0.25)[0])
     pred, distance = torch.cat(preds), torch.cat(dists)
     targets = torch.cat([b[3].reshape(-1) for b in batches]).to(pred.device)
     scope = [int(c) for b in batches for c in b[2]]
@@ -330,10 +297,7 @@ def split_overlap(bank: ReactionBank, vectors: torch.Tensor, rel_tol: float = 1e
 
 # ------------------------------------------------------------------------------------------------ selection
 def _per_row(t, rows: int, dev, name: str) -> torch.Tensor:
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev or t.numel() != rows:
-        got = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"kcenter_greedy: `{name}` must be {rows} float32 values on {dev} (got {got})")
-    return t.detach().reshape(-1).contiguous()
+    return _embed.per_row(t, rows, dev, name, "kcenter_greedy")
 
 
 def kcenter_greedy(vectors: torch.Tensor, n: int, init_dist=None, weight=None) -> dict:
@@ -354,13 +318,13 @@ def kcenter_greedy(vectors: torch.Tensor, n: int, init_dist=None, weight=None) -
     stream, and the call is ordered on that stream: n + 1 launches, no host synchronisation in between.
     ValueError - before any launch - for CPU tensors, width 0, n outside [0, 65536], or an init_dist / weight that is not
     P float32 values on the same device."""
-    _matrix(vectors, "vectors")
+    _embed.matrix(vectors, "vectors", "kcenter_greedy")
     nn = int(n)
     if nn != n or not (0 <= nn <= MAX_PICKS):
         raise ValueError(f"kcenter_greedy: n must be an integer in [0, {MAX_PICKS}] (got {n!r})")
     if vectors.shape[1] < 1:
         raise ValueError("kcenter_greedy: rows of width 0")
-    x = _rows(vectors, "vectors")
+    x = _embed.rows(vectors, "vectors", "kcenter_greedy")
     P, H, dev = x.shape[0], x.shape[1], x.device
     if P > 2 ** 31 - 1:
         raise ValueError(f"kcenter_greedy: {P} rows (at most 2^31 - 1)")
@@ -372,14 +336,12 @@ def kcenter_greedy(vectors: torch.Tensor, n: int, init_dist=None, weight=None) -
     assign = torch.empty(P, dtype=torch.int32, device=dev)
     if P > 0 or nn > 0:
         with torch.cuda.device(dev):
-            nbytes = C.c_size_t()
-            check(lib().rr_kcenter_workspace_bytes(P, nn, C.byref(nbytes)), "rr_kcenter_workspace_bytes")
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            one = torch.empty(1, dtype=torch.float32, device=dev)         # (the C entry wants non-null pointers for empty arrays)
-            check(lib().rr_kcenter_f32(ptr(x) if P > 0 else ptr(one), x.stride(0) if P > 1 else H, P, H, nn, ptr(init), ptr(w),
+            ws, nbytes = _embed.scratch("rr_kcenter_workspace_bytes", dev, P, nn)
+            one = _embed.placeholder(dev)
+            check(lib().rr_kcenter_f32(ptr(x) if P > 0 else ptr(one), _embed.pitch(x), P, H, nn, ptr(init), ptr(w),
                                        ptr(picks) if nn > 0 else ptr(one), ptr(gain) if nn > 0 else ptr(one),
                                        ptr(min_dist) if P > 0 else ptr(one), ptr(assign) if P > 0 else ptr(one), ptr(ws),
-                                       C.c_size_t(nbytes.value), stream()), "rr_kcenter_f32")
+                                       nbytes, stream()), "rr_kcenter_f32")
     return dict(picks=picks.to(torch.int64), gain=gain, min_dist=min_dist, assign=assign.to(torch.int64))
 
 
@@ -410,21 +372,14 @@ def acquire(model, bank: ReactionBank, pool_batches: Sequence, n: int, gpu, weig
     H = int(model.encoder.hidden_size)
     if bank.vectors.shape[1] != H:
         raise ValueError(f"the bank holds vectors of width {bank.vectors.shape[1]}, the model's are {H}")
-    was_training, old_keep, old_last = model.training, StepPlan.keep_last, StepPlan.last
     vecs, stds = [], []
-    try:
-        model.eval()
-        StepPlan.keep_last = True
-        with torch.no_grad():
-            for r_batch, p_batch, scope, _targets, add in batches:
-                out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
-                vecs.append(vec[:, :H].contiguous())
-                if kind is not None:
-                    zeros = torch.zeros(vec.shape[0], dtype=torch.float32)
-                    stds.append(U.analytic_stats(out, scope, zeros, kind, gpu=gpu)["std"])
-    finally:
-        StepPlan.keep_last, StepPlan.last = old_keep, old_last
-        model.train(was_training)
+    with _eval_keeping_vectors(model):
+        for r_batch, p_batch, scope, _targets, add in batches:
+            out, vec = _forward_with_vectors(model, r_batch, p_batch, add, gpu)
+            vecs.append(vec[:, :H].contiguous())
+            if kind is not None:
+                zeros = torch.zeros(vec.shape[0], dtype=torch.float32)
+                stds.append(U.analytic_stats(out, scope, zeros, kind, gpu=gpu)["std"])
     dev = bank.vectors.device
     vec = torch.cat(vecs, 0) if vecs else torch.zeros(0, H, dtype=torch.float32, device=dev)
     if kind is not None:

@@ -287,3 +287,11 @@ def test_cluster_kfold_and_degenerate_inputs():
     for k in (0, -1, 2.5):
         with pytest.raises(ValueError, match="k must be"):
             K.cluster_kfold(giant, k)
+
+
+def test_a_cpu_tensor_error_names_the_function_that_was_called():
+    x, y = torch.zeros(7, 5), torch.zeros(3, 5)
+    with pytest.raises(ValueError, match=r"^sphere_exclusion: .*GPU"):
+        K.sphere_exclusion(x, 1.0)
+    with pytest.raises(ValueError, match=r"^radius_count: .*GPU"):
+        K.radius_count(y, x, 1.0)

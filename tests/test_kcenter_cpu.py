@@ -168,3 +168,12 @@ def test_python_argument_checks_raise_before_any_launch():
         with pytest.raises(ValueError, match="weight"):
             N._per_row(bad, 7, meta.device, "weight")
     assert N._per_row(torch.zeros(7, device="meta"), 7, meta.device, "weight").shape == (7,)
+
+
+def test_a_cpu_tensor_error_names_the_function_that_was_called():
+    from reactranker_amd import neighbors as N
+    x = torch.zeros(7, 5)
+    with pytest.raises(ValueError, match=r"^kcenter_greedy: .*GPU"):
+        N.kcenter_greedy(x, 2)
+    with pytest.raises(ValueError, match=r"^row_sqnorm: .*GPU"):
+        N.row_sqnorm(x)

@@ -236,3 +236,11 @@ def test_python_argument_checks_raise_before_any_launch():
         Nb.evaluate_applicability(None, None, [], "ck.pt", 0, method="euclid")
     with pytest.raises(ValueError, match="gaussian"):
         Nb.evaluate_applicability(None, None, [], "ck.pt", 0, gaussian=object())
+
+
+def test_a_cpu_tensor_error_names_the_function_that_was_called():
+    x = torch.zeros(7, 5)
+    with pytest.raises(ValueError, match=r"^moments: .*GPU"):
+        G.moments(x)
+    with pytest.raises(ValueError, match=r"^center_project: .*GPU"):
+        G.center_project(x, None, torch.zeros(5, 2))
