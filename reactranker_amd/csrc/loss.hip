@@ -8,9 +8,11 @@
 // list lengths never wait on each other.  Per-query partials are finished by a fixed-order
 // second kernel: no float atomics, results are run-to-run identical.
 //
-// The kernels of the list losses are shells: stage the list, build its term (loss_list.h, where each loss formula is
-// written once - the composite step of task_loss.hip builds the same terms), write the partial with this entry point's
-// normaliser and / or hand the term an emit that stores the gradient, finish.
+// The nine list losses share ONE kernel shell, list_loss_kernel<K>: stage the list, build its term (loss_list.h, where each
+// loss formula is written once with its normalisers - the composite step of task_loss.hip builds the same terms), write the
+// partial and / or hand the term an emit that stores the gradient, finish; and one host body, list_launch<K>.  RankNet keeps
+// its own pair loops (ranknet_fwd_kernel, ranknet_bwd_kernel).  The four pointwise losses share pointwise_kernel<K, BWD> over
+// point_row<K> (loss_list.h), and every workgroup-wide sum is block_sum (wave_util.h).
 //
 // The reference evaluates these losses as a Python loop of ~10 tiny ATen ops per query
 // (train/loss.py:86-97, 338-347, 504-554; train/train_pairwise.py:99-137).
@@ -20,122 +22,76 @@ std::atomic<long long> rr_lds_opt_in_count{0};
 
 namespace {
 
-// ---------------------------------------------------------------- fused loss + gradient launches ("step" entry points)
-// mode 2 of the three kernels below writes the loss AND d loss / d score for an upstream gradient of one (what
-// `loss.backward()` feeds a loss that is the root of the graph; gloss == nullptr stands for it): the reference's trainer
-// step (train_listwise.py:287-288) then needs no second loss kernel, no separate reduction launch and no host-created
-// gradient.  Same operations in the same order as modes 0 (forward: partial) and 1 (backward: the gradient), and the
-// partials are summed by the last-arriving workgroup (finish_last, loss_list.h), so the bits are those of the two-kernel path.
-__device__ inline void finish_step(const float* partial, int n, float scale, float* loss, unsigned int* counter, int lane) {
-  float sum[1];
-  if (finish_last(partial, n, counter, lane, sum)) loss[0] = sum[0] * scale;
-}
+// ---------------------------------------------------------------- the shell of the nine list losses: ListMLE, ListNet,
+// UC-Listwise, MLEDis, ListNet-Gauss, ListNet-lognorm, ListNet-evidential, ListNet-uq, Dirichlet-uq (ListLoss<K>, loss_list.h)
+struct VarIn {            // up to three per-candidate inputs, each read at x[k][row * st[k]]
+  const float* x[3];
+  int64_t st[3];
+};
 
-// ---------------------------------------------------------------- ListMLE
-__global__ void __launch_bounds__(RR_WAVE) listmle_kernel(const float* __restrict__ score, int64_t sstride,
-                                                          const float* __restrict__ targets,
-                                                          const int32_t* __restrict__ seg_off, int L, int Q, int bwd,
-                                                          float* __restrict__ partial, const float* __restrict__ gloss,
-                                                          float* __restrict__ dscore, int64_t dstride, float scale,
-                                                          float* __restrict__ loss,
-                                                          unsigned int* __restrict__ counter) {
+struct VarOut {           // their gradients, written at d[k][row * st]
+  float* d[3];
+  int64_t st;
+};
+
+// kForward: partial[q] = the query's loss.  kBackward: the gradients of the finished loss, times *gloss.  kStep: both in one
+// launch - the loss AND d loss / d input for an upstream gradient of one (what `loss.backward()` feeds a loss that is the
+// root of the graph; gloss == nullptr stands for it): the reference's trainer step (train_listwise.py:287-288) then needs
+// no second loss kernel, no separate reduction launch and no host-created gradient.  Same operations in the same order as
+// the other two modes, and the partials are summed by the last-arriving workgroup (finish_last, loss_list.h), so the bits
+// are those of the two-kernel path.
+enum ListMode : int { kForward = 0, kBackward = 1, kStep = 2 };
+
+struct ListArgs {
+  VarIn in;
+  const float* targets;
+  const int32_t* seg_off;
+  int L, Q;
+  float coef, inv_total;  // the penalty coefficient of the UQ losses; ListNet's 1 / candidates of the window
+  int mode;
+  float* partial;
+  const float* gloss;
+  VarOut out;
+  float scale;            // kStep: loss = scale * the sum of the partials
+  float* loss;
+  unsigned int* counter;
+};
+
+template <int K>
+__global__ void __launch_bounds__(RR_WAVE) list_loss_kernel(ListArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
+  using Loss = ListLoss<K>;
   const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) {
-    if (bwd != 1 && lane == 0) partial[q] = 0.f;
+  const int off = a.seg_off[q], C = a.seg_off[q + 1] - off;
+  if (C <= 0) {                                                     // an empty query adds nothing (still counted in Q)
+    if (a.mode != kBackward && lane == 0) a.partial[q] = 0.f;
   } else {
-    const ListView v = carve(sm, L);
+    const ListView v = carve(sm, a.L);
     for (int i = lane; i < C; i += RR_WAVE) {
-      v.s[i] = score[static_cast<int64_t>(off + i) * sstride];
-      v.t[i] = targets[off + i];
+      const int64_t r = off + i;
+#pragma unroll
+      for (int k = 0; k < Loss::kInputs; ++k) v.col(k)[i] = a.in.x[k][r * a.in.st[k]];
+      v.t[i] = a.targets[r];
     }
     wave_sync();
-    const ListMleTerm term(v, C, lane);
-    if (bwd != 1) {
-      const float acc = term.forward();
-      if (lane == 0) partial[q] = acc / static_cast<float>(C);      // torch.mean, loss.py:94
+    const ListNorm n{C, a.Q, a.inv_total, a.coef};
+    const auto term = Loss::term(v, n, lane);
+    if (a.mode != kBackward) {
+      const auto acc = term.forward();
+      if (lane == 0) a.partial[q] = Loss::partial(acc, n);
     }
-    if (bwd != 0) {
-      const float g = (gloss ? gloss[0] : 1.0f) / (static_cast<float>(C) * static_cast<float>(Q));
-      term.gradient(g, [&](int i, float d) { dscore[static_cast<int64_t>(off + i) * dstride] = d; });
-    }
-  }
-  if (bwd == 2) finish_step(partial, Q, scale, loss, counter, lane);
-}
-
-// ---------------------------------------------------------------- ListNet
-__global__ void __launch_bounds__(RR_WAVE) listnet_kernel(const float* __restrict__ score, int64_t sstride,
-                                                          const float* __restrict__ targets,
-                                                          const int32_t* __restrict__ seg_off, int L, int bwd,
-                                                          float* __restrict__ partial, const float* __restrict__ gloss,
-                                                          float inv_total, float* __restrict__ dscore,
-                                                          int64_t dstride, float* __restrict__ loss,
-                                                          unsigned int* __restrict__ counter) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) {
-    if (bwd != 1 && lane == 0) partial[q] = 0.f;
-  } else {
-    float* s = sm;
-    float* t = sm + L;
-    for (int i = lane; i < C; i += RR_WAVE) {
-      s[i] = score[static_cast<int64_t>(off + i) * sstride];
-      t[i] = targets[off + i];
-    }
-    wave_sync();
-    const ListNetTerm term(s, t, C, lane);
-    if (bwd != 1) {
-      const float acc = term.forward();
-      if (lane == 0) partial[q] = acc;                              // ONE mean over all candidates (loss.py:347): inv_total
-    }
-    if (bwd != 0) {
-      const float g = (gloss ? gloss[0] : 1.0f) * inv_total;
-      term.gradient(g, [&](int i, float d) { dscore[static_cast<int64_t>(off + i) * dstride] = d; });
-    }
-  }
-  if (bwd == 2) finish_step(partial, gridDim.x, inv_total, loss, counter, lane);
-}
-
-// ---------------------------------------------------------------- evidential UC-Listwise
-__global__ void __launch_bounds__(RR_WAVE) evidential_kernel(const float* __restrict__ mu, const float* __restrict__ var,
-                                                             int64_t stride, const float* __restrict__ targets,
-                                                             const int32_t* __restrict__ seg_off, int L, int Q, int bwd,
-                                                             float* __restrict__ partial,
-                                                             const float* __restrict__ gloss, float* __restrict__ dmu,
-                                                             float* __restrict__ dvar, int64_t dstride,
-                                                             float* __restrict__ loss,
-                                                             unsigned int* __restrict__ counter) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) {
-    if (bwd != 1 && lane == 0) partial[q] = 0.f;
-  } else {
-    float* s = sm;
-    float* t = sm + L;
-    float* vv = sm + 2 * L;
-    for (int i = lane; i < C; i += RR_WAVE) {
-      s[i] = mu[static_cast<int64_t>(off + i) * stride];
-      vv[i] = var[static_cast<int64_t>(off + i) * stride];
-      t[i] = targets[off + i];
-    }
-    wave_sync();
-    const UcListwiseTerm term(s, vv, t, C, lane);
-    if (bwd != 1) {
-      const float acc = term.forward();
-      if (lane == 0) partial[q] = acc / static_cast<float>(C);
-    }
-    if (bwd != 0) {
-      const float g = (gloss ? gloss[0] : 1.0f) / (static_cast<float>(C) * static_cast<float>(Q));
-      term.gradient(g, [&](int i, float gm, float gv) {
-        dmu[static_cast<int64_t>(off + i) * dstride] = gm;
-        dvar[static_cast<int64_t>(off + i) * dstride] = gv;
+    if (a.mode != kForward) {
+      const float g = Loss::grad_scale(a.gloss ? a.gloss[0] : 1.0f, n);
+      term.gradient(g, [&](int i, auto... gs) {
+        int k = 0;
+        ((a.out.d[k++][static_cast<int64_t>(off + i) * a.out.st] = gs), ...);
       });
     }
   }
-  if (bwd == 2) finish_step(partial, gridDim.x, 1.0f / static_cast<float>(Q), loss, counter, lane);
+  if (a.mode == kStep) {
+    float sum[1];
+    if (finish_last(a.partial, a.Q, a.counter, lane, sum)) a.loss[0] = sum[0] * a.scale;
+  }
 }
 
 // ---------------------------------------------------------------- RankNet
@@ -155,11 +111,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_fwd_kernel(const float* __res
   }
   float* s = sm;
   float* t = sm + L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
+  stage_list(s, t, score, sstride, targets, off, C, lane);
   // The pair costs are float32; their sum is kept in double: a lane adds C * C / 64 of them (a million at C = 8192), and a
   // float32 running sum of ~1e6 rounds every further cost of ~1 to 1/16 - 6.5e-4 of the loss at 8192, 1e-4 at 5462.
   double acc = 0.0;
@@ -198,11 +150,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_bwd_kernel(const float* __res
   float* s = sm;
   float* t = sm + L;
   float* lamv = sm + 2 * L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
+  stage_list(s, t, score, sstride, targets, off, C, lane);
   int npos = 0;
   for (int i = lane; i < C; i += RR_WAVE) {
     const float ti = t[i], si = s[i];
@@ -228,56 +176,37 @@ __global__ void __launch_bounds__(RR_WAVE) ranknet_bwd_kernel(const float* __res
 // ---------------------------------------------------------------- final fixed-order reductions
 __global__ void __launch_bounds__(256) reduce_scale_kernel(const float* __restrict__ partial, int64_t n, int64_t step,
                                                            float scale, float* __restrict__ out) {
-  __shared__ float red[256];
   float acc = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += 256) acc += partial[i * step];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] * scale;
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) out[0] = acc * scale;
 }
 
-// ---------------------------------------------------------------- pointwise losses (rows: point_row, loss_list.h)
-__global__ void __launch_bounds__(256) pointwise_fwd_kernel(const float* __restrict__ mean, const float* __restrict__ var,
-                                                            int64_t stride, const float* __restrict__ targets,
-                                                            int64_t n, int gauss, float* __restrict__ partial) {
-  __shared__ float red[256];
-  float acc = 0.f;
+// ---------------------------------------------------------------- pointwise losses: MSE, Gaussian NLL, Lognorm, exp-MSE
+// (rows: point_row<K>, loss_list.h).  Grid-stride; the forward leaves one partial per workgroup, the backward scales the
+// rows' gradients by *gloss / n
+template <int K, bool BWD>
+__global__ void __launch_bounds__(256) pointwise_kernel(const float* __restrict__ x, const float* __restrict__ var,
+                                                        int64_t stride, const float* __restrict__ targets, int64_t n,
+                                                        float* __restrict__ partial, const float* __restrict__ gloss,
+                                                        float* __restrict__ dx, float* __restrict__ dvar, int64_t dstride) {
+  float g = 0.f, acc = 0.f;
+  if constexpr (BWD) g = gloss[0] / static_cast<float>(n);
   const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    if (gauss) {
-      acc += point_row<true>(mean[i * stride], targets[i], var[i * stride], 0.f).value;
+    float v = 0.f;
+    if constexpr (point_has_var(K)) v = var[i * stride];
+    const PointRow r = point_row<K>(x[i * stride], targets[i], v, g);
+    if constexpr (BWD) {
+      dx[i * dstride] = r.dmean;
+      if constexpr (point_has_var(K)) dvar[i * dstride] = r.dvar;
     } else {
-      acc += point_row<false>(mean[i * stride], targets[i], 0.f, 0.f).value;
+      acc += r.value;
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ void __launch_bounds__(256) pointwise_bwd_kernel(const float* __restrict__ mean, const float* __restrict__ var,
-                                                            int64_t stride, const float* __restrict__ targets,
-                                                            int64_t n, int gauss, const float* __restrict__ gloss,
-                                                            float* __restrict__ dmean, float* __restrict__ dvar,
-                                                            int64_t dstride) {
-  const float g = gloss[0] / static_cast<float>(n);
-  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    if (gauss) {
-      const PointRow r = point_row<true>(mean[i * stride], targets[i], var[i * stride], g);
-      dmean[i * dstride] = r.dmean;
-      dvar[i * dstride] = r.dvar;
-    } else {
-      dmean[i * dstride] = point_row<false>(mean[i * stride], targets[i], 0.f, g).dmean;
-    }
+  if constexpr (!BWD) {
+    acc = block_sum(acc);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
   }
 }
 
@@ -302,11 +231,7 @@ __global__ void __launch_bounds__(RR_WAVE) ranking_metrics_kernel(const float* _
   uint16_t* to = po + L;                                     // target order
   uint16_t* pr = to + L;                                     // predicted rank of every candidate (inverse of po)
   uint16_t* tr = pr + L;                                     // target rank of every candidate (inverse of to)
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
+  stage_list(s, t, score, sstride, targets, off, C, lane);
   for (int i = lane; i < C; i += RR_WAVE) {                   // stable descending ranks of both keys
     const float si = s[i], ti = t[i];
     int rp = 0, rt = 0;
@@ -436,73 +361,6 @@ __global__ void __launch_bounds__(RR_WAVE) lce_bwd_kernel(const float* __restric
   lce_backward(x, fd, cs, n, lane, [&](int i, float w) { gx[i] = gy[i] * w; });
 }
 
-// ---------------------------------------------------------------- listwise variants: MLEDisLoss, Listnet_For_Gauss,
-// Listnetlognorm, Listnet_For_evidential, Listnet_with_uq, Dirichlet_uq (their terms: loss_list.h)
-enum LossVariant : int { kMleDis = 0, kListnetGauss = 1, kListnetLognorm = 2, kListnetEvid = 3, kListnetUq = 4, kDirichletUq = 5 };
-
-struct VarIn {            // up to three per-candidate inputs, each read at x[k][row * st[k]]
-  const float* x[3];
-  int64_t st[3];
-};
-
-struct VarOut {           // their gradients, written at d[k][row * st]
-  float* d[3];
-  int64_t st;
-};
-
-constexpr int variant_inputs(int V) { return V == kListnetEvid ? 3 : (V == kListnetUq || V == kDirichletUq) ? 1 : 2; }
-// staged floats per candidate: x0, t, x1, x2 (ListNet-evidential) or perm (MLEDis), scan (MLEDis)
-constexpr int variant_lds(int V) { return V == kMleDis ? 5 : V == kListnetEvid ? 4 : (V == kListnetUq || V == kDirichletUq) ? 2 : 3; }
-
-template <int V>
-__global__ void __launch_bounds__(RR_WAVE) listwise_variant_kernel(VarIn in, const float* __restrict__ targets,
-                                                                   const int32_t* __restrict__ seg_off, int L, int Q, float coef,
-                                                                   int bwd, float* __restrict__ partial,
-                                                                   const float* __restrict__ gloss, VarOut out) {
-  // bwd: 0 = forward (partial[q] = the query's loss), 1 = backward (gradients of sum_q partial[q] / Q, times *gloss)
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  constexpr int NIN = variant_inputs(V);
-  const int q = blockIdx.x, lane = threadIdx.x;
-  const int off = seg_off[q], C = seg_off[q + 1] - off;
-  if (C <= 0) {                                                     // an empty query adds nothing (still counted in Q)
-    if (!bwd && lane == 0) partial[q] = 0.f;
-    return;
-  }
-  float* x0 = sm;
-  float* t = sm + L;
-  float* x1 = sm + 2 * L;
-  float* x2 = sm + 3 * L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    const int64_t r = off + i;
-    x0[i] = in.x[0][r * in.st[0]];
-    if (NIN > 1) x1[i] = in.x[1][r * in.st[1]];
-    if (NIN > 2) x2[i] = in.x[2][r * in.st[2]];
-    t[i] = targets[r];
-  }
-  wave_sync();
-  const float invC = 1.0f / static_cast<float>(C);
-  const float g = bwd ? gloss[0] / (static_cast<float>(C) * static_cast<float>(Q)) : 0.f;
-  auto run = [&](const auto& term) {
-    if (!bwd) {
-      const auto acc = term.forward();
-      if (lane != 0) return;
-      if constexpr (V == kListnetUq || V == kDirichletUq) partial[q] = acc.acc * invC + coef * (acc.pen * invC);
-      else if constexpr (V == kListnetEvid) partial[q] = -(acc * invC);
-      else partial[q] = acc * invC;
-    } else {
-      term.gradient(g, [&](int i, auto... gs) {
-        int k = 0;
-        ((out.d[k++][static_cast<int64_t>(off + i) * out.st] = gs), ...);
-      });
-    }
-  };
-  if constexpr (V == kMleDis) run(MleDisTerm<false>(x0, x1, t, reinterpret_cast<int32_t*>(x2), sm + 4 * L, C, lane));
-  else if constexpr (V == kListnetGauss) run(ListNetGaussTerm(x0, x1, t, C, lane));
-  else if constexpr (V == kListnetLognorm) run(ListNetLognormTerm(x0, x1, t, C, lane));
-  else if constexpr (V == kListnetEvid) run(ListNetEvidTerm(x0, x1, x2, t, C, lane));
-  else run(UqTerm<V == kDirichletUq>(x0, t, coef, C, lane));
-}
-
 // ---------------------------------------------------------------- evidential_loss_new (train/loss.py:402-437)
 // NIG negative log-likelihood + lam * (|t - mu| (2 v + alpha) - eps) of parameter row i against target j.  Elementwise form:
 // j = i.  Cross form (parameters [M, 1] against targets [M], what torch broadcasting makes of the trainer's call): all M x M
@@ -574,11 +432,10 @@ __device__ inline NigRow nig_load(const NigIn& in, int64_t i, float lam, float e
   return nig_row(in.x[0][i * in.st[0]], in.x[1][i * in.st[1]], in.x[2][i * in.st[2]], in.x[3][i * in.st[3]], lam, eps, grads);
 }
 
-// elementwise form: grid-stride, one partial per workgroup (pointwise_fwd_kernel's layout)
+// elementwise form: grid-stride, one partial per workgroup (pointwise_kernel's layout)
 __global__ void __launch_bounds__(256) nig_elem_kernel(NigIn in, const float* __restrict__ targets, int64_t n, float lam,
                                                        float eps, int bwd, float* __restrict__ partial,
                                                        const float* __restrict__ gloss, NigOut out) {
-  __shared__ float red[256];
   float acc = 0.f;
   const float g = bwd ? gloss[0] / static_cast<float>(n) : 0.f;
   const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
@@ -595,14 +452,9 @@ __global__ void __launch_bounds__(256) nig_elem_kernel(NigIn in, const float* __
       out.d[3][i * out.st] = g * d.b;
     }
   }
-  if (bwd) return;
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  if (bwd) return;                                                  // (uniform: no thread reaches the barriers below)
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // cross form: a workgroup owns kNigRows parameter rows (lane = row) and its four waves split the targets, which stream
@@ -661,59 +513,6 @@ __global__ void __launch_bounds__(256) digamma_kernel(const float* __restrict__ 
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) y[i] = digamma_f(x[i]);
 }
 
-// ---------------------------------------------------------------- pointwise: Lognorm (train/loss.py:165-184) and the
-// regression_exploss expression mean((exp(t) - exp(o))^2) (train/train_listwise.py:274-279)
-enum PointwiseExt : int { kLognorm = 0, kExpMse = 1 };
-
-template <int MODE>
-__global__ void __launch_bounds__(256) pointwise_ext_fwd_kernel(const float* __restrict__ x, const float* __restrict__ var,
-                                                                int64_t stride, const float* __restrict__ targets, int64_t n,
-                                                                float* __restrict__ partial) {
-  __shared__ float red[256];
-  const float half_log_2pi = 0.5f * logf(2.0f * 3.14159274101257324f);   // float32(np.pi), loss.py:176,180
-  float acc = 0.f;
-  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    const float s = x[i * stride];
-    if constexpr (MODE == kLognorm) {
-      const float v = var[i * stride];
-      const float e = logf(s) - targets[i];
-      acc += half_log_2pi + 0.5f * logf(v * (s * s)) + (e * e) / (2.0f * v);
-    } else {
-      const float e = expf(targets[i]) - expf(s);
-      acc += e * e;
-    }
-  }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) pointwise_ext_bwd_kernel(const float* __restrict__ x, const float* __restrict__ var,
-                                                                int64_t stride, const float* __restrict__ targets, int64_t n,
-                                                                const float* __restrict__ gloss, float* __restrict__ dx,
-                                                                float* __restrict__ dvar, int64_t dstride) {
-  const float g = gloss[0] / static_cast<float>(n);
-  const int64_t gs = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += gs) {
-    const float s = x[i * stride];
-    if constexpr (MODE == kLognorm) {
-      const float v = var[i * stride];
-      const float e = logf(s) - targets[i];
-      dx[i * dstride] = g * (1.0f / s + e / (v * s));
-      dvar[i * dstride] = g * (0.5f / v - (e * e) / (2.0f * v * v));
-    } else {
-      const float es = expf(s);
-      dx[i * dstride] = g * (-2.0f * es * (expf(targets[i]) - es));
-    }
-  }
-}
-
 int pointwise_blocks(int64_t n) {
   int64_t b = (n + 255) / 256;
   if (b < 1) b = 1;
@@ -731,19 +530,6 @@ int finish_mean(int st, const float* partial, int n, float scale, float* loss, h
 
 inline float inv_count(int64_t n) { return n > 0 ? 1.0f / static_cast<float>(n) : 0.f; }
 
-// forward (gloss == nullptr: partials + the mean over queries into `loss`) or backward of one listwise variant
-template <int V>
-int variant_launch(const VarIn& in, const float* targets, const int32_t* seg_off, int Q, int max_len, float coef, float* loss,
-                   float* partial, const float* gloss, const VarOut& out, rr_stream_t stream) {
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int bwd = gloss != nullptr;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(listwise_variant_kernel<V>, Q, L, variant_lds(V) * sizeof(float), RR_WAVE, s, in, targets,
-                                  seg_off, L, Q, coef, bwd, partial, gloss, out);
-  return bwd ? st : finish_mean(st, partial, Q, inv_count(Q), loss, s);
-}
-
 inline bool strides_ok(const VarIn& in, int nin) {
   for (int k = 0; k < nin; ++k)
     if (!in.x[k] || in.st[k] < 1) return false;
@@ -754,6 +540,52 @@ inline bool outs_ok(const VarOut& o, int nout) {
   for (int k = 0; k < nout; ++k)
     if (!o.d[k]) return false;
   return o.st >= 1;
+}
+
+// The host body of the 21 list entry points: argument check, list-length cap, launch, finish.  total: ListNet's candidate
+// count (the other losses pass 0), coef: the UQ losses' penalty coefficient.  kForward needs loss and partial, kBackward
+// gloss and out, kStep all but gloss.
+template <int K>
+int list_launch(int mode, const VarIn& in, const float* targets, const int32_t* seg_off, int Q, int max_len, int64_t total,
+                float coef, float* loss, float* partial, unsigned int* counter, const float* gloss, const VarOut& out,
+                rr_stream_t stream) {
+  using Loss = ListLoss<K>;
+  RR_CHECK_ARG(list_args_ok(in.x[0], targets, seg_off, Q, max_len) && strides_ok(in, Loss::kInputs) && total >= 0);
+  RR_CHECK_ARG(mode == kBackward ? gloss != nullptr : loss && partial);
+  RR_CHECK_ARG(mode == kForward || outs_ok(out, Loss::kInputs));
+  RR_CHECK_ARG(mode != kStep || counter);
+  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // no candidate to rank: no gradient to write, and a step is the empty mean of the forward entry point.  (The forward still
+  // launches for ListNet's total == 0: it owes the caller its Q zero partials.)
+  const bool nothing = Q == 0 || (K == kListNet && total == 0);
+  if (nothing && mode == kBackward) return RR_OK;
+  if (nothing && mode == kStep) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);
+  const float scale = Loss::finish_scale(inv_count(Q), inv_count(total));
+  const ListArgs a{in,   targets, seg_off, list_words(max_len), Q,    coef,   inv_count(total),
+                   mode, partial, gloss,   out,                 scale, loss,  counter};
+  const int st = launch_per_query(list_loss_kernel<K>, Q, a.L, Loss::kWords * sizeof(float), RR_WAVE, s, a);
+  return mode == kForward ? finish_mean(st, partial, Q, scale, loss, s) : st;
+}
+
+inline VarIn cols(const float* x0, int64_t st0, const float* x1 = nullptr, int64_t st1 = 1, const float* x2 = nullptr,
+                  int64_t st2 = 1) {
+  return VarIn{{x0, x1, x2}, {st0, st1, st2}};
+}
+
+// The host body of the eight pointwise entry points.  The mean of nothing is NaN in the forward (torch.mean); the backward of
+// nothing launches nothing.
+template <int K, bool BWD>
+int pointwise_launch(const float* x, const float* var, int64_t stride, const float* targets, int64_t n, float* loss,
+                     float* partial, const float* gloss, float* dx, float* dvar, int64_t dstride, rr_stream_t stream) {
+  RR_CHECK_ARG(x && (var || !point_has_var(K)) && targets && n >= 0 && stride >= 1);
+  RR_CHECK_ARG(BWD ? gloss && dx && (dvar || !point_has_var(K)) && dstride >= 1 : loss && partial);
+  if (BWD && n == 0) return RR_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nb = pointwise_blocks(n);
+  pointwise_kernel<K, BWD><<<nb, 256, 0, s>>>(x, var, stride, targets, n, partial, gloss, dx, dvar, dstride);
+  if (!BWD) reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
+  return rr_launch_status();
 }
 
 int nig_launch(const NigIn& in, const float* targets, int64_t n, int cross, float lam, float eps, float* loss, float* partial,
@@ -793,122 +625,122 @@ extern "C" {
 
 long long rr_lds_opt_ins(void) { return rr_lds_opt_in_count.load(std::memory_order_relaxed); }
 
+// ---------------------------------------------------------------- the list losses: thin wrappers over list_launch<K>
 int rr_listmle_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, float* loss, float* partial, rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && score_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, Q,
-                                  0, partial, nullptr, nullptr, 1, 0.f, nullptr, nullptr);
-  return finish_mean(st, partial, Q, inv_count(Q), loss, s);
+  return list_launch<kListMle>(kForward, cols(score, score_stride), targets, seg_off, Q, max_len, 0, 0.f, loss, partial, nullptr,
+                               nullptr, VarOut{}, stream);
 }
 
 int rr_listmle_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, const float* gloss, float* dscore, int64_t dscore_stride, rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
-               dscore_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
-                          targets, seg_off, L, Q, 1, nullptr, gloss, dscore, dscore_stride, 0.f, nullptr, nullptr);
+  return list_launch<kListMle>(kBackward, cols(score, score_stride), targets, seg_off, Q, max_len, 0, 0.f, nullptr, nullptr,
+                               nullptr, gloss, VarOut{{dscore}, dscore_stride}, stream);
 }
 
 int rr_listmle_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
                         float* loss, float* partial, unsigned int* counter, float* dscore, int64_t dscore_stride,
                         rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && counter && dscore && score_stride >= 1 &&
-               dscore_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);   // nothing to rank: the empty mean of the forward entry point
-  const int L = list_words(max_len);
-  return launch_per_query(listmle_kernel, Q, L, 5 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, Q, 2,
-                          partial, nullptr, dscore, dscore_stride, 1.0f / static_cast<float>(Q), loss, counter);
+  return list_launch<kListMle>(kStep, cols(score, score_stride), targets, seg_off, Q, max_len, 0, 0.f, loss, partial, counter,
+                               nullptr, VarOut{{dscore}, dscore_stride}, stream);
 }
 
 int rr_listnet_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, int64_t total, float* loss, float* partial, rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && score_stride >= 1 && total >= 0);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, 0,
-                                  partial, nullptr, 0.f, nullptr, 1, nullptr, nullptr);
-  return finish_mean(st, partial, Q, inv_count(total), loss, s);    // ONE global mean over all candidates (loss.py:347)
+  return list_launch<kListNet>(kForward, cols(score, score_stride), targets, seg_off, Q, max_len, total, 0.f, loss, partial,
+                               nullptr, nullptr, VarOut{}, stream);
 }
 
 int rr_listnet_bwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, int64_t total, const float* gloss, float* dscore, int64_t dscore_stride,
                        rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
-               dscore_stride >= 1 && total >= 0);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  if (total == 0) return RR_OK;
-  const int L = list_words(max_len);
-  return launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
-                          targets, seg_off, L, 1, nullptr, gloss, 1.0f / static_cast<float>(total), dscore, dscore_stride, nullptr,
-                          nullptr);
+  return list_launch<kListNet>(kBackward, cols(score, score_stride), targets, seg_off, Q, max_len, total, 0.f, nullptr, nullptr,
+                               nullptr, gloss, VarOut{{dscore}, dscore_stride}, stream);
 }
 
 int rr_listnet_step_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
                         int64_t total, float* loss, float* partial, unsigned int* counter, float* dscore, int64_t dscore_stride,
                         rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss && partial && counter && dscore && score_stride >= 1 &&
-               dscore_stride >= 1 && total >= 0);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0 || total == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);
-  const int L = list_words(max_len);
-  return launch_per_query(listnet_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L, 2, partial,
-                          nullptr, 1.0f / static_cast<float>(total), dscore, dscore_stride, loss, counter);
+  return list_launch<kListNet>(kStep, cols(score, score_stride), targets, seg_off, Q, max_len, total, 0.f, loss, partial, counter,
+                               nullptr, VarOut{{dscore}, dscore_stride}, stream);
 }
 
 int rr_evidential_ranking_fwd_f32(const float* mu, const float* var, int64_t stride, const float* targets,
                                   const int32_t* seg_off, int Q, int max_len, float* loss, float* partial,
                                   rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(mu, targets, seg_off, Q, max_len) && var && loss && partial && stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, s, mu, var, stride, targets, seg_off, L, Q, 0,
-                                  partial, nullptr, nullptr, nullptr, 1, nullptr, nullptr);
-  return finish_mean(st, partial, Q, inv_count(Q), loss, s);
+  return list_launch<kUcListwise>(kForward, cols(mu, stride, var, stride), targets, seg_off, Q, max_len, 0, 0.f, loss, partial,
+                                  nullptr, nullptr, VarOut{}, stream);
 }
 
 int rr_evidential_ranking_bwd_f32(const float* mu, const float* var, int64_t stride, const float* targets,
                                   const int32_t* seg_off, int Q, int max_len, const float* gloss, float* dmu,
                                   float* dvar, int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(mu, targets, seg_off, Q, max_len) && var && gloss && dmu && dvar && stride >= 1 &&
-               dstride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), mu, var, stride,
-                          targets, seg_off, L, Q, 1, nullptr, gloss, dmu, dvar, dstride, nullptr, nullptr);
+  return list_launch<kUcListwise>(kBackward, cols(mu, stride, var, stride), targets, seg_off, Q, max_len, 0, 0.f, nullptr, nullptr,
+                                  nullptr, gloss, VarOut{{dmu, dvar}, dstride}, stream);
 }
 
 int rr_evidential_ranking_step_f32(const float* mu, const float* var, int64_t stride, const float* targets, const int32_t* seg_off,
                                    int Q, int max_len, float* loss, float* partial, unsigned int* counter, float* dmu, float* dvar,
                                    int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(list_args_ok(mu, targets, seg_off, Q, max_len) && var && loss && partial && counter && dmu && dvar && stride >= 1 &&
-               dstride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (Q == 0) return finish_mean(RR_OK, partial, 0, 0.f, loss, s);
-  const int L = list_words(max_len);
-  return launch_per_query(evidential_kernel, Q, L, 3 * sizeof(float), RR_WAVE, s, mu, var, stride, targets, seg_off, L, Q, 2, partial,
-                          nullptr, dmu, dvar, dstride, loss, counter);
+  return list_launch<kUcListwise>(kStep, cols(mu, stride, var, stride), targets, seg_off, Q, max_len, 0, 0.f, loss, partial,
+                                  counter, nullptr, VarOut{{dmu, dvar}, dstride}, stream);
 }
+
+#define RR_VAR2(NAME, K)                                                                                                        \
+  int rr_##NAME##_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
+                          const int32_t* seg_off, int Q, int max_len, float* loss, float* partial, rr_stream_t stream) {      \
+    return list_launch<K>(kForward, cols(mean, mean_stride, var, var_stride), targets, seg_off, Q, max_len, 0, 0.f, loss,       \
+                          partial, nullptr, nullptr, VarOut{}, stream);                                                        \
+  }                                                                                                                              \
+  int rr_##NAME##_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
+                          const int32_t* seg_off, int Q, int max_len, const float* gloss, float* dmean, float* dvar,           \
+                          int64_t dstride, rr_stream_t stream) {                                                               \
+    return list_launch<K>(kBackward, cols(mean, mean_stride, var, var_stride), targets, seg_off, Q, max_len, 0, 0.f, nullptr,   \
+                          nullptr, nullptr, gloss, VarOut{{dmean, dvar}, dstride}, stream);                                    \
+  }
+
+RR_VAR2(mledis, kMleDis)
+RR_VAR2(listnet_gauss, kListnetGauss)
+RR_VAR2(listnet_lognorm, kListnetLognorm)
+#undef RR_VAR2
+
+int rr_listnet_evidential_fwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
+                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
+                                  float* loss, float* partial, rr_stream_t stream) {
+  return list_launch<kListnetEvid>(kForward, cols(mean, mean_stride, v, v_stride, alpha, alpha_stride), targets, seg_off, Q,
+                                   max_len, 0, 0.f, loss, partial, nullptr, nullptr, VarOut{}, stream);
+}
+
+int rr_listnet_evidential_bwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
+                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
+                                  const float* gloss, float* dmean, float* dv, float* dalpha, int64_t dstride,
+                                  rr_stream_t stream) {
+  return list_launch<kListnetEvid>(kBackward, cols(mean, mean_stride, v, v_stride, alpha, alpha_stride), targets, seg_off, Q,
+                                   max_len, 0, 0.f, nullptr, nullptr, nullptr, gloss, VarOut{{dmean, dv, dalpha}, dstride}, stream);
+}
+
+#define RR_VAR1(NAME, K)                                                                                                        \
+  int rr_##NAME##_fwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
+                          float coef, float* loss, float* partial, rr_stream_t stream) {                                       \
+    return list_launch<K>(kForward, cols(x, stride), targets, seg_off, Q, max_len, 0, coef, loss, partial, nullptr, nullptr,    \
+                          VarOut{}, stream);                                                                                   \
+  }                                                                                                                              \
+  int rr_##NAME##_bwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
+                          float coef, const float* gloss, float* dx, int64_t dstride, rr_stream_t stream) {                    \
+    return list_launch<K>(kBackward, cols(x, stride), targets, seg_off, Q, max_len, 0, coef, nullptr, nullptr, nullptr, gloss,  \
+                          VarOut{{dx}, dstride}, stream);                                                                      \
+  }
+
+RR_VAR1(listnet_uq, kListnetUq)
+RR_VAR1(dirichlet_uq, kDirichletUq)
+#undef RR_VAR1
 
 int rr_ranknet_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                        int max_len, float sigma, float* loss_sum, int64_t* pairs, float* partial,
                        rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss_sum && pairs && partial && score_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(ranknet_fwd_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L,
-                                  sigma, partial);
+  const int st = launch_list(ranknet_fwd_kernel, 2 * sizeof(float), score, score_stride, targets, seg_off, Q, max_len, s, sigma, partial);
   if (st != RR_OK) return st;
   finish_counted_kernel<<<1, RR_WAVE, 0, s>>>(partial, Q, 1.0f, loss_sum, pairs);
   return rr_launch_status();
@@ -919,50 +751,50 @@ int rr_ranknet_bwd_f32(const float* score, int64_t score_stride, const float* ta
                        rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1 && (mode == 0 || mode == 1));
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(ranknet_bwd_kernel, Q, L, 3 * sizeof(float), RR_WAVE, static_cast<hipStream_t>(stream), score,
-                          score_stride, targets, seg_off, L, sigma, mode, gloss, dscore, dscore_stride);
+  return launch_list(ranknet_bwd_kernel, 3 * sizeof(float), score, score_stride, targets, seg_off, Q, max_len,
+                     static_cast<hipStream_t>(stream), sigma, mode, gloss, dscore, dscore_stride);
 }
 
 int64_t rr_pointwise_partial_count(int64_t n) { return pointwise_blocks(n); }
 
 int rr_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
                    rr_stream_t stream) {
-  RR_CHECK_ARG(pred && targets && loss && partial && n >= 0 && stride >= 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nb = pointwise_blocks(n);
-  pointwise_fwd_kernel<<<nb, 256, 0, s>>>(pred, nullptr, stride, targets, n, 0, partial);
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
-  return rr_launch_status();
+  return pointwise_launch<kPointMse, false>(pred, nullptr, stride, targets, n, loss, partial, nullptr, nullptr, nullptr, 1, stream);
 }
 
 int rr_mse_bwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, const float* gloss,
                    float* dpred, int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(pred && targets && gloss && dpred && n >= 0 && stride >= 1 && dstride >= 1);
-  if (n == 0) return RR_OK;
-  pointwise_bwd_kernel<<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      pred, nullptr, stride, targets, n, 0, gloss, dpred, nullptr, dstride);
-  return rr_launch_status();
+  return pointwise_launch<kPointMse, true>(pred, nullptr, stride, targets, n, nullptr, nullptr, gloss, dpred, nullptr, dstride, stream);
 }
 
 int rr_gauss_nll_fwd_f32(const float* mean, const float* var, int64_t stride, const float* targets, int64_t n,
                          float* loss, float* partial, rr_stream_t stream) {
-  RR_CHECK_ARG(mean && var && targets && loss && partial && n >= 0 && stride >= 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nb = pointwise_blocks(n);
-  pointwise_fwd_kernel<<<nb, 256, 0, s>>>(mean, var, stride, targets, n, 1, partial);
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
-  return rr_launch_status();
+  return pointwise_launch<kPointGauss, false>(mean, var, stride, targets, n, loss, partial, nullptr, nullptr, nullptr, 1, stream);
 }
 
 int rr_gauss_nll_bwd_f32(const float* mean, const float* var, int64_t stride, const float* targets, int64_t n,
                          const float* gloss, float* dmean, float* dvar, int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(mean && var && targets && gloss && dmean && dvar && n >= 0 && stride >= 1 && dstride >= 1);
-  if (n == 0) return RR_OK;
-  pointwise_bwd_kernel<<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      mean, var, stride, targets, n, 1, gloss, dmean, dvar, dstride);
-  return rr_launch_status();
+  return pointwise_launch<kPointGauss, true>(mean, var, stride, targets, n, nullptr, nullptr, gloss, dmean, dvar, dstride, stream);
+}
+
+int rr_lognorm_fwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, float* loss,
+                       float* partial, rr_stream_t stream) {
+  return pointwise_launch<kPointLognorm, false>(score, var, stride, targets, n, loss, partial, nullptr, nullptr, nullptr, 1, stream);
+}
+
+int rr_lognorm_bwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, const float* gloss,
+                       float* dscore, float* dvar, int64_t dstride, rr_stream_t stream) {
+  return pointwise_launch<kPointLognorm, true>(score, var, stride, targets, n, nullptr, nullptr, gloss, dscore, dvar, dstride, stream);
+}
+
+int rr_exp_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
+                       rr_stream_t stream) {
+  return pointwise_launch<kPointExpMse, false>(pred, nullptr, stride, targets, n, loss, partial, nullptr, nullptr, nullptr, 1, stream);
+}
+
+int rr_exp_mse_bwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, const float* gloss, float* dpred,
+                       int64_t dstride, rr_stream_t stream) {
+  return pointwise_launch<kPointExpMse, true>(pred, nullptr, stride, targets, n, nullptr, nullptr, gloss, dpred, nullptr, dstride, stream);
 }
 
 int rr_ranking_metrics_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
@@ -970,10 +802,8 @@ int rr_ranking_metrics_f32(const float* score, int64_t score_stride, const float
                            rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && order && stats && score_stride >= 1);
   RR_CHECK_ARG(ratio >= 0.0 && ratio <= 1.0 && ndcg_cut >= 0.0 && ndcg_cut <= 1.0);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(ranking_metrics_kernel, Q, L, 2 * sizeof(float) + 4 * sizeof(uint16_t), RR_WAVE,
-                          static_cast<hipStream_t>(stream), score, score_stride, targets, seg_off, L, ratio, ndcg_cut, order, stats);
+  return launch_list(ranking_metrics_kernel, 2 * sizeof(float) + 4 * sizeof(uint16_t), score, score_stride, targets, seg_off, Q,
+                     max_len, static_cast<hipStream_t>(stream), ratio, ndcg_cut, order, stats);
 }
 
 int rr_logcumsumexp_fwd_f32(const float* x, int n, float* y, rr_stream_t stream) {
@@ -996,66 +826,6 @@ int rr_logcumsumexp_bwd_f32(const float* x, const float* y, const float* gy, int
   return rr_launch_status();
 }
 
-
-// ---------------------------------------------------------------- listwise variants
-#define RR_VAR2(NAME, V)                                                                                                        \
-  int rr_##NAME##_fwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
-                          const int32_t* seg_off, int Q, int max_len, float* loss, float* partial, rr_stream_t stream) {      \
-    const VarIn in{{mean, var, nullptr}, {mean_stride, var_stride, 1}};                                                          \
-    RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 2) && loss && partial);                      \
-    return variant_launch<V>(in, targets, seg_off, Q, max_len, 0.f, loss, partial, nullptr, VarOut{}, stream);                  \
-  }                                                                                                                              \
-  int rr_##NAME##_bwd_f32(const float* mean, int64_t mean_stride, const float* var, int64_t var_stride, const float* targets,  \
-                          const int32_t* seg_off, int Q, int max_len, const float* gloss, float* dmean, float* dvar,           \
-                          int64_t dstride, rr_stream_t stream) {                                                               \
-    const VarIn in{{mean, var, nullptr}, {mean_stride, var_stride, 1}};                                                          \
-    const VarOut out{{dmean, dvar, nullptr}, dstride};                                                                           \
-    RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 2) && gloss && outs_ok(out, 2));             \
-    return variant_launch<V>(in, targets, seg_off, Q, max_len, 0.f, nullptr, nullptr, gloss, out, stream);                      \
-  }
-
-RR_VAR2(mledis, kMleDis)
-RR_VAR2(listnet_gauss, kListnetGauss)
-RR_VAR2(listnet_lognorm, kListnetLognorm)
-#undef RR_VAR2
-
-int rr_listnet_evidential_fwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
-                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
-                                  float* loss, float* partial, rr_stream_t stream) {
-  const VarIn in{{mean, v, alpha}, {mean_stride, v_stride, alpha_stride}};
-  RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 3) && loss && partial);
-  return variant_launch<kListnetEvid>(in, targets, seg_off, Q, max_len, 0.f, loss, partial, nullptr, VarOut{}, stream);
-}
-
-int rr_listnet_evidential_bwd_f32(const float* mean, int64_t mean_stride, const float* v, int64_t v_stride, const float* alpha,
-                                  int64_t alpha_stride, const float* targets, const int32_t* seg_off, int Q, int max_len,
-                                  const float* gloss, float* dmean, float* dv, float* dalpha, int64_t dstride,
-                                  rr_stream_t stream) {
-  const VarIn in{{mean, v, alpha}, {mean_stride, v_stride, alpha_stride}};
-  const VarOut out{{dmean, dv, dalpha}, dstride};
-  RR_CHECK_ARG(list_args_ok(mean, targets, seg_off, Q, max_len) && strides_ok(in, 3) && gloss && outs_ok(out, 3));
-  return variant_launch<kListnetEvid>(in, targets, seg_off, Q, max_len, 0.f, nullptr, nullptr, gloss, out, stream);
-}
-
-#define RR_VAR1(NAME, V)                                                                                                        \
-  int rr_##NAME##_fwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
-                          float coef, float* loss, float* partial, rr_stream_t stream) {                                       \
-    const VarIn in{{x, nullptr, nullptr}, {stride, 1, 1}};                                                                       \
-    RR_CHECK_ARG(list_args_ok(x, targets, seg_off, Q, max_len) && strides_ok(in, 1) && loss && partial);                         \
-    return variant_launch<V>(in, targets, seg_off, Q, max_len, coef, loss, partial, nullptr, VarOut{}, stream);                 \
-  }                                                                                                                              \
-  int rr_##NAME##_bwd_f32(const float* x, int64_t stride, const float* targets, const int32_t* seg_off, int Q, int max_len,     \
-                          float coef, const float* gloss, float* dx, int64_t dstride, rr_stream_t stream) {                    \
-    const VarIn in{{x, nullptr, nullptr}, {stride, 1, 1}};                                                                       \
-    const VarOut out{{dx, nullptr, nullptr}, dstride};                                                                           \
-    RR_CHECK_ARG(list_args_ok(x, targets, seg_off, Q, max_len) && strides_ok(in, 1) && gloss && outs_ok(out, 1));                \
-    return variant_launch<V>(in, targets, seg_off, Q, max_len, coef, nullptr, nullptr, gloss, out, stream);                     \
-  }
-
-RR_VAR1(listnet_uq, kListnetUq)
-RR_VAR1(dirichlet_uq, kDirichletUq)
-#undef RR_VAR1
-
 // ---------------------------------------------------------------- evidential_loss_new
 int rr_nig_fwd_f32(const float* mu, int64_t mu_stride, const float* v, int64_t v_stride, const float* alpha, int64_t alpha_stride,
                    const float* beta, int64_t beta_stride, const float* targets, int64_t n, int cross, float lam, float epsilon,
@@ -1076,45 +846,6 @@ int rr_digamma_f32(const float* x, int64_t n, float* y, rr_stream_t stream) {
   RR_CHECK_ARG(x && y && n >= 0);
   if (n == 0) return RR_OK;
   digamma_kernel<<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(x, n, y);
-  return rr_launch_status();
-}
-
-// ---------------------------------------------------------------- Lognorm, exp-MSE
-int rr_lognorm_fwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, float* loss,
-                       float* partial, rr_stream_t stream) {
-  RR_CHECK_ARG(score && var && targets && loss && partial && n >= 0 && stride >= 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nb = pointwise_blocks(n);
-  pointwise_ext_fwd_kernel<kLognorm><<<nb, 256, 0, s>>>(score, var, stride, targets, n, partial);
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
-  return rr_launch_status();
-}
-
-int rr_lognorm_bwd_f32(const float* score, const float* var, int64_t stride, const float* targets, int64_t n, const float* gloss,
-                       float* dscore, float* dvar, int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(score && var && targets && gloss && dscore && dvar && n >= 0 && stride >= 1 && dstride >= 1);
-  if (n == 0) return RR_OK;
-  pointwise_ext_bwd_kernel<kLognorm><<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      score, var, stride, targets, n, gloss, dscore, dvar, dstride);
-  return rr_launch_status();
-}
-
-int rr_exp_mse_fwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, float* loss, float* partial,
-                       rr_stream_t stream) {
-  RR_CHECK_ARG(pred && targets && loss && partial && n >= 0 && stride >= 1);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nb = pointwise_blocks(n);
-  pointwise_ext_fwd_kernel<kExpMse><<<nb, 256, 0, s>>>(pred, nullptr, stride, targets, n, partial);
-  reduce_scale_kernel<<<1, 256, 0, s>>>(partial, nb, 1, n > 0 ? 1.0f / static_cast<float>(n) : NAN, loss);
-  return rr_launch_status();
-}
-
-int rr_exp_mse_bwd_f32(const float* pred, int64_t stride, const float* targets, int64_t n, const float* gloss, float* dpred,
-                       int64_t dstride, rr_stream_t stream) {
-  RR_CHECK_ARG(pred && targets && gloss && dpred && n >= 0 && stride >= 1 && dstride >= 1);
-  if (n == 0) return RR_OK;
-  pointwise_ext_bwd_kernel<kExpMse><<<pointwise_blocks(n), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      pred, nullptr, stride, targets, n, gloss, dpred, nullptr, dstride);
   return rr_launch_status();
 }
 

@@ -1,6 +1,6 @@
-// The per-list loss terms, each defined ONCE for every kernel that evaluates it (loss.hip: one kernel per loss;
-// task_loss.hip: the composite one-launch step).  One 64-lane wavefront owns one list staged in LDS; only wave-level
-// synchronisation.
+// The per-list loss terms, each defined ONCE for every kernel that evaluates it (loss.hip: list_loss_kernel, one shell over
+// the nine list losses; task_loss.hip: the composite one-launch step).  One 64-lane wavefront owns one list staged in LDS;
+// only wave-level synchronisation.
 //
 // A term is a small struct built over the staged list (its constructor does the work forward and gradient share: ranking,
 // softmax statistics, scans) with
@@ -9,6 +9,10 @@
 //                      staged, g0.. the gradient of its input columns for the caller's scale g.
 // The kernel shell owns the rest: where the list lies in LDS (the term takes pointers), any transform of its inputs, and
 // every normaliser (1 / C, 1 / Q, 1 / total, the upstream gradient).  No term divides by a count.
+// Next to each term, ListLoss<K> holds what list_loss_kernel needs to know of the loss: kInputs input columns, kWords staged
+// words per candidate, term() the term over the staged list, partial() the query's loss from forward(), grad_scale() the g of
+// gradient() and finish_scale() what the sum of the partials is multiplied with.  The normalisers differ between the losses
+// on purpose, and in bits: they are the reference's expressions, not to be aligned.
 // The library is built with -ffp-contract=off and no fast-math, so an expression has the same bits in every kernel it is
 // inlined into.
 #pragma once
@@ -17,11 +21,12 @@
 namespace {
 
 struct ListView {
-  float* s;       // scores (as given)
+  float* s;       // scores (as given): input column 0
   float* t;       // targets
-  float* ss;      // scores sorted by target, descending
-  int32_t* perm;  // perm[j] = original position of sorted element j
+  float* ss;      // scores sorted by target, descending (ListMLE); input column 1 of the losses that have one
+  int32_t* perm;  // perm[j] = original position of sorted element j (ListMLE, MLEDis); input column 2 (ListNet-evidential)
   float* aux;     // scratch (fd values)
+  __device__ float* col(int k) const { return k == 0 ? s : k == 1 ? ss : reinterpret_cast<float*>(perm); }   // input column k
 };
 
 // the one LDS layout of the list kernels: five arrays of L words, of which a kernel allocates the leading ones it uses
@@ -105,6 +110,26 @@ __device__ inline void softmax_stats(const float* a, int C, int lane, float* mx,
   *sum = rr_wave_sum(s);
 }
 
+enum ListLossKind : int {
+  kListMle, kListNet, kUcListwise, kMleDis, kListnetGauss, kListnetLognorm, kListnetEvid, kListnetUq, kDirichletUq
+};
+
+// what a list loss's normalisers are made of: the list's length, the window's query count, 1 / its candidate count
+// (ListNet alone) and the penalty coefficient (the UQ losses alone)
+struct ListNorm {
+  int C, Q;
+  float inv_total, coef;
+};
+
+// The normalisers most losses share: a mean over the list (in partial()), then a mean over the queries.  gl: the upstream gradient
+struct PerQueryMean {
+  __device__ static float grad_scale(float gl, const ListNorm& n) { return gl / (static_cast<float>(n.C) * static_cast<float>(n.Q)); }
+  static float finish_scale(float inv_queries, float /*inv_total*/) { return inv_queries; }
+};
+
+template <int K>
+struct ListLoss;
+
 __device__ inline float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }   // torch.abs' gradient
 
 // softmax of a staged list: p(i) = exp(a[i] - max) / sum
@@ -142,6 +167,13 @@ struct ListMleTerm {
   }
 };
 
+template <>
+struct ListLoss<kListMle> : PerQueryMean {
+  static constexpr int kInputs = 1, kWords = 5;
+  __device__ static ListMleTerm term(const ListView& v, const ListNorm& n, int lane) { return ListMleTerm(v, n.C, lane); }
+  __device__ static float partial(float acc, const ListNorm& n) { return acc / static_cast<float>(n.C); }   // torch.mean, loss.py:94
+};
+
 // ---------------------------------------------------------------- ListNet top-1 (train/loss.py:317-352)
 struct ListNetTerm {
   Softmax ps, pt;
@@ -161,6 +193,16 @@ struct ListNetTerm {
     const float tsum = pt.total(C, lane);
     for (int i = lane; i < C; i += RR_WAVE) emit(i, g * (ps(i) * tsum - pt(i)));
   }
+};
+
+// ONE mean over all candidates (loss.py:347): the partial is the raw sum, 1 / total scales the gradient and the finish
+template <>
+struct ListLoss<kListNet> {
+  static constexpr int kInputs = 1, kWords = 2;
+  __device__ static ListNetTerm term(const ListView& v, const ListNorm& n, int lane) { return ListNetTerm(v.s, v.t, n.C, lane); }
+  __device__ static float partial(float acc, const ListNorm&) { return acc; }
+  __device__ static float grad_scale(float gl, const ListNorm& n) { return gl * n.inv_total; }
+  static float finish_scale(float /*inv_queries*/, float inv_total) { return inv_total; }
 };
 
 // ---------------------------------------------------------------- evidential UC-Listwise (train/loss.py:477-556)
@@ -202,6 +244,15 @@ struct UcListwiseTerm {
       emit(i, g * (c - p * csum + sgnf(s[i] - t[i])), g * (-0.5f * d * d / (vv[i] * vv[i]) + 0.5f / vv[i]));
     }
   }
+};
+
+template <>
+struct ListLoss<kUcListwise> : PerQueryMean {
+  static constexpr int kInputs = 2, kWords = 3;
+  __device__ static UcListwiseTerm term(const ListView& v, const ListNorm& n, int lane) {
+    return UcListwiseTerm(v.s, v.ss, v.t, n.C, lane);
+  }
+  __device__ static float partial(float acc, const ListNorm& n) { return acc / static_cast<float>(n.C); }
 };
 
 // ---------------------------------------------------------------- the listwise variants (train/loss.py:102-141, 187-314,
@@ -250,6 +301,19 @@ struct MleDisTerm {
   }
 };
 
+// the variants multiply with the rounded 1 / C where ListMLE and UC-Listwise divide by C
+struct VariantMean : PerQueryMean {
+  __device__ static float partial(float acc, const ListNorm& n) { return acc * (1.0f / static_cast<float>(n.C)); }
+};
+
+template <>
+struct ListLoss<kMleDis> : VariantMean {
+  static constexpr int kInputs = 2, kWords = 5;   // x0, t, x1, perm, F
+  __device__ static MleDisTerm<false> term(const ListView& v, const ListNorm& n, int lane) {
+    return MleDisTerm<false>(v.s, v.ss, v.t, v.perm, v.aux, n.C, lane);
+  }
+};
+
 // Listnet_For_Gauss: log sum_j exp(s_j - s_i + (v_i + v_j) / 2) = LSE_j(s_j + v_j / 2) - s_i + v_i / 2.  emit(row, d / d s, d / d v)
 struct ListNetGaussTerm {
   const float *x0, *x1;
@@ -278,6 +342,14 @@ struct ListNetGaussTerm {
       const float pk = expf(x0[k] + 0.5f * x1[k] - lse), tk = pt(k);
       emit(k, g * (tsum * pk - tk), g * 0.5f * (tsum * pk + tk));
     }
+  }
+};
+
+template <>
+struct ListLoss<kListnetGauss> : VariantMean {
+  static constexpr int kInputs = 2, kWords = 3;
+  __device__ static ListNetGaussTerm term(const ListView& v, const ListNorm& n, int lane) {
+    return ListNetGaussTerm(v.s, v.ss, v.t, n.C, lane);
   }
 };
 
@@ -311,6 +383,14 @@ struct ListNetLognormTerm {
   }
 };
 
+template <>
+struct ListLoss<kListnetLognorm> : VariantMean {
+  static constexpr int kInputs = 2, kWords = 3;
+  __device__ static ListNetLognormTerm term(const ListView& v, const ListNorm& n, int lane) {
+    return ListNetLognormTerm(v.s, v.ss, v.t, n.C, lane);
+  }
+};
+
 // Listnet_For_evidential: forward() is sum_i softmax(t)_i * log_softmax(s)_i * (2 v_i + alpha_i); the loss is its NEGATIVE
 // mean (the caller's sign, with its normaliser), and gradient() is the gradient of that loss.  emit(row, d / d s, d / d v, d / d alpha)
 struct ListNetEvidTerm {
@@ -337,6 +417,15 @@ struct ListNetEvidTerm {
       emit(k, -g * (tk * (2.0f * x1[k] + x2[k]) - pk * wsum), -g * 2.0f * tk * lsk, -g * tk * lsk);
     }
   }
+};
+
+template <>
+struct ListLoss<kListnetEvid> : PerQueryMean {
+  static constexpr int kInputs = 3, kWords = 4;
+  __device__ static ListNetEvidTerm term(const ListView& v, const ListNorm& n, int lane) {
+    return ListNetEvidTerm(v.s, v.ss, v.col(2), v.t, n.C, lane);
+  }
+  __device__ static float partial(float acc, const ListNorm& n) { return -(acc * (1.0f / static_cast<float>(n.C))); }
 };
 
 // Listnet_with_uq (DIRICHLET false): p = s / sum(s); KL(softmax(t) || p) / C + coef * mean_i |log(softmax(t)_i / p_i) (s_i - 1)|
@@ -408,26 +497,54 @@ struct UqTerm {
   }
 };
 
-// ---------------------------------------------------------------- pointwise rows: MSE and Gaussian NLL (train/loss.py:144-162)
+template <bool DIRICHLET>
+struct UqLoss : PerQueryMean {
+  static constexpr int kInputs = 1, kWords = 2;
+  __device__ static UqTerm<DIRICHLET> term(const ListView& v, const ListNorm& n, int lane) {
+    return UqTerm<DIRICHLET>(v.s, v.t, n.coef, n.C, lane);
+  }
+  __device__ static float partial(const UqSums& acc, const ListNorm& n) {
+    const float invC = 1.0f / static_cast<float>(n.C);
+    return acc.acc * invC + n.coef * (acc.pen * invC);
+  }
+};
+template <> struct ListLoss<kListnetUq> : UqLoss<false> {};
+template <> struct ListLoss<kDirichletUq> : UqLoss<true> {};
+
+// ---------------------------------------------------------------- pointwise rows: MSE and Gaussian NLL (train/loss.py:144-162),
+// Lognorm (train/loss.py:165-184) and the regression_exploss expression mean((exp(t) - exp(o))^2) (train/train_listwise.py:274-279)
 // One row's value and its gradients for the caller's scale g (a forward-only caller passes anything and ignores them, a
 // backward-only caller ignores the value: the compiler drops what is unused).
 struct PointRow {
   float value, dmean, dvar;
 };
 
-template <bool GAUSS>
-__device__ inline PointRow point_row(float mean, float targ, float v, float g) {
-  const float d = mean - targ;
-  if constexpr (GAUSS) {
-    const float half_log_2pi = 0.5f * logf(2.0f * 3.14159274101257324f);   // float32(np.pi), loss.py:152,159
-    return PointRow{half_log_2pi + 0.5f * logf(v) + (d * d) / (2.0f * v), g * d / v, g * (0.5f / v - (d * d) / (2.0f * v * v))};
+enum PointKind : int { kPointMse, kPointGauss, kPointLognorm, kPointExpMse };
+constexpr bool point_has_var(int K) { return K == kPointGauss || K == kPointLognorm; }
+
+// x: the mean (MSE, Gauss), the score (Lognorm) or the prediction (exp-MSE); v is read by the kinds that have a variance
+__device__ inline float half_log_2pi() { return 0.5f * logf(2.0f * 3.14159274101257324f); }   // float32(np.pi), loss.py:152,159,176,180
+
+template <int K>
+__device__ inline PointRow point_row(float x, float targ, float v, float g) {
+  if constexpr (K == kPointGauss) {
+    const float d = x - targ;
+    return PointRow{half_log_2pi() + 0.5f * logf(v) + (d * d) / (2.0f * v), g * d / v, g * (0.5f / v - (d * d) / (2.0f * v * v))};
+  } else if constexpr (K == kPointLognorm) {
+    const float e = logf(x) - targ;
+    return PointRow{half_log_2pi() + 0.5f * logf(v * (x * x)) + (e * e) / (2.0f * v), g * (1.0f / x + e / (v * x)),
+                    g * (0.5f / v - (e * e) / (2.0f * v * v))};
+  } else if constexpr (K == kPointExpMse) {
+    const float es = expf(x), e = expf(targ) - es;
+    return PointRow{e * e, g * (-2.0f * es * e), 0.f};
   } else {
+    const float d = x - targ;
     return PointRow{d * d, g * 2.0f * d, 0.f};
   }
 }
 
 // ---------------------------------------------------------------- the last-arriver finish of the one-launch "step" kernels
-// fixed-order sum of n floats on one wave: reduce_scale_kernel's order (256 strided accumulators, then its halving tree),
+// fixed-order sum of n floats on one wave: reduce_scale_kernel's order (256 strided accumulators, then block_sum's halving tree),
 // lane l playing threads l, l + 64, l + 128, l + 192; the result is valid in lane 0.  step: the distance between two values.
 __device__ inline float fixed_sum(const float* p, int n, int lane, int step = 1) {
   float a[4];

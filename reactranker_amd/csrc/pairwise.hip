@@ -202,8 +202,6 @@ __global__ void __launch_bounds__(RR_WAVE) beta_evi_kernel(const float* __restri
 // loss_sum = sum of the per-query partials, pairs = sum of C^2 - C: one block, fixed order
 __global__ void __launch_bounds__(256) finish_sq_kernel(const double* __restrict__ partial, const int32_t* __restrict__ seg_off,
                                                         int Q, float* __restrict__ loss_sum, int64_t* __restrict__ pairs) {
-  __shared__ double red[256];
-  __shared__ long long redp[256];
   double acc = 0.0;
   long long np = 0;
   for (int i = threadIdx.x; i < Q; i += 256) {
@@ -211,19 +209,11 @@ __global__ void __launch_bounds__(256) finish_sq_kernel(const double* __restrict
     const long long c = seg_off[i + 1] - seg_off[i];
     if (c > 0) np += c * c - c;
   }
-  red[threadIdx.x] = acc;
-  redp[threadIdx.x] = np;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) {
-      red[threadIdx.x] += red[threadIdx.x + o];
-      redp[threadIdx.x] += redp[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
+  acc = block_sum(acc);                                             // two types, so two trees: each in block_sum's order
+  np = block_sum(np);
   if (threadIdx.x == 0) {
-    loss_sum[0] = static_cast<float>(red[0]);
-    pairs[0] = redp[0];
+    loss_sum[0] = static_cast<float>(acc);
+    pairs[0] = np;
   }
 }
 
@@ -245,11 +235,7 @@ __global__ void __launch_bounds__(RR_WAVE) pairwise_eval_kernel(const float* __r
   }
   float* s = sm;
   float* t = sm + L;
-  for (int i = lane; i < C; i += RR_WAVE) {
-    s[i] = score[static_cast<int64_t>(off + i) * sstride];
-    t[i] = targets[off + i];
-  }
-  wave_sync();
+  stage_list(s, t, score, sstride, targets, off, C, lane);
   int npos = 0, mism = 0;
   double ce = 0.0;
   for (int i = lane; i < C; i += RR_WAVE) {
@@ -279,7 +265,6 @@ __global__ void __launch_bounds__(RR_WAVE) pairwise_eval_kernel(const float* __r
 
 // out = { sum over queries with npos > 0 of 1 - mism / (2 npos), number of those queries, sum of ce, sum of 2 npos }
 __global__ void __launch_bounds__(256) finish_eval_kernel(const double* __restrict__ qstats, int Q, double* __restrict__ out) {
-  __shared__ double red[4][256];
   double a[4] = {0.0, 0.0, 0.0, 0.0};
   for (int i = threadIdx.x; i < Q; i += 256) {
     const double* o = qstats + 4 * static_cast<int64_t>(i);
@@ -290,25 +275,19 @@ __global__ void __launch_bounds__(256) finish_eval_kernel(const double* __restri
       a[3] += 2.0 * o[0];
     }
   }
-  for (int u = 0; u < 4; ++u) red[u][threadIdx.x] = a[u];
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o)
-      for (int u = 0; u < 4; ++u) red[u][threadIdx.x] += red[u][threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) out[threadIdx.x] = red[threadIdx.x][0];
+  block_sum(a);
+  if (threadIdx.x == 0)
+    for (int u = 0; u < 4; ++u) out[u] = a[u];
 }
 
 // ---------------------------------------------------------------- baseline pair loop (train_pairwise.py:27-59, eval.py:246-266)
-constexpr int kPairBlock = 256;
+constexpr int kPairBlock = 256;   // block_sum's workgroup
 inline int pair_blocks(int64_t n) { return rr_grid_for(n, kPairBlock, 1024); }
 
 // loss = mean_b sum_k (softmax(t_b)_k - y_bk / (y_b0 + y_b1))^2
 __global__ void __launch_bounds__(kPairBlock) pair_mse_fwd_kernel(const float* __restrict__ y, int64_t ldy,
                                                                   const float* __restrict__ tg, int64_t ldt, int64_t B,
                                                                   double* __restrict__ partial) {
-  __shared__ double red[kPairBlock];
   double acc = 0.0;
   for (int64_t b = static_cast<int64_t>(blockIdx.x) * kPairBlock + threadIdx.x; b < B;
        b += static_cast<int64_t>(gridDim.x) * kPairBlock) {
@@ -317,27 +296,16 @@ __global__ void __launch_bounds__(kPairBlock) pair_mse_fwd_kernel(const float* _
     const double S = y0 + y1, e0 = tp0 - y0 / S, e1 = tp1 - y1 / S;
     acc += e0 * e0 + e1 * e1;
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = kPairBlock / 2; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 __global__ void __launch_bounds__(256) finish_scale_kernel(const double* __restrict__ partial, int n, double scale,
                                                            float* __restrict__ out) {
-  __shared__ double red[256];
   double acc = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = static_cast<float>(red[0] * scale);
+  acc = block_sum(acc);
+  if (threadIdx.x == 0) out[0] = static_cast<float>(acc * scale);
 }
 
 // d pp_k / d y_m = (delta_km - pp_k) / S
@@ -361,20 +329,14 @@ __global__ void __launch_bounds__(kPairBlock) pair_mse_bwd_kernel(const float* _
 // acc = 1 - sum_b |[y_b0 > y_b1] - [tp_b0 > tp_b1]| / B with tp = exp(t) / sum exp(t) in float32 as the reference forms it
 __global__ void __launch_bounds__(256) pair_acc_kernel(const float* __restrict__ y, int64_t ldy, const float* __restrict__ tg,
                                                        int64_t ldt, int64_t B, float* __restrict__ acc) {
-  __shared__ int red[256];
   int miss = 0;
   for (int64_t b = threadIdx.x; b < B; b += 256) {
     const float e0 = expf(tg[b * ldt]), e1 = expf(tg[b * ldt + 1]), es = e0 + e1;
     const bool tp = (e0 / es) > (e1 / es), pp = y[b * ldy] > y[b * ldy + 1];
     miss += (tp != pp) ? 1 : 0;
   }
-  red[threadIdx.x] = miss;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (static_cast<int>(threadIdx.x) < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) acc[0] = 1.0f - static_cast<float>(red[0]) / static_cast<float>(B);
+  miss = block_sum(miss);
+  if (threadIdx.x == 0) acc[0] = 1.0f - static_cast<float>(miss) / static_cast<float>(B);
 }
 
 // out[row] = h1[i1[row]] + h2[i2[row]] - 2 hr[ir[row]]; a null index array is the identity.  One 16-byte lane per 4 columns.
@@ -415,11 +377,8 @@ int rr_betanet_fwd_f32(const float* score, int64_t score_stride, const float* ta
                        int max_len, float alpha0, float* loss_sum, int64_t* pairs, double* partial, rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss_sum && pairs && partial && score_stride >= 1 &&
                alpha0 > 0.f);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(betanet_fwd_kernel, Q, L, kSqBytes, RR_WAVE, s, score, score_stride, targets, seg_off, L, alpha0,
-                                  partial);
+  const int st = launch_list(betanet_fwd_kernel, kSqBytes, score, score_stride, targets, seg_off, Q, max_len, s, alpha0, partial);
   return finish_sq(st, partial, seg_off, Q, loss_sum, pairs, s);
 }
 
@@ -428,21 +387,17 @@ int rr_betanet_bwd_f32(const float* score, int64_t score_stride, const float* ta
                        rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1 && alpha0 > 0.f);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(betanet_bwd_kernel, Q, L, kSqBytes, RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
-                          targets, seg_off, L, alpha0, gloss, dscore, dscore_stride);
+  return launch_list(betanet_bwd_kernel, kSqBytes, score, score_stride, targets, seg_off, Q, max_len,
+                     static_cast<hipStream_t>(stream), alpha0, gloss, dscore, dscore_stride);
 }
 
 int rr_beta_evidential_fwd_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off,
                                int Q, int max_len, float coef, float* loss_sum, int64_t* pairs, double* partial,
                                rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && loss_sum && pairs && partial && score_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(beta_evi_kernel<false>, Q, L, kSqBytes, RR_WAVE, s, score, score_stride, targets, seg_off, L, coef,
-                                  partial, nullptr, nullptr, 0);
+  const int st = launch_list(beta_evi_kernel<false>, kSqBytes, score, score_stride, targets, seg_off, Q, max_len, s, coef, partial,
+                             nullptr, nullptr, 0);
   return finish_sq(st, partial, seg_off, Q, loss_sum, pairs, s);
 }
 
@@ -451,20 +406,15 @@ int rr_beta_evidential_bwd_f32(const float* score, int64_t score_stride, const f
                                rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && gloss && dscore && score_stride >= 1 &&
                dscore_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
-  const int L = list_words(max_len);
-  return launch_per_query(beta_evi_kernel<true>, Q, L, kSqBytes, RR_WAVE, static_cast<hipStream_t>(stream), score, score_stride,
-                          targets, seg_off, L, coef, nullptr, gloss, dscore, dscore_stride);
+  return launch_list(beta_evi_kernel<true>, kSqBytes, score, score_stride, targets, seg_off, Q, max_len,
+                     static_cast<hipStream_t>(stream), coef, nullptr, gloss, dscore, dscore_stride);
 }
 
 int rr_pairwise_eval_f32(const float* score, int64_t score_stride, const float* targets, const int32_t* seg_off, int Q,
                          int max_len, float sigma, double* qstats, double* out, rr_stream_t stream) {
   RR_CHECK_ARG(list_args_ok(score, targets, seg_off, Q, max_len) && qstats && out && score_stride >= 1);
-  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int L = list_words(max_len);
-  const int st = launch_per_query(pairwise_eval_kernel, Q, L, 2 * sizeof(float), RR_WAVE, s, score, score_stride, targets, seg_off, L,
-                                  sigma, qstats);
+  const int st = launch_list(pairwise_eval_kernel, 2 * sizeof(float), score, score_stride, targets, seg_off, Q, max_len, s, sigma, qstats);
   if (st != RR_OK) return st;
   finish_eval_kernel<<<1, 256, 0, s>>>(qstats, Q, out);
   return rr_launch_status();

@@ -65,9 +65,9 @@ __global__ void __launch_bounds__(RR_WAVE) task_step_kernel(TaskArgs a) {
         const float mean = LT != RR_LIST_NONE ? x0[i] : a.out[r * a.ld_out];
         const float targ = LT != RR_LIST_NONE ? t[i] : a.targets[r];
         if constexpr (PT == RR_POINT_GAUSS) {
-          p = point_row<true>(mean, targ, a.out[r * a.ld_out + 1], a.inv_cands);   // the raw column 1 (GaussDisLoss takes its log)
+          p = point_row<kPointGauss>(mean, targ, a.out[r * a.ld_out + 1], a.inv_cands);   // the raw column 1 (GaussDisLoss takes its log)
         } else {
-          p = point_row<false>(mean, targ, 0.f, a.inv_cands);
+          p = point_row<kPointMse>(mean, targ, 0.f, a.inv_cands);
         }
         point_acc += p.value;
       }

@@ -1,9 +1,12 @@
 // Helpers of the per-list kernels - one wavefront per list (loss.hip, task_loss.hip, pairwise.hip, lambdarank.hip, uq.hip) or one
-// workgroup of one or four (approx_ndcg.hip, rank_corr.hip, calibration.hip): the list-length cap and wave-level synchronisation;
+// workgroup of one or four (approx_ndcg.hip, rank_corr.hip, calibration.hip): the list-length cap, wave-level synchronisation,
+// the plain staging of a list (stage_list) and the fixed-order sum of a 256-thread workgroup (block_sum), which every
+// partial-producing and finishing kernel of loss.hip and pairwise.hip goes through;
 // on the host side the dynamic-LDS opt-in, the argument check, the words per staged array (list_words, list_words4), the wave
-// knob of the one-or-four-wave kernels (WaveKnob), the blocks knob of the grid-strided embedding kernels (BlocksKnob) and the one
-// launch of a "one workgroup per query" kernel (launch_per_query, launch_per_query_bytes, launch_waves).  The wave reductions and
-// the ordering rule are in rr_common.h.  Everything lives in an unnamed namespace: each translation unit gets its own copy.
+// knob of the one-or-four-wave kernels (WaveKnob), the blocks knob of the grid-strided embedding kernels (BlocksKnob) and the
+// one launch of a "one workgroup per query" kernel (launch_per_query, launch_per_query_bytes, launch_list, launch_waves).
+// The wave reductions and the ordering rule are in rr_common.h.  Everything lives in an unnamed namespace: each translation
+// unit gets its own copy.
 #pragma once
 #include <atomic>
 
@@ -22,6 +25,47 @@ static_assert(kMaxLen <= 65536, "ranking_metrics_kernel keeps list positions in 
 __device__ inline void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+}
+
+// The fixed-order sum of a 256-thread workgroup, one value per thread and row: v[r] goes through shared memory as
+// red[t] += red[t + o] for o = 128, 64, ..., 1 with a barrier after each step, and comes back as the sum in thread 0 alone.
+// This order is a contract: fixed_sum (loss_list.h) replays it on one wave and the tests assert its bits, so it is not to be
+// replaced by wave shuffles.  Every thread of the workgroup must call it; rows are summed side by side in one tree.
+template <typename T, int ROWS>
+__device__ inline void block_sum(T (&v)[ROWS]) {
+  __shared__ T red[ROWS][256];
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r) red[r][t] = v[r];
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (t < o) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) red[r][t] += red[r][t + o];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) v[r] = red[r][0];
+  }
+}
+
+template <typename T>
+__device__ inline T block_sum(T v) {
+  T a[1] = {v};
+  block_sum(a);
+  return a[0];
+}
+
+// stages a query's strided score column and its targets into LDS as they are
+__device__ inline void stage_list(float* s, float* t, const float* __restrict__ score, int64_t sstride,
+                                  const float* __restrict__ targets, int off, int C, int lane) {
+  for (int i = lane; i < C; i += RR_WAVE) {
+    s[i] = score[static_cast<int64_t>(off + i) * sstride];
+    t[i] = targets[off + i];
+  }
+  wave_sync();
 }
 
 template <typename Kern>
@@ -85,6 +129,16 @@ int launch_per_query_bytes(Kern kern, int Q, size_t lds, int threads, hipStream_
 template <typename Kern, typename... Args>
 int launch_per_query(Kern kern, int Q, int L, size_t bytes_per_cand, int threads, hipStream_t s, Args... args) {
   return launch_per_query_bytes(kern, Q, static_cast<size_t>(L) * bytes_per_cand, threads, s, args...);
+}
+
+// The host body of a one-wave kernel that takes (score, sstride, targets, seg_off, L, rest...): the list-length cap, the words
+// per staged array and the launch
+template <typename Kern, typename... Rest>
+int launch_list(Kern kern, size_t bytes_per_cand, const float* score, int64_t sstride, const float* targets,
+                const int32_t* seg_off, int Q, int max_len, hipStream_t s, Rest... rest) {
+  if (max_len > kMaxLen) return RR_ERR_UNSUPPORTED;
+  const int L = list_words(max_len);
+  return launch_per_query(kern, Q, L, bytes_per_cand, RR_WAVE, s, score, sstride, targets, seg_off, L, rest...);
 }
 
 // The one-wave or the four-wave instantiation of a kernel, `waves` (1 or 4) wavefronts per query

@@ -510,15 +510,15 @@ def forward_only(kind, win):
 # bytes per candidate x the window's longest list and opts in above 65,536 bytes (csrc/wave_util.h: set_lds, once per launch);
 # forward and backward are counted apart, so neither kernel can stand in for the other.
 OPT_IN = {
-    "mle": ("mle", "mixed", False, 1, 1),                                  # 20 bytes: listmle_kernel forward, backward
+    "mle": ("mle", "mixed", False, 1, 1),                                  # 20 bytes: list_loss_kernel<kListMle> forward, backward
     "mle step": ("mle", "mixed", True, 1, 0),                              # ... and its one-launch form
     "mle 3277": ("mle", "at20", False, 1, 1),                              # 65,540 bytes: the first length of 20 bytes
     "mle 3276": ("mle", "below20", False, 0, 0),                           # 65,520
-    "evid": ("evid", "mixed", False, 1, 1),                                # 12 bytes x 5462 = 65,544: the first length
+    "evid": ("evid", "mixed", False, 1, 1),                                # <kUcListwise>: 12 bytes x 5462 = 65,544: the first length
     "evid step": ("evid", "mixed", True, 1, 0),
     "evid 5461": ("evid", "below12", False, 0, 0),                         # 65,532
     "ranknet": ("ranknet", "mixed", False, 0, 1),                          # 8 bytes forward, 12 backward
-    "mledis": ("mledis", "mixed", False, 1, 1),                            # listwise_variant_kernel<V>: 20,
+    "mledis": ("mledis", "mixed", False, 1, 1),                            # list_loss_kernel<K> of the variants: 20,
     "listnet_gauss": ("listnet_gauss", "mixed", False, 1, 1),              # 12,
     "listnet_lognorm": ("listnet_lognorm", "mixed", False, 1, 1),          # 12,
     "listnet_evidential": ("listnet_evidential", "mixed", False, 1, 1),    # 16 bytes

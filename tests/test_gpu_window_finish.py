@@ -3,7 +3,7 @@ rr_ranknet_fwd_f32, rr_lambdarank_fwd_f32 and rr_approx_ndcg_fwd_f32, and the la
 rr_lambdarank_step_f32 and rr_approx_ndcg_step_f32.  The entry points are called at the C ABI with the caller's own `partial`
 buffer [2 * Q] (the query's loss as a float, its count as an int32), which is read back after every call:
   - the loss has exactly the bits of reduce_scale_kernel's order over the float halves (256 strided accumulators, then the
-    halving tree), restated in numpy float32, times `scale` in float32;
+    halving tree of block_sum, csrc/wave_util.h), restated in numpy float32, times `scale` in float32;
   - the int64 count is the exact sum of the int32 halves;
   - step and fwd agree bit for bit, and the step leaves its ticket word at zero;
   - a window without queries gives +0.0f and 0.
@@ -43,7 +43,7 @@ def window(Q):
 
 def fixed_order_sum(v):
     """reduce_scale_kernel's sum of the float32 vector v: thread t adds v[t], v[t + 256], ... to 0.f in that order, then
-    red[t] += red[t + o] for o = 128, 64, ..., 1"""
+    block_sum's tree, red[t] += red[t + o] for o = 128, 64, ..., 1"""
     v = np.asarray(v, np.float32)
     pad = np.zeros((len(v) + 255) // 256 * 256, np.float32)        # (x + 0.f == x: an accumulator is never -0.f)
     pad[:len(v)] = v
