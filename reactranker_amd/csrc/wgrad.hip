@@ -48,6 +48,96 @@ __device__ __forceinline__ WgradWork wgrad_work(const WgradParams& P, int chunk)
   return w;
 }
 
+// The extended X of one row, written once: [ x1 (k1 columns, then dead pad columns up to k1p) | x2 (k2) | ones ], kext
+// columns.  wgrad_x_chunk is the 16-byte chunk that starts at extended column kx (kx % 4 == 0); wgrad_x_column is the
+// inverse for one column.  All three loaders and the slab store take the layout from these two.
+enum : int { X_NONE = 0, X_SEG1 = 1, X_SEG2 = 2, X_ONES = 3 };
+struct WgradXChunk {
+  int kind;             // X_NONE: dead pad columns or past kext, the chunk reads as zero
+  int col;              // first column inside the segment's source (x1 / x1_sub, or x2)
+  int nv;               // leading elements that come from the source; the others are zero ...
+  int one;              // ... except this one, the ones column (bias gradient); -1: not in this chunk
+};
+__device__ __forceinline__ WgradXChunk wgrad_x_chunk(const WgradParams& P, int kx) {
+  const rr_wgrad_args& a = P.a;
+  WgradXChunk c = {X_NONE, 0, 4, -1};
+  if (kx < a.k1) {
+    c.kind = X_SEG1; c.col = kx; c.nv = min(4, a.k1 - kx);
+  } else if (kx >= P.k1p && kx < P.kext) {
+    const int c2 = kx - P.k1p;
+    if (c2 < a.k2) {
+      c.kind = X_SEG2; c.col = c2; c.nv = min(4, a.k2 - c2);
+      if (a.k2 - c2 < 4) c.one = a.k2 - c2;             // the ones column shares this chunk (k2 % 4 != 0)
+    } else {
+      c.kind = X_ONES; c.nv = 0; c.one = 0;             // c2 == k2 (k2 % 4 == 0): the chunk is {1, 0, 0, 0}
+    }
+  }
+  return c;
+}
+// column of dw that extended column kx lands in; -1: dead pad column (or past kext), -2: the ones column (dbias)
+__device__ __forceinline__ int wgrad_x_column(const WgradParams& P, int kx) {
+  const rr_wgrad_args& a = P.a;
+  int col = -1;
+  if (kx < a.k1) col = kx;
+  else if (kx >= P.k1p && kx < P.k1p + a.k2) col = a.k1 + (kx - P.k1p);
+  else if (kx == P.k1p + a.k2) col = -2;
+  return col;
+}
+
+// Row m of a direct operand, or row j = idx[m] of a gathered one; a negative index is "no row" (nullptr: reads as zero).
+__device__ __forceinline__ const float* wgrad_row(const float* base, int64_t ld, int64_t m, bool gathered, int32_t j) {
+  if (!gathered) return base + m * ld;
+  return j >= 0 ? base + static_cast<int64_t>(j) * ld : nullptr;
+}
+
+// A partial chunk of the extended X, element by element: the first nv elements are x (- the subtract source), the ones
+// element is 1 in a row inside the M-chunk, everything else 0.
+template <bool HAS_SUB>
+__device__ __forceinline__ f32x4 wgrad_patch_x(f32x4 xv, f32x4 xs, int nv, int one, bool row_ok) {
+  f32x4 x;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float u = e < nv ? xv[e] : 0.f;
+    if (HAS_SUB) u -= e < nv ? xs[e] : 0.f;
+    if (e == one) u = row_ok ? 1.0f : 0.f;
+    x[e] = u;
+  }
+  return x;
+}
+
+template <int NJ>
+__device__ __forceinline__ void wgrad_zero_acc(f32x4 (&acc)[WT][NJ]) {
+#pragma unroll
+  for (int i = 0; i < WT; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4(0.f);
+}
+
+// A wave's WT x NJ accumulator tiles into the partial slab [chunk][ N*K (dw, row-major) | N (dbias) ]; (nb + wn, kb + wk) is the
+// wave's corner in (n, extended k).  D[i = n][j = k]: lane -> n = .. + fq*4 + e, k = .. + fr
+template <int NJ>
+__device__ __forceinline__ void wgrad_store_slab(const WgradParams& P, int chunk, int nb, int kb, int wn, int wk, int fr, int fq,
+                                                 const f32x4 (&acc)[WT][NJ]) {
+  const rr_wgrad_args& a = P.a;
+  const int K = a.k1 + a.k2;
+  float* slab = static_cast<float*>(a.workspace) + static_cast<int64_t>(chunk) * P.slab;
+#pragma unroll
+  for (int i = 0; i < WT; ++i) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int kreal = wgrad_x_column(P, kb + wk + j * 16 + fr);
+      if (kreal == -1) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int n = nb + wn + i * 16 + fq * 4 + e;
+        if (n >= a.N) continue;
+        if (kreal >= 0) slab[static_cast<int64_t>(n) * K + kreal] = acc[i][j][e];
+        else slab[static_cast<int64_t>(a.N) * K + n] = acc[i][j][e];
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
   __shared__ __attribute__((aligned(16))) float lds[2][2 * WMT * WLD];
   const rr_wgrad_args& a = P.a;
@@ -58,7 +148,6 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
   const int nb = w.nb, kb = w.kb;
   const int64_t mbeg = w.mbeg, mend = w.mend;
   const int flags = P.flags;
-  const int K = a.k1 + a.k2;
 
   // staging: 2 tiles x 16 rows x 40 float4 = 1280 chunks, 5 per thread
   auto load_chunk_z = [&](int64_t mrow, int col) -> f32x4 {       // dZ[mrow][nb+col .. +3]
@@ -71,34 +160,19 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
   };
   auto load_chunk_x = [&](int64_t mrow, int col) -> f32x4 {       // X_ext[mrow][kb+col .. +3]
     f32x4 v = f32x4(0.f);
-    const int k = kb + col;
-    if (mrow >= mend || k >= P.kext) return v;
-    if (k < P.k1p) {
-      const float* p = nullptr;
-      if (a.x1_idx) {
-        const int32_t j = a.x1_idx[mrow];
-        if (j >= 0) p = a.x1 + static_cast<int64_t>(j) * a.ldx1;
-      } else {
-        p = a.x1 + mrow * a.ldx1;
-      }
-      v = load_chunk(p, k, a.k1, flags & F_A1_VEC);
+    const WgradXChunk c = wgrad_x_chunk(P, kb + col);
+    if (mrow >= mend || c.kind == X_NONE) return v;
+    if (c.kind == X_SEG1) {
+      const float* p = wgrad_row(a.x1, a.ldx1, mrow, a.x1_idx != nullptr, a.x1_idx ? a.x1_idx[mrow] : 0);
+      v = load_chunk(p, c.col, a.k1, flags & F_A1_VEC);
       if (a.x1_sub) {
-        const float* sp = nullptr;
-        if (a.x1_sub_idx) {
-          const int32_t j = a.x1_sub_idx[mrow];
-          if (j >= 0) sp = a.x1_sub + static_cast<int64_t>(j) * a.ldx1_sub;
-        } else {
-          sp = a.x1_sub + mrow * a.ldx1_sub;
-        }
-        v = v - load_chunk(sp, k, a.k1, flags & F_SUB_VEC);
+        const float* sp = wgrad_row(a.x1_sub, a.ldx1_sub, mrow, a.x1_sub_idx != nullptr, a.x1_sub_idx ? a.x1_sub_idx[mrow] : 0);
+        v = v - load_chunk(sp, c.col, a.k1, flags & F_SUB_VEC);
       }
-    } else {
-      const int k2 = k - P.k1p;
-      if (a.k2 > 0) v = load_chunk(a.x2 + mrow * a.ldx2, k2, a.k2, flags & F_A2_VEC);
-      // the ones column (bias gradient) sits right after segment 2
-      const int one = a.k2 - k2;                 // position of the ones column inside this chunk
-      if (one >= 0 && one < 4) v[one] = 1.0f;
+    } else if (c.kind == X_SEG2) {
+      v = load_chunk(a.x2 + mrow * a.ldx2, c.col, a.k2, flags & F_A2_VEC);
     }
+    if (c.one >= 0) v[c.one] = 1.0f;             // the ones column (bias gradient) sits right after segment 2
     return v;
   };
   constexpr int CH = 5;
@@ -124,10 +198,7 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
   };
 
   f32x4 acc[WT][WT];
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int j = 0; j < WT; ++j) acc[i][j] = f32x4(0.f);
+  wgrad_zero_acc(acc);
 
   const int wn = (wave >> 1) * (WT * 16), wk = (wave & 1) * (WT * 16);   // wave's corner inside the 160x160 tile
   const int fr = lane & 15, fq = lane >> 4;
@@ -164,30 +235,8 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
     __syncthreads();
   }
 
-  // partial slab [chunk][ N*K (dw, row-major) | N (dbias) ]; D[i = n][j = k]: lane -> n = .. + fq*4 + e, k = .. + fr
-  float* slab = static_cast<float*>(a.workspace) + static_cast<int64_t>(chunk) * P.slab;
-#pragma unroll
-  for (int i = 0; i < WT; ++i) {
-#pragma unroll
-    for (int j = 0; j < WT; ++j) {
-      const int kx = kb + wk + j * 16 + fr;       // extended column
-      if (kx >= P.kext) continue;
-      int kreal = -1;                             // -1: dead pad column, -2: ones column
-      if (kx < a.k1) kreal = kx;
-      else if (kx >= P.k1p && kx < P.k1p + a.k2) kreal = a.k1 + (kx - P.k1p);
-      else if (kx == P.k1p + a.k2) kreal = -2;
-      if (kreal == -1) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int n = nb + wn + i * 16 + fq * 4 + e;
-        if (n >= a.N) continue;
-        if (kreal >= 0) slab[static_cast<int64_t>(n) * K + kreal] = acc[i][j][e];
-        else slab[static_cast<int64_t>(a.N) * K + n] = acc[i][j][e];
-      }
-    }
-  }
+  wgrad_store_slab(P, chunk, nb, kb, wn, wk, fr, fq, acc);
 }
-
 
 // ------------------------------------------------------------------------ wgrad fast path
 // Hot case: every operand 16-byte addressable, N % 4 == 0.  A 16-row tile is 640 dZ chunks +
@@ -209,6 +258,16 @@ __global__ void __launch_bounds__(THREADS) wgrad_kernel(const WgradParams P) {
 // What remains per tile: the loads, the pointer bumps, the ReLU-mask select and the subtraction.
 __device__ __attribute__((aligned(16))) const float rr_one_chunk[4] = {1.f, 0.f, 0.f, 0.f};
 
+#ifdef RR_TRACE_LOOP                  // per-tile stamps of wgrad_fast_kernel's loop (t: the tile), next to its RR_STAMPs
+#define RR_LSTAMP(q)                                                                                      \
+    do {                                                                                                   \
+      if (rr_trace_buf && (threadIdx.x & 63) == 0 && blockIdx.x < 2 && t < 48)                             \
+        rr_trace_buf[4096 * 8 + ((blockIdx.x * 4 + (threadIdx.x >> 6)) * 48 + t) * 8 + (q)] = __builtin_amdgcn_s_memtime(); \
+    } while (0)
+#else
+#define RR_LSTAMP(q)
+#endif
+
 template <bool HAS_MASK, bool HAS_SUB, int WTK>
 __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParams P) {
   constexpr int KB = 32 * WTK;                          // columns per k-block (160 / 128 / 96)
@@ -223,15 +282,13 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParam
   const WgradWork w = wgrad_work<KB>(P, chunk);
   const int nb = w.nb, kb = w.kb;
   const int64_t mbeg = w.mbeg, mend = w.mend;
-  const int K = a.k1 + a.k2;
   const int nrows = static_cast<int>(mend - mbeg);      // rows of this M-chunk (> 0: chunk < nchunks)
   const int ntiles = (nrows + WMT - 1) / WMT;
   const float* const zero = rr_zero_chunk;
   const bool partial = (a.k1 & 3) != 0 || (a.k2 & 3) != 0;
 
   // ---- slot roles (loop invariant)
-  enum : int { X_NONE = 0, X_DIRECT = 1, X_GATHER = 2, X_ONES = 3 };
-  int zrow[S], zoff[S], xrow[S], xoff[S], xkind[S], nval[S], onee[S];
+  int zrow[S], zoff[S], xrow[S], xoff[S], nval[S], onee[S];
   const float* pz[S];                                   // dZ chunk of this slot in the current tile (advances)
   const float* pm[S];                                   // ReLU-mask chunk
   const float* px[S];                                   // X chunk (direct) or column pointer into row 0 (gather)
@@ -263,48 +320,37 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParam
     xrow[i] = xuse ? g / XC : 0;
     const int xc0 = xuse ? (g - xrow[i] * XC) * 4 : 0;
     xoff[i] = (xuse ? WMT * WLD + xrow[i] * WLD + xc0 : 2 * WMT * WLD) / 4;
-    const int kx = kb + xc0;                            // extended column of the chunk
-    xkind[i] = X_NONE;
+    const WgradXChunk c = wgrad_x_chunk(P, kb + xc0);   // the slot's chunk of the extended X
+    const int kind = xuse ? c.kind : X_NONE;
     px[i] = zero; ps[i] = zero; xstep[i] = 0; sstep[i] = 0; sgather[i] = false;
     pi[i] = reinterpret_cast<const int32_t*>(rr_zero_chunk); pj[i] = pi[i];   // non-gather slots read index 0
     gi[i] = 0; gj[i] = 0;
-    nval[i] = 4; onee[i] = -1;
-    if (xuse && kx < a.k1) {                            // segment 1
-      nval[i] = min(4, a.k1 - kx);
+    nval[i] = xuse ? c.nv : 4; onee[i] = xuse ? c.one : -1;
+    if (kind == X_SEG1) {
       if (a.x1_idx) {
-        xkind[i] = X_GATHER;
-        px[i] = a.x1 + kx;
+        px[i] = a.x1 + c.col;
         pi[i] = a.x1_idx + mbeg + xrow[i];
         gi[i] = -1;
       } else {
-        xkind[i] = X_DIRECT;
-        px[i] = a.x1 + (mbeg + xrow[i]) * a.ldx1 + kx;
+        px[i] = a.x1 + (mbeg + xrow[i]) * a.ldx1 + c.col;
         xstep[i] = static_cast<uint32_t>(WMT * 4 * a.ldx1);
       }
       if (HAS_SUB) {
         if (a.x1_sub_idx) {
           sgather[i] = true;
-          ps[i] = a.x1_sub + kx;
+          ps[i] = a.x1_sub + c.col;
           pj[i] = a.x1_sub_idx + mbeg + xrow[i];
           gj[i] = -1;
         } else {
-          ps[i] = a.x1_sub + (mbeg + xrow[i]) * a.ldx1_sub + kx;
+          ps[i] = a.x1_sub + (mbeg + xrow[i]) * a.ldx1_sub + c.col;
           sstep[i] = static_cast<uint32_t>(WMT * 4 * a.ldx1_sub);
         }
       }
-    } else if (xuse && kx >= P.k1p && kx < P.kext) {    // segment 2 and / or the ones column
-      const int c2 = kx - P.k1p;
-      if (c2 < a.k2) {
-        xkind[i] = X_DIRECT;
-        px[i] = a.x2 + (mbeg + xrow[i]) * a.ldx2 + c2;
-        xstep[i] = static_cast<uint32_t>(WMT * 4 * a.ldx2);
-        nval[i] = min(4, a.k2 - c2);
-        if (a.k2 - c2 < 4) onee[i] = a.k2 - c2;         // ones column shares this chunk (k2 % 4 != 0)
-      } else {                                          // c2 == k2 (k2 % 4 == 0): the chunk is {1, 0, 0, 0}
-        xkind[i] = X_ONES;
-        px[i] = rr_one_chunk;
-        nval[i] = 0; onee[i] = 0;
-      }
+    } else if (kind == X_SEG2) {
+      px[i] = a.x2 + (mbeg + xrow[i]) * a.ldx2 + c.col;
+      xstep[i] = static_cast<uint32_t>(WMT * 4 * a.ldx2);
+    } else if (kind == X_ONES) {
+      px[i] = rr_one_chunk;
     }
   }
 
@@ -349,36 +395,17 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParam
   auto commit = [&](int buf) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < S; ++i) {
-      {
-        f32x4 z = zv[i];
-        if (HAS_MASK) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) z[e] = zm[i][e] > 0.f ? zv[i][e] * a.mask_scale : 0.f;
-        }
-        reinterpret_cast<f32x4*>(lds[buf])[zoff[i]] = z;
-      }
-      {
-        f32x4 x = xv[i];
-        if (HAS_SUB) x = xv[i] - xs[i];
-        if (partial) {                                  // k1 % 4 or k2 % 4 != 0: patch the chunk per element
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            float u = e < nval[i] ? xv[i][e] : 0.f;
-            if (HAS_SUB) u -= e < nval[i] ? xs[i][e] : 0.f;
-            if (e == onee[i]) u = xrv[i] ? 1.0f : 0.f;
-            x[e] = u;
-          }
-        }
-        reinterpret_cast<f32x4*>(lds[buf])[xoff[i]] = x;
-      }
+      reinterpret_cast<f32x4*>(lds[buf])[zoff[i]] = HAS_MASK ? apply_mask(zv[i], zm[i], a.mask_scale) : zv[i];
+      f32x4 x = xv[i];
+      if (HAS_SUB) x = xv[i] - xs[i];
+      // k1 % 4 or k2 % 4 != 0: patch the chunk per element
+      if (partial) x = wgrad_patch_x<HAS_SUB>(xv[i], HAS_SUB ? xs[i] : xv[i], nval[i], onee[i], xrv[i]);
+      reinterpret_cast<f32x4*>(lds[buf])[xoff[i]] = x;
     }
   };
 
   f32x4 acc[WT][WTK];
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int j = 0; j < WTK; ++j) acc[i][j] = f32x4(0.f);
+  wgrad_zero_acc(acc);
 
   const int wn = (wave >> 1) * (WT * 16), wk = (wave & 1) * (WTK * 16);
   const int fr = lane & 15, fq = lane >> 4;
@@ -392,15 +419,6 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParam
   for (int t = 0; t < ntiles; ++t) {
     const int cur = t & 1;
     const bool more = t + 1 < ntiles;
-#ifdef RR_TRACE_LOOP
-#define RR_LSTAMP(q)                                                                                      \
-    do {                                                                                                   \
-      if (rr_trace_buf && (threadIdx.x & 63) == 0 && blockIdx.x < 2 && t < 48)                             \
-        rr_trace_buf[4096 * 8 + ((blockIdx.x * 4 + (threadIdx.x >> 6)) * 48 + t) * 8 + (q)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define RR_LSTAMP(q)
-#endif
     RR_LSTAMP(0);
     if (more) {
       const int left = nrows - (t + 1) * WMT;           // rows of tile t+1 (uses the indices fetched one tile ago)
@@ -436,27 +454,7 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_fast_kernel(const WgradParam
   }
 
   RR_STAMP(2);
-  float* slab = static_cast<float*>(a.workspace) + static_cast<int64_t>(chunk) * P.slab;
-#pragma unroll
-  for (int i = 0; i < WT; ++i) {
-#pragma unroll
-    for (int j = 0; j < WTK; ++j) {
-      const int kx = kb + wk + j * 16 + fr;
-      if (kx >= P.kext) continue;
-      int kreal = -1;
-      if (kx < a.k1) kreal = kx;
-      else if (kx >= P.k1p && kx < P.k1p + a.k2) kreal = a.k1 + (kx - P.k1p);
-      else if (kx == P.k1p + a.k2) kreal = -2;
-      if (kreal == -1) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int n = nb + wn + i * 16 + fq * 4 + e;
-        if (n >= a.N) continue;
-        if (kreal >= 0) slab[static_cast<int64_t>(n) * K + kreal] = acc[i][j][e];
-        else slab[static_cast<int64_t>(a.N) * K + n] = acc[i][j][e];
-      }
-    }
-  }
+  wgrad_store_slab(P, chunk, nb, kb, wn, wk, fr, fq, acc);
 #ifdef RR_TRACE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   RR_STAMP(3);
@@ -484,6 +482,25 @@ __device__ __forceinline__ u32x4 tr_read8(const unsigned char* p, int rowbytes) 
   r.x = __builtin_bit_cast(uint2, lo).x; r.y = __builtin_bit_cast(uint2, lo).y;
   r.z = __builtin_bit_cast(uint2, hi).x; r.w = __builtin_bit_cast(uint2, hi).y;
   return r;
+}
+
+// c += z * x over the term images of one 16x16 tile and 32 rows of M (z[0] / x[0]: the leading terms), smallest terms first:
+// the six products of three bf16 terms, or the three of two f16 terms
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma_terms(const u32x4 (&z)[F16 ? 2 : 3], const u32x4 (&x)[F16 ? 2 : 3], f32x4 c) {
+  if constexpr (F16) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(z[1]), as_f16x8(x[0]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(z[0]), as_f16x8(x[1]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_f16x8(z[0]), as_f16x8(x[0]), c, 0, 0, 0);
+  } else {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[2]), as_bf16x8(x[0]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[1]), as_bf16x8(x[1]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[0]), as_bf16x8(x[2]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[1]), as_bf16x8(x[0]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[0]), as_bf16x8(x[1]), c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(z[0]), as_bf16x8(x[0]), c, 0, 0, 0);
+  }
+  return c;
 }
 
 constexpr int SMT = 32;             // rows of M per staged tile on the split path
@@ -515,7 +532,6 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
   const WgradWork w = wgrad_work<KB>(P, chunk);
   const int nb = w.nb, kb = w.kb;
   const int64_t mbeg = w.mbeg, mend = w.mend;
-  const int K = a.k1 + a.k2;
   const int nrows = static_cast<int>(mend - mbeg);
   const int ntiles = (nrows + SMT - 1) / SMT;
   const float* const zero = rr_zero_chunk;
@@ -523,7 +539,6 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
   // ---- loader role: row r of the tile, chunks g + 8 i
   const int r = tid >> 3, g = tid & 7;
   const int xr = ((r >> 3) & 1) << 5;                   // column-block swap of this row in the images
-  enum : int { X_NONE = 0, X_SEG1 = 1, X_SEG2 = 2, X_ONES = 3 };
   bool zok[5];
   int xcode[WTK];                                       // per chunk: column | kind << 16 | valid elements << 18 | (ones element + 1) << 21
   bool partial = false;
@@ -531,21 +546,9 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
   for (int i = 0; i < 5; ++i) zok[i] = nb + 4 * (g + 8 * i) < a.N;
 #pragma unroll
   for (int i = 0; i < WTK; ++i) {
-    const int kx = kb + 4 * (g + 8 * i);                // extended column of the chunk
-    int kind = X_NONE, col = 0, nv = 4, one = -1;
-    if (kx < a.k1) {
-      kind = X_SEG1; col = kx; nv = min(4, a.k1 - kx);
-    } else if (kx >= P.k1p && kx < P.kext) {
-      const int c2 = kx - P.k1p;
-      if (c2 < a.k2) {
-        kind = X_SEG2; col = c2; nv = min(4, a.k2 - c2);
-        if (a.k2 - c2 < 4) one = a.k2 - c2;             // the ones column shares this chunk (k2 % 4 != 0)
-      } else {
-        kind = X_ONES; nv = 0; one = 0;                 // c2 == k2: the chunk is {1, 0, 0, 0}
-      }
-    }
-    if (nv != 4 || one >= 0) partial = true;
-    xcode[i] = col | (kind << 16) | (nv << 18) | ((one + 1) << 21);
+    const WgradXChunk c = wgrad_x_chunk(P, kb + 4 * (g + 8 * i));
+    if (c.nv != 4 || c.one >= 0) partial = true;
+    xcode[i] = c.col | (c.kind << 16) | (c.nv << 18) | ((c.one + 1) << 21);
   }
   partial = __any(partial);
 
@@ -572,18 +575,8 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
     const float* p1 = nullptr;
     const float* ps = nullptr;
     if (a.k1 > 0) {
-      if (a.x1_idx) {
-        if (ia >= 0) p1 = a.x1 + static_cast<int64_t>(ia) * a.ldx1;
-      } else {
-        p1 = a.x1 + m * a.ldx1;
-      }
-      if (HAS_SUB) {
-        if (a.x1_sub_idx) {
-          if (is >= 0) ps = a.x1_sub + static_cast<int64_t>(is) * a.ldx1_sub;
-        } else {
-          ps = a.x1_sub + m * a.ldx1_sub;
-        }
-      }
+      p1 = wgrad_row(a.x1, a.ldx1, m, a.x1_idx != nullptr, ia);
+      if (HAS_SUB) ps = wgrad_row(a.x1_sub, a.ldx1_sub, m, a.x1_sub_idx != nullptr, is);
     }
     const float* p2 = a.k2 > 0 ? a.x2 + m * a.ldx2 : nullptr;
 #pragma unroll
@@ -594,56 +587,34 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
       if (HAS_SUB) xs[i] = ldg4((m_ok && ps != nullptr && kind == X_SEG1) ? ps + col : zero);
     }
   };
-  auto put = [&](unsigned char* img, int imgbytes, int rowbytes, int chunk8, f32x4 v, float sc) {   // split + three 8-byte stores
-    uint32_t a0, a1, a2, b0, b1, b2;
-    if (F16) {
-      split_pair_h(v.x, v.y, sc, a0, a1);
-      split_pair_h(v.z, v.w, sc, b0, b1);
-      unsigned char* d = img + r * rowbytes + ((chunk8 * 8) ^ xr);
-      *reinterpret_cast<uint2*>(d) = make_uint2(a0, b0);
-      *reinterpret_cast<uint2*>(d + imgbytes) = make_uint2(a1, b1);
-      return;
+  auto put = [&](unsigned char* img, int imgbytes, int rowbytes, int chunk8, f32x4 v, float sc) {   // split + one 8-byte store per term
+    uint32_t lo[3], hi[3];
+    if constexpr (F16) {
+      split_pair_h(v.x, v.y, sc, lo[0], lo[1]);
+      split_pair_h(v.z, v.w, sc, hi[0], hi[1]);
+    } else {
+      split_pair(v.x, v.y, lo[0], lo[1], lo[2]);
+      split_pair(v.z, v.w, hi[0], hi[1], hi[2]);
     }
-    split_pair(v.x, v.y, a0, a1, a2);
-    split_pair(v.z, v.w, b0, b1, b2);
     unsigned char* d = img + r * rowbytes + ((chunk8 * 8) ^ xr);
-    *reinterpret_cast<uint2*>(d) = make_uint2(a0, b0);
-    *reinterpret_cast<uint2*>(d + imgbytes) = make_uint2(a1, b1);
-    *reinterpret_cast<uint2*>(d + 2 * imgbytes) = make_uint2(a2, b2);
+#pragma unroll
+    for (int k = 0; k < TERMS; ++k) *reinterpret_cast<uint2*>(d + k * imgbytes) = make_uint2(lo[k], hi[k]);
   };
   auto commit = [&]() {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      f32x4 z = zv[i];
-      if (HAS_MASK) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) z[e] = zm[i][e] > 0.f ? zv[i][e] * a.mask_scale : 0.f;
-      }
-      put(lds, ZIMG, ZRB, g + 8 * i, z, zs);
-    }
+    for (int i = 0; i < 5; ++i) put(lds, ZIMG, ZRB, g + 8 * i, HAS_MASK ? apply_mask(zv[i], zm[i], a.mask_scale) : zv[i], zs);
 #pragma unroll
     for (int i = 0; i < WTK; ++i) {
       f32x4 x = xv[i];
       if (HAS_SUB) x = xv[i] - xs[i];
-      if (partial) {                                    // k1 % 4 or k2 % 4 != 0, or the ones column: patch per element
-        const int nv = (xcode[i] >> 18) & 7, one = ((xcode[i] >> 21) & 7) - 1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          float u = e < nv ? xv[i][e] : 0.f;
-          if (HAS_SUB) u -= e < nv ? xs[i][e] : 0.f;
-          if (e == one) u = m_ok ? 1.0f : 0.f;
-          x[e] = u;
-        }
-      }
+      // k1 % 4 or k2 % 4 != 0, or the ones column: patch per element
+      if (partial) x = wgrad_patch_x<HAS_SUB>(xv[i], HAS_SUB ? xs[i] : xv[i], (xcode[i] >> 18) & 7, ((xcode[i] >> 21) & 7) - 1, m_ok);
       put(lds + TERMS * ZIMG, XIMG, XRB, g + 8 * i, x, xsc);
     }
   };
 
   f32x4 acc[WT][WTK];
-#pragma unroll
-  for (int i = 0; i < WT; ++i)
-#pragma unroll
-    for (int j = 0; j < WTK; ++j) acc[i][j] = f32x4(0.f);
+  wgrad_zero_acc(acc);
 
   const int wn = (wave >> 1) * (WT * 16), wk = (wave & 1) * (WTK * 16);
   const int fr = lane & 15, fq = lane >> 4;
@@ -671,95 +642,36 @@ __global__ void __launch_bounds__(THREADS, 2) wgrad_split_kernel(const WgradPara
 #pragma unroll
     for (int j0 = 0; j0 < WTK; j0 += JH) {
       asm volatile("" ::: "memory");                    // the second group RE-READS the dZ terms (no CSE across groups)
-      if constexpr (F16) {
-        f16x8 h0[JH], h1[JH];
-#pragma unroll
-        for (int jj = 0; jj < JH; ++jj) {
-          if (j0 + jj < WTK) {
-            const int xc = ((wk + 16 * (j0 + jj)) * 2) ^ txr;
-            h0[jj] = as_f16x8(tr_read8(xbase + xc, XRB));
-            h1[jj] = as_f16x8(tr_read8(xbase + XIMG + xc, XRB));
-          }
-        }
-#pragma unroll
-        for (int i = 0; i < WT; ++i) {
-          const int zc = ((wn + 16 * i) * 2) ^ txr;
-          const f16x8 a0 = as_f16x8(tr_read8(zbase + zc, ZRB));
-          const f16x8 a1 = as_f16x8(tr_read8(zbase + ZIMG + zc, ZRB));
-#pragma unroll
-          for (int jj = 0; jj < JH; ++jj) {
-            if (j0 + jj < WTK) {
-              f32x4 c = acc[i][j0 + jj];
-              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, h0[jj], c, 0, 0, 0);   // smallest terms first
-              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, h1[jj], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, h0[jj], c, 0, 0, 0);
-              acc[i][j0 + jj] = c;
-            }
-          }
-        }
-        continue;
-      }
-      bf16x8 b0[JH], b1[JH], b2[JH];
+      u32x4 xt[JH][TERMS];
 #pragma unroll
       for (int jj = 0; jj < JH; ++jj) {
         if (j0 + jj < WTK) {
           const int xc = ((wk + 16 * (j0 + jj)) * 2) ^ txr;
-          b0[jj] = as_bf16x8(tr_read8(xbase + xc, XRB));
-          b1[jj] = as_bf16x8(tr_read8(xbase + XIMG + xc, XRB));
-          b2[jj] = as_bf16x8(tr_read8(xbase + 2 * XIMG + xc, XRB));
+#pragma unroll
+          for (int k = 0; k < TERMS; ++k) xt[jj][k] = tr_read8(xbase + k * XIMG + xc, XRB);
         }
       }
 #pragma unroll
       for (int i = 0; i < WT; ++i) {
         const int zc = ((wn + 16 * i) * 2) ^ txr;
-        const bf16x8 a0 = as_bf16x8(tr_read8(zbase + zc, ZRB));
-        const bf16x8 a1 = as_bf16x8(tr_read8(zbase + ZIMG + zc, ZRB));
-        const bf16x8 a2 = as_bf16x8(tr_read8(zbase + 2 * ZIMG + zc, ZRB));
+        u32x4 zt[TERMS];
 #pragma unroll
-        for (int jj = 0; jj < JH; ++jj) {
-          if (j0 + jj < WTK) {
-            f32x4 c = acc[i][j0 + jj];
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, b0[jj], c, 0, 0, 0);   // smallest terms first
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1[jj], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b2[jj], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b0[jj], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b1[jj], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0[jj], c, 0, 0, 0);
-            acc[i][j0 + jj] = c;
-          }
-        }
+        for (int k = 0; k < TERMS; ++k) zt[k] = tr_read8(zbase + k * ZIMG + zc, ZRB);
+#pragma unroll
+        for (int jj = 0; jj < JH; ++jj)
+          if (j0 + jj < WTK) acc[i][j0 + jj] = mfma_terms<F16>(zt, xt[jj], acc[i][j0 + jj]);
       }
     }
     __syncthreads();                                    // every wave is done with the images before the next commit
   }
 
-  float* slab = static_cast<float*>(a.workspace) + static_cast<int64_t>(chunk) * P.slab;
   if (F16) {                                            // back from the scaled operands (two exact powers of two)
 #pragma unroll
     for (int i = 0; i < WT; ++i)
 #pragma unroll
       for (int j = 0; j < WTK; ++j) acc[i][j] = (acc[i][j] * izs) * ixs;
   }
-#pragma unroll
-  for (int i = 0; i < WT; ++i) {
-#pragma unroll
-    for (int j = 0; j < WTK; ++j) {
-      const int kx = kb + wk + j * 16 + fr;
-      if (kx >= P.kext) continue;
-      int kreal = -1;
-      if (kx < a.k1) kreal = kx;
-      else if (kx >= P.k1p && kx < P.k1p + a.k2) kreal = a.k1 + (kx - P.k1p);
-      else if (kx == P.k1p + a.k2) kreal = -2;
-      if (kreal == -1) continue;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int n = nb + wn + i * 16 + fq * 4 + e;
-        if (n >= a.N) continue;
-        if (kreal >= 0) slab[static_cast<int64_t>(n) * K + kreal] = acc[i][j][e];
-        else slab[static_cast<int64_t>(a.N) * K + n] = acc[i][j][e];
-      }
-    }
-  }
+  wgrad_store_slab(P, chunk, nb, kb, wn, wk, fr, fq, acc);
 }
 
 // fixed-order sum of the chunk slabs into dw / dbias.  64 elements per workgroup; the chunk range is cut in four
