@@ -51,6 +51,17 @@ together, by sphere exclusion (clusters.sphere_exclusion; RADIUS 0: clusters.sug
 and sizes, sends whole clusters to train / validation / test folds (clusters.cluster_split) and prints, per held-out fold, the
 quantiles of the distance to the nearest training query (clusters.split_report) next to a random split of the same fold sizes.
 
+--fingerprint-neighbors K (listwise task types, one process) asks "has training seen this reaction?" of the structure instead of
+the model: circular fingerprints of reactant and product, side by side, for every training and validation reaction
+(fingerprints.reaction_fingerprint, mode='concat'), the K nearest training reactions of every validation reaction under the
+Tanimoto distance (fingerprints.tanimoto_knn) and the validation reactions whose fingerprint a training reaction shares
+(fingerprints.structure_overlap); it logs the mean structural nearest-neighbour similarity next to the mean latent distance
+(neighbors.latent_distance) and the Spearman correlation of the two over the validation reactions.
+
+--add-fingerprint [--fingerprint-bits N] (listwise task types, one process) trains with add_features_dim = N: the product's
+binary circular fingerprint (fingerprints.feature_generate, made on the device, N bits, default 2048) takes the place of the
+synthetic extra feature.
+
 --bootstrap N (listwise task types, one process) prints the validation metrics of the restored best checkpoint with their 95 %
 bootstrap intervals over the validation queries (significance.metric_intervals, N resamples), and the paired comparison of that
 checkpoint against the last epoch's weights on the same queries: the difference per metric, its interval and the two-sided
@@ -67,7 +78,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from reactranker_amd import featurization, synth                      # noqa: E402
 from reactranker_amd.base_model import build_model                    # noqa: E402
-from reactranker_amd import attribution, clusters, latent_gaussian, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
+from reactranker_amd import attribution, clusters, fingerprints, latent_gaussian, neighbors, ranknet_baseline, significance, uncertainty   # noqa: E402
 from reactranker_amd.run_train_pairwise import run_train              # noqa: E402
 from reactranker_amd.train_listwise import train                      # noqa: E402
 from reactranker_amd.train_utils import build_lr_scheduler, build_optimizer, param_count   # noqa: E402
@@ -141,6 +152,28 @@ def nearest_training_reactions(model, train_b, val_b, checkpoint, k, gpu, log):
     for c in range(n0):
         near = ", ".join(f"#{int(i)} (d {float(d):.4f}, target {float(t):+.3f})" for d, i, t in zip(dist[c], idx[c], tgt[c]))
         log.info("  query 0 candidate %2d (target %+.3f): %s", c, float(b["targets"][c]), near)
+
+
+def structural_neighbours(model, train_b, val_b, k, gpu, log):
+    """How close the validation reactions lie to the training ones by structure (Tanimoto on circular fingerprints) and by the
+    model's embedding, side by side."""
+    as_tuple = lambda b: (b["r"], b["p"], b["scope"], b["targets"], b["add"])          # noqa: E731
+    fp = lambda bs: torch.cat([fingerprints.reaction_fingerprint(b["r"], b["p"], mode="concat", gpu=gpu) for b in bs])   # noqa: E731
+    bank_bits, val_bits = fp(train_b), fp(val_b)
+    dist, idx = fingerprints.tanimoto_knn(val_bits, bank_bits, k, bank_popcount=fingerprints.row_popcount(bank_bits))
+    found = idx >= 0
+    sim = torch.where(found, 1.0 - dist, torch.zeros_like(dist)).sum(dim=1) / found.sum(dim=1).clamp_min(1)
+    same = fingerprints.structure_overlap(bank_bits, val_bits)
+    bank = neighbors.ReactionBank.from_batches(model, [as_tuple(b) for b in train_b], gpu)
+    latent = neighbors.latent_distance(bank, neighbors.reaction_vectors(model, [as_tuple(b) for b in val_b], gpu), k)
+    # (the calibration's Spearman is that of |pred - target| and the third argument: with targets of zero, of `sim` and `latent`)
+    rho = uncertainty.uncertainty_calibration(sim, torch.zeros_like(sim), latent)["spearman"]
+    log.info("structural neighbours (%d bits per reaction, bank of %d training reactions, k %d): mean Tanimoto similarity to the k "
+             "nearest %.4f, to the nearest %.4f; %d of %d validation reactions share a fingerprint with a training reaction",
+             32 * bank_bits.shape[1], bank_bits.shape[0], k, float(sim.mean()), float(same["similarity"].mean()), same["count"],
+             val_bits.shape[0])
+    log.info("  next to the model's embedding: mean latent distance to the k nearest %.4f; Spearman(similarity, latent distance) %.3f",
+             float(latent.mean()), rho)
 
 
 def both_distances(model, train_b, val_b, checkpoint, k, gpu, log):
@@ -286,6 +319,11 @@ def main():
                     "cluster-held-out split and their distance to the training fold next to a random split of the same sizes")
     ap.add_argument("--bootstrap", type=int, default=0, metavar="N", help="listwise task types: after training, the validation metrics "
                     "with 95 %% bootstrap intervals (N resamples of the queries) and the paired test of the best checkpoint against the last epoch")
+    ap.add_argument("--fingerprint-neighbors", type=int, default=0, metavar="K", help="listwise task types: after training, the mean "
+                    "Tanimoto similarity of the validation reactions to their K structurally nearest training reactions next to the latent distance")
+    ap.add_argument("--add-fingerprint", action="store_true", help="listwise task types: train with the product's binary circular "
+                    "fingerprint as the additional features (add_features_dim = --fingerprint-bits)")
+    ap.add_argument("--fingerprint-bits", type=int, default=2048, help="with --add-fingerprint: bits of the fingerprint")
     ap.add_argument("--ig-steps", type=int, default=16, help="with --attribute integrated_gradients: midpoint nodes")
     ap.add_argument("--checkpoint", default="/tmp/reactranker_amd_synthetic/model.pt")
     args = ap.parse_args()
@@ -310,11 +348,16 @@ def main():
         model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
                             add_features_dim=1, task_num=1, ffn_last_layer="no_softplus")
     else:
+        if args.add_fingerprint and world > 1:
+            raise SystemExit("--add-fingerprint runs in one process")
         model = build_model(hidden_size=args.hidden, mpnn_depth=3, mpnn_diff_depth=3, ffn_depth=3, use_bias=True, dropout=0.1,
-                            add_features_dim=1, **head_for(args.task_type))
+                            add_features_dim=args.fingerprint_bits if args.add_fingerprint else 1, **head_for(args.task_type))
     log.info("parameters: %d", param_count(model))
     train_b = make_batches(0, args.queries, args.cands, args.batch_queries, rank, world)
     val_b = make_batches(10 ** 6, max(args.batch_queries, args.queries // 8), args.cands, args.batch_queries, rank, world)
+    if args.add_fingerprint and args.task_type not in PAIRWISE:
+        for b in list(train_b) + list(val_b):             # the product's fingerprint, made on the device, as the additional features
+            b["add"] = fingerprints.feature_generate("binary_morgan_fingerprint", b["p"], num_bits=args.fingerprint_bits, gpu=args.gpu)
     opt = build_optimizer(model.cuda(args.gpu))
     sch = build_lr_scheduler(opt, warmup_epochs=2, total_epochs=args.epochs, train_data_size=args.queries,
                              batch_size=args.batch_queries, init_lr=1e-4, max_lr=1e-3, final_lr=1e-4)
@@ -372,6 +415,8 @@ def main():
         explain_top_candidate(model, val_b[0], args.attribute, args.ig_steps, args.gpu, log)
     if world == 1 and args.neighbors:
         nearest_training_reactions(model, train_b, val_b, args.checkpoint, args.neighbors, args.gpu, log)
+    if world == 1 and args.fingerprint_neighbors:
+        structural_neighbours(model, train_b, val_b, args.fingerprint_neighbors, args.gpu, log)
     if world == 1 and args.mahalanobis:
         both_distances(model, train_b, val_b, args.checkpoint, args.neighbors or 8, args.gpu, log)
     if world == 1 and args.embedding_map:

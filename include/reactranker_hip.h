@@ -1263,6 +1263,73 @@ int rr_center_project_f32(const float* x, int64_t ld, int64_t N, int H,
                           float* sq,             /* [N] or NULL */
                           rr_stream_t stream);
 
+/* Circular (Morgan-style) fingerprints from the packed graph (additive: two new symbols, the ABI revision stays 8).  This
+ * library's own definition: NOT bit-compatible with RDKit's Morgan fingerprints, and without ECFP's duplicate-substructure
+ * removal.  All arithmetic on uint32 with wrap-around:
+ *   fmix(x):  x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16        (murmur3's finaliser)
+ *   step(h, w) = fmix((h ^ w) + 0x9e3779b9)
+ *   rowhash(v[0..n)) = fold h = 0; for c ascending: h = step(h, bits(v[c]))     bits = the f32 pattern, -0.0 taken as +0.0
+ *   id_0[a] = rowhash(f_atoms[a, 0:atom_fdim])          bh[b] = rowhash(bond_cols[b, 0:bond_fdim])
+ *   round r = 1..radius, atom a: m_k = step(bh[b], id_{r-1}[b2a[b]]) over the incoming bonds b = a2b[a,k] != 0 (bond 0 is the
+ *     padding bond), S = sum_k m_k, X = xor_k fmix(m_k ^ 0x7f4a7c15), id_r[a] = step(step(step(id_{r-1}[a], r), S), X)
+ * Both joins are commutative: the ids do not depend on the numbering of atoms or bonds.  Every (a, r), r = 0..radius, a an atom of
+ * molecule m (a_scope[m] = (first atom, atoms); atom 0 is padding and never contributes) contributes j = id_r[a] % num_bits to
+ * row m: bits_out [M, num_bits / 32] uint32 (ld_bits in words), bit j in word j >> 5 at position j & 31, and / or counts_out
+ * [M, num_bits] int32 (ld_counts).  Either may be NULL, not both.  Every word of a row is written; a molecule without atoms
+ * gives a zero row.  bond_cols are the bond-only columns: f_bonds + atom_fdim with f_bonds' pitch, or a [nB, bond_fdim] array.
+ * One wavefront per molecule, the ids and the row in LDS, plain stores at the end (molecules above 256 atoms keep their ids in
+ * the workspace): no global atomics, and a row depends on its molecule only - not on its position in the batch, the other
+ * molecules, the grid or what output and workspace held.  A bond index outside [1, nB) is skipped; a neighbour outside the
+ * molecule's own atoms is read as its first atom; a scope outside [1, nA) gives a zero row (values change, never an address).
+ * Status, all before any launch: RR_ERR_ARG for a null f_atoms / bond_cols / a2b / b2a / workspace / bytes, a null a_scope with
+ * M > 0, both outputs null, nA < 1, nB < 1, M < 0, K < 1, a feature width < 1, a pitch below its width, radius < 0, or num_bits
+ * below 32 or not a multiple of 32; RR_ERR_UNSUPPORTED for radius > RR_FP_MAX_RADIUS, num_bits > RR_FP_MAX_BITS or nA, nB, M
+ * above 2^31 - 1; RR_ERR_WORKSPACE for a workspace below rr_circular_fp_workspace_bytes.  M == 0 returns RR_OK without a launch. */
+#define RR_FP_MAX_RADIUS 8
+#define RR_FP_MAX_BITS 8192
+int rr_circular_fp_workspace_bytes(int64_t nA, int64_t nB, size_t* bytes);
+int rr_circular_fp_u32(const float* f_atoms, int64_t ld_fa, int atom_fdim, const float* bond_cols, int64_t ld_bc, int bond_fdim,
+                       const int32_t* a2b, int K, const int32_t* b2a, const int32_t* a_scope, int64_t nA, int64_t nB, int64_t M,
+                       int radius, int num_bits, uint32_t* bits_out /* nullable */, int64_t ld_bits,
+                       int32_t* counts_out /* nullable */, int64_t ld_counts, void* workspace, size_t workspace_bytes,
+                       rr_stream_t stream);
+
+/* Tanimoto search on bit rows (additive: eight new symbols, the ABI revision stays 8).  This library's own definition.  For query
+ * rows q [M,W] (ld_q) and bank rows bank [N,W] (ld_b), uint32 words in device memory, pitches in words:
+ *   c = popcount(q[m] & bank[n])     u = |q[m]| + |bank[n]| - c     d(m,n) = u == 0 ? 0 : (float)(u - c) / (float)u
+ * one correctly rounded f32 division of exact integers: d = 1 - Tanimoto similarity, and two empty rows are at distance 0.
+ * Order, group exclusion (q_group[m] == b_group[n] >= 0), padding (dist = +inf, idx = -1) and the bank splits with their merge
+ * are rr_knn_f32's (one copy of the list, csrc/topk_list.h): dist [M,k] ascending, ties to the lower bank index; the same bits
+ * for every split count, pitch, alignment and position of the rows; no atomics.  16-byte loads where a pointer and its pitch
+ * allow, 4-byte loads otherwise; the words between W and the pitch never reach a result.
+ *   rr_row_popcount_u32                out[r] = |x[r]|, int32: what the searches take as bank_popcount (NULL: computed into the
+ *                                      workspace)
+ *   rr_tanimoto_knn_u32                the search; k in [1, RR_KNN_MAX_K]; N == 0 writes the padding; M == 0 launches nothing
+ *   rr_tanimoto_count_u32              count[m] = number of non-excluded bank rows with d(m,n) <= radius (radius >= 0, +inf
+ *                                      allowed); N == 0 writes zeros
+ *   rr_tanimoto_knn_workspace_bytes / rr_tanimoto_count_workspace_bytes   the popcounts and the per-split partial results UNDER
+ *                                      THE CURRENT SPLIT SETTING
+ *   rr_tanimoto_splits / rr_tanimoto_set_splits   as rr_knn_set_splits: 0 = automatic, 1 .. 1024 fixed; process-wide, NOT
+ *                                      thread-safe, for the bench tool and the tests
+ *   rr_tanimoto_geometry               query rows per workgroup, bank rows per tile, RR_KNN_MAX_K, RR_TANIMOTO_MAX_WORDS
+ * Status, all before any launch: RR_ERR_ARG for a null q / bank / dist / idx / count / workspace / x / out / bytes, one group
+ * array without the other, a negative M, N or rows, W < 1, k < 1, a pitch below W, a radius that is negative or a NaN, or a split
+ * count outside [0, 1024]; RR_ERR_UNSUPPORTED for k > RR_KNN_MAX_K, W > RR_TANIMOTO_MAX_WORDS or N (count: M or N) above
+ * 2^31 - 1; RR_ERR_WORKSPACE for a workspace below the sizer's value. */
+#define RR_TANIMOTO_MAX_WORDS 256
+int rr_row_popcount_u32(const uint32_t* x, int64_t ld, int64_t rows, int W, int32_t* out, rr_stream_t stream);
+int rr_tanimoto_knn_workspace_bytes(int64_t M, int64_t N, int k, size_t* bytes);
+int rr_tanimoto_knn_u32(const uint32_t* q, int64_t ld_q, int64_t M, const uint32_t* bank, int64_t ld_b, int64_t N, int W, int k,
+                        const int32_t* q_group, const int32_t* b_group, const int32_t* bank_popcount, float* dist, int32_t* idx,
+                        void* workspace, size_t workspace_bytes, rr_stream_t stream);
+int rr_tanimoto_count_workspace_bytes(int64_t M, int64_t N, size_t* bytes);
+int rr_tanimoto_count_u32(const uint32_t* q, int64_t ld_q, int64_t M, const uint32_t* bank, int64_t ld_b, int64_t N, int W,
+                          float radius, const int32_t* q_group, const int32_t* b_group, const int32_t* bank_popcount,
+                          int32_t* count, void* workspace, size_t workspace_bytes, rr_stream_t stream);
+void rr_tanimoto_geometry(int* row_tile, int* bank_tile, int* max_k, int* max_words);
+int rr_tanimoto_splits(void);
+int rr_tanimoto_set_splits(int splits);
+
 /* How many launches of the one-wavefront-per-list kernels (losses, task step, pairwise, uncertainty) have so far opted in
  * to more than 64 KiB of dynamic LDS, in this process.  A kernel stages up to 20 bytes per candidate, so lists above 3276
  * to 5461 candidates need the opt-in, once per kernel and template instantiation.  Today's HIP runtime launches without it

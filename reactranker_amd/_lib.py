@@ -332,6 +332,19 @@ _SIGS = {
     "rr_moments_blocks": (i32, []),
     "rr_moments_set_blocks": (i32, [i32]),
     "rr_center_project_f32": (i32, [c_f32p, i64, i64, i32, c_f32p, c_f32p, i32, c_f32p, c_f32p, c_stream]),
+    "rr_circular_fp_workspace_bytes": (i32, [i64, i64, C.POINTER(C.c_size_t)]),
+    "rr_circular_fp_u32": (i32, [c_f32p, i64, i32, c_f32p, i64, i32, c_i32p, i32, c_i32p, c_i32p, i64, i64, i64, i32, i32,
+                                 C.c_void_p, i64, c_i32p, i64, C.c_void_p, C.c_size_t, c_stream]),
+    "rr_row_popcount_u32": (i32, [C.c_void_p, i64, i64, i32, c_i32p, c_stream]),
+    "rr_tanimoto_knn_workspace_bytes": (i32, [i64, i64, i32, C.POINTER(C.c_size_t)]),
+    "rr_tanimoto_knn_u32": (i32, [C.c_void_p, i64, i64, C.c_void_p, i64, i64, i32, i32, c_i32p, c_i32p, c_i32p, c_f32p, c_i32p,
+                                  C.c_void_p, C.c_size_t, c_stream]),
+    "rr_tanimoto_count_workspace_bytes": (i32, [i64, i64, C.POINTER(C.c_size_t)]),
+    "rr_tanimoto_count_u32": (i32, [C.c_void_p, i64, i64, C.c_void_p, i64, i64, i32, f32, c_i32p, c_i32p, c_i32p, c_i32p,
+                                    C.c_void_p, C.c_size_t, c_stream]),
+    "rr_tanimoto_geometry": (None, [C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    "rr_tanimoto_splits": (i32, []),
+    "rr_tanimoto_set_splits": (i32, [i32]),
     "rr_logcumsumexp_fwd_f32": (i32, [c_f32p, i32, c_f32p, c_stream]),
     "rr_logcumsumexp_bwd_f32": (i32, [c_f32p, c_f32p, c_f32p, i32, c_f32p, c_stream]),
     "rr_pack_sizes": (i32, [C.c_void_p, C.c_void_p, i64, C.c_void_p, i32, C.POINTER(i64), C.POINTER(i64),
@@ -378,6 +391,8 @@ RR_RESAMPLE_MAX_COLS = 32
 RR_RESAMPLE_MAX_ROWS = 1 << 20
 RR_RESAMPLE_BOOTSTRAP, RR_RESAMPLE_SIGNFLIP = 0, 1
 RR_MOMENTS_MAX_H = 1024
+RR_FP_MAX_RADIUS, RR_FP_MAX_BITS = 8, 8192
+RR_TANIMOTO_MAX_WORDS = 256
 ABI_VERSION = 8
 (RR_SAVED_R_MSG, RR_SAVED_R_H, RR_SAVED_P_MSG, RR_SAVED_P_H, RR_SAVED_D_MSG, RR_SAVED_D_HID, RR_SAVED_VECS, RR_SAVED_FFN_H,
  RR_SAVED_R_MSG0_U, RR_SAVED_R_Z1_U) = range(10)

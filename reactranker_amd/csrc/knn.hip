@@ -25,17 +25,18 @@
 // list epilogue above, knn_count_kernel (rr_radius_count_f32, DESIGN section 4k: neighbours within a radius) a counting one
 // that needs neither the LDS distance tile nor a list.  Both form the distance through kn_dist.
 // kn_run is the one copy of the host side of both entries (checks, splits, workspace, the empty bank, norms, tile launch, merge).
+// The sorted list (kn_less, kn_insert, kn_offer, KN_PAD) and the two merge kernels are topk_list.h's, shared with csrc/tanimoto.hip.
 //
 // row_sqnorm_kernel: one wave per row; lane l sums x[h]^2 over h = l, l + 64, ... ascending (product rounded, then added), the
 // 64 partial sums are joined by the butterfly xor 32, 16, 8, 4, 2, 1.  4-byte loads only (a wave reads 256 contiguous bytes).
 #include "row_chain.h"
+#include "topk_list.h"
 
 namespace {
 
 constexpr int KN_ROWS = 64;                       // query rows per workgroup
 constexpr int KN_BANK = 128;                      // bank rows per tile
 constexpr int KN_KC = 64;                         // columns staged per chunk
-constexpr int KN_NT = 256;                        // threads (4 waves)
 constexpr int KN_SP = KN_KC + 4;                  // pitch of the staged operands (== 4 mod 32: 16 rows x 16 bytes hit 64 banks)
 constexpr int KN_DP = KN_BANK + 4;                // pitch of the distance tile
 constexpr int KN_RPP = KN_NT / (KN_KC / 4);       // rows of a chunk the 256 threads stage per pass (16 bytes per thread)
@@ -43,7 +44,6 @@ constexpr int KN_QU = KN_ROWS / KN_RPP, KN_BU = KN_BANK / KN_RPP;   // passes pe
 constexpr int KN_STAGE = (KN_ROWS + KN_BANK) * KN_SP, KN_DT = KN_ROWS * KN_DP;
 constexpr int KN_LDS = KN_STAGE > KN_DT ? KN_STAGE : KN_DT;        // the distance tile reuses the staging buffers
 constexpr int KN_MAX_SPLITS = 1024;
-constexpr int KN_PAD = 0x7fffffff;                // index of an empty slot inside the kernels (N <= 2^31 - 1: above every row)
 
 std::atomic<int> g_splits{0};
 
@@ -76,40 +76,6 @@ __device__ __forceinline__ f32x4 kn_load4(const float* row, int c, int width, bo
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = (row_ok && c + e < width) ? v[e] : 0.f;
   return v;
-}
-
-__device__ __forceinline__ bool kn_less(float d1, int i1, float d2, int i2) { return d1 < d2 || (d1 == d2 && i1 < i2); }
-__device__ __forceinline__ float kn_lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ int kn_lane_i(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-
-// the sorted list (ld, li), one slot per lane: candidate (d, n) takes its place, everything behind it moves one lane up
-__device__ __forceinline__ void kn_insert(float& ld, int& li, float d, int n, int lane) {
-  const bool mine_less = kn_less(ld, li, d, n);
-  const float ud = __shfl_up(ld, 1, 64);
-  const int ui = __shfl_up(li, 1, 64);
-  const bool up_less = lane == 0 || kn_less(ud, ui, d, n);
-  if (!mine_less) {
-    ld = up_less ? d : ud;
-    li = up_less ? n : ui;
-  }
-}
-
-// one candidate per lane: those below the list's slot km1 are inserted, lowest lane first (all 64 lanes active)
-__device__ __forceinline__ void kn_offer(float& ld, int& li, float d, int n, bool valid, int km1, int lane) {
-  float td = kn_lane_f(ld, km1);
-  int ti = kn_lane_i(li, km1);
-  uint64_t mask = __ballot(valid && kn_less(d, n, td, ti));
-  while (mask != 0) {                             // (uniform)
-    const int src = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mask));
-    mask &= mask - 1;
-    const float cd = kn_lane_f(d, src);
-    const int cn = kn_lane_i(n, src);
-    if (kn_less(cd, cn, td, ti)) {
-      kn_insert(ld, li, cd, cn, lane);
-      td = kn_lane_f(ld, km1);
-      ti = kn_lane_i(li, km1);
-    }
-  }
 }
 
 // The tile walk, the one copy of it: the workgroup's 64 query rows against its contiguous range of bank tiles, both operands
@@ -366,35 +332,6 @@ __global__ void __launch_bounds__(KN_NT, 2) knn_count_kernel(const KnCountParams
     for (int w = 0; w < KN_NT / 64; ++w) c += s_cnt[w][tid];
     if (P.S == 1) P.out[m] = c;
     else P.part[m * P.S + blockIdx.y] = c;
-  }
-}
-
-// one thread per row: the S partial counts of a row, in split order (S == 0: zeros)
-__global__ void __launch_bounds__(KN_NT) knn_count_merge_kernel(const int32_t* part, int64_t M, int S, int32_t* out) {
-  const int64_t m = static_cast<int64_t>(blockIdx.x) * KN_NT + threadIdx.x;
-  if (m >= M) return;
-  int c = 0;
-  for (int s = 0; s < S; ++s) c += part[m * S + s];
-  out[m] = c;
-}
-
-// one wave per row: the S partial lists of a row -> the row's result (S == 0: all padding)
-__global__ void __launch_bounds__(KN_NT) knn_merge_kernel(const float* part_d, const int32_t* part_i, int64_t M, int S, int k,
-                                                          float* out_d, int32_t* out_i) {
-  const int lane = threadIdx.x & 63;
-  const int64_t m = static_cast<int64_t>(blockIdx.x) * (KN_NT / 64) + (threadIdx.x >> 6);
-  if (m >= M) return;                             // (uniform per wave)
-  float ld = __builtin_inff();
-  int li = KN_PAD;
-  for (int s = 0; s < S; ++s) {
-    const int64_t o = (m * S + s) * k + (lane < k ? lane : 0);
-    const float d = part_d[o];
-    const int n = part_i[o];
-    kn_offer(ld, li, d, n, lane < k && n != KN_PAD, k - 1, lane);
-  }
-  if (lane < k) {
-    out_d[m * k + lane] = ld;
-    out_i[m * k + lane] = li == KN_PAD ? -1 : li;
   }
 }
 
